@@ -1,6 +1,14 @@
 """Throughput bench of the KNN hot path (BASELINE.json metric: distance pairs/s).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config A|B|C|C1|L] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config A|B|C|C1|L] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set up, W warmup steps, K timed
+steps, the outputs written if --dump-outputs is given, one JSON line (value, ms_per_step, the
+timed steps' own stage times and the roofline derived from them).  --full adds everything that
+takes runs of its own: the untimed profiled steps (all stages, select_stage), the uncached
+steps, the oracle bit-match, the host-buffer calls, the CPU baselines, and on multi-rank lines
+the RCCL exchange check; each has its own --no-* switch.  --dump-outputs DIR writes what the
+last timed step returned to its caller (the predictions) as DIR/<name>.npy.
 
 One process per GPU (torchrun for N > 1).  Workload A (default, BASELINE configs[2]):
 1,000,000 train x 100,000 query rows x 128-d fp32, k = 10, 10 classes, synthetic rows from
@@ -30,7 +38,7 @@ baseline is the reference's own multi-thread binary (and serial main) on the sam
 
 Rank 0 prints one JSON line.  roofline: the dominant kernel (k_gemm_fused, the fused-norm
 bf16 filter; k_gemm_filter for the fp32 / split operands) timed with
-HIP events on its own stream; cpu_baseline: the reference's pthreads KNN (oracle/_ref,
+HIP events on its own stream; cpu_baseline (--full): the reference's pthreads KNN (oracle/_ref,
 built -O0 as shipped) on a bounded sample, else the C restatement labelled "port".
 """
 import argparse
@@ -75,6 +83,27 @@ MPIEXEC = os.environ.get("KNN_MPIEXEC", "/opt/conda/bin/mpiexec")
 
 def _ref_exe(name):
     return os.path.join(REPO, "oracle", "_ref", name)
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(directory, arrays, rank=0, world=1):
+    """--dump-outputs: the arrays the timed path's last step gave its caller, as
+    DIR/<name>.npy in float32 (class labels are small integers, exact in float32).  The inputs
+    are the same from run to run (the counter-based generator / the ARFF pair), so two builds
+    can be compared file for file.  An array over its share of DUMP_LIMIT_BYTES is cut to a
+    fixed, seeded sample of its rows (sorted, the same rows in every run).  Ranks above 0 of a
+    multi-rank run write <name>_rank<r>.npy (each rank holds its own queries' outputs)."""
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        rows = budget // (4 * max(1, a.size // max(1, len(a))))
+        if len(a) > rows:
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), rows, replace=False))]
+        suffix = f"_rank{rank}" if world > 1 and rank else ""
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), a.astype(np.float32))
 
 
 def cpu_baseline(d, k, C, seed, kind=0, nt_cfg=1_000_000):
@@ -215,9 +244,8 @@ def bench_arff(args, knn, torch, local):
     dev = torch.device("cuda", local)
     # the timed calls run without events (each timed event pair costs a call ~6 us of its 0.1 ms:
     # scripts/diag/sync_latency.hip); a second context with events around the dominant stage
-    # only then repeats the same steps for the kernel's time (stages_ms, roofline)
+    # only then repeats the same steps for the kernel's time (stages_ms, roofline; --full)
     ctx = knn.Context(local, algo=args.algo, train_splits=args.splits)
-    pctx = knn.Context(local, algo=args.algo, train_splits=args.splits, profile=3)
     # device rows are 16-B aligned: [n][ld] with ld = 12 for d = 11 (the pad column is never read)
     ld = (d + 3) // 4 * 4
     train = torch.zeros((nt, ld), dtype=torch.float32, device=dev)
@@ -235,6 +263,33 @@ def bench_arff(args, knn, torch, local):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     got = pred.cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"pred": got})
+    pairs = float(nt) * nq * args.steps
+    out = {
+        "metric": METRIC, "value": pairs / elapsed, "unit": "pairs/s", "n_gpus": 1,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+        "data": "the reference's large ARFF pair (tests/data), parsed by the boundary's reader",
+        "config": {"workload": f"L: large-train.arff x large-test.arff ({nt} x {nq} x {d}-d), k={k}",
+                   "n_train": nt, "n_query_total": nq, "d": d, "k": k, "classes": C,
+                   "parallelism": "single GPU, direct form"},
+        "queries_per_s": nq * args.steps / elapsed,
+    }
+    if args.full:
+        out.update(arff_full(args, knn, torch, local, (tf, tl, qf, ql), (train, labels, test, pred), got))
+    print(json.dumps(out), flush=True)
+    ctx.close()
+
+
+def arff_full(args, knn, torch, local, host_arrays, dev_arrays, got):
+    """--full on config L: the runs beside the timed steps (kernel time by events on a second
+    context, the golden comparison, the host-buffer path, the CPU baselines)."""
+    nt, nq, d, k, C = CONFIGS["L"][:5]
+    tf, tl, qf, ql = host_arrays
+    train, labels, test, pred = dev_arrays
+    C = int(tl.max()) + 1
+    pctx = knn.Context(local, algo=args.algo, train_splits=args.splits, profile=3)
     stage_sum = {}
     ppred = torch.empty_like(pred)
     for step in range(args.warmup + args.steps):
@@ -255,7 +310,6 @@ def bench_arff(args, knn, torch, local):
         host_ms[phase] = round(1e3 * (time.perf_counter() - t1), 3)
     hctx.close()
     cm = knn.computeConfusionMatrix(got, ql, C)
-    pairs = float(nt) * nq * args.steps
     stages = {n: v / args.steps for n, v in stage_sum.items()}
     # the dominant kernel: AUTO picks the direct form here -- k_direct_rows for d <= 16, k <= 16
     # (config L: its segments merged by its own last wave per query group, round 6), else
@@ -280,15 +334,7 @@ def bench_arff(args, knn, torch, local):
                 "merge": ("fused: each query group's last segment wave merges + votes (round 6)"
                           if kernel == "k_direct_rows" else "k_merge_vote"),
                 "note": "launch/latency bound: 52.9 M pairs is ~22 us of VALU at peak"}
-    out = {
-        "metric": METRIC, "value": pairs / elapsed, "unit": "pairs/s", "n_gpus": 1,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-        "data": "the reference's large ARFF pair (tests/data), parsed by the boundary's reader",
-        "config": {"workload": f"L: large-train.arff x large-test.arff ({nt} x {nq} x {d}-d), k={k}",
-                   "n_train": nt, "n_query_total": nq, "d": d, "k": k, "classes": C,
-                   "parallelism": "single GPU, direct form"},
-        "queries_per_s": nq * args.steps / elapsed,
+    return {
         "stages_ms": {n: round(v, 4) for n, v in stages.items()},
         "stages_source": "a second run of the same steps with HIP events around the dominant stage",
         "bit_match": {"predictions_equal_reference": bool(np.array_equal(got, want)),
@@ -298,8 +344,6 @@ def bench_arff(args, knn, torch, local):
         "roofline": roof,
         "cpu_baseline": None if args.no_cpu_baseline else cpu_baseline_arff(k),
     }
-    print(json.dumps(out), flush=True)
-    ctx.close()
 
 
 def host_buffer_times(knn, local, algo, train, labels, test, k, C, pred_dev):
@@ -468,6 +512,14 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: per config)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps (default: per config)")
     ap.add_argument("--config", default="A", choices=sorted(CONFIGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller (the "
+                         "predictions) as DIR/<name>.npy, float32; the inputs are the same in every run")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, run everything else the bench measures or checks: untimed "
+                         "profiled steps (all stages, select_stage), uncached steps, the oracle bit-match, the "
+                         "host-buffer calls, the CPU baselines, the multi-rank RCCL exchange check "
+                         "(the --no-* switches below drop single parts of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--strong", action="store_true",
                     help="(the default) test-sharded configs: split BASELINE's fixed n_query set by the "
@@ -499,6 +551,8 @@ def main():
         args.steps = DEFAULT_STEPS[args.config]
     if args.warmup is None:
         args.warmup = {"A": 3, "L": 20}.get(args.config, 1)
+    if not args.full:  # a plain run: none of the parts that take runs of their own
+        args.no_cpu_baseline = args.no_host_path = args.no_bit_match = args.no_uncached = True
 
     import torch
     import torch.distributed as dist
@@ -632,20 +686,24 @@ def main():
     elapsed = float(t.item())
     stats = ctx.stats()
     pred_timed = pred.clone()  # the timed steps' predictions (bit_match below checks these)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"pred": pred_timed.cpu().numpy()}, rank, world)
     # select stage (k_rescore): one untimed diagnostic pass counts the filter's candidates,
     # giving the rescore's algorithmic bytes (select stage vs HBM)
     select = None
-    # untimed diagnostic steps (every rank: a train-sharded step is collective) on a context
-    # with every stage timed and the filter's candidates counted (profile=2); the first builds
-    # its train operand cache like the warmup did, the second is the one reported
-    ctx.close()
-    ctx = knn.Context(local, algo=args.algo, train_splits=args.splits, profile=2,
-                      cache_train=not args.no_train_cache)
-    if comm is not None:
-        comm.ctx = ctx  # the communicator is bound to a device, the context per call
-    step()
-    diag_stages = step()
-    if "rescore" in stage_sum:
+    diag_stages = {}
+    if args.full:
+        # untimed diagnostic steps (every rank: a train-sharded step is collective) on a context
+        # with every stage timed and the filter's candidates counted (profile=2); the first builds
+        # its train operand cache like the warmup did, the second is the one reported
+        ctx.close()
+        ctx = knn.Context(local, algo=args.algo, train_splits=args.splits, profile=2,
+                          cache_train=not args.no_train_cache)
+        if comm is not None:
+            comm.ctx = ctx  # the communicator is bound to a device, the context per call
+        step()
+        diag_stages = step()
+    if args.full and "rescore" in stage_sum:
         cand = ctx.stats()["candidates"]
         stats["candidates"] = cand  # the timed steps do not count them (profile=2 pass only)
         esz = 2 if dtype == "bf16" else 4
@@ -760,7 +818,7 @@ def main():
             "queries_per_s": total_q * args.steps / elapsed,
             "stages_ms": {n: round(v, 3) for n, v in stages.items()},
             "stages_source": ("timed steps for " + ", ".join(sorted(stage_sum)) +
-                              "; one untimed profiled step for the rest"),
+                              ("; one untimed profiled step for the rest" if args.full else "")),
             "gemm_stats": stats,
             "predictions_gathered": gathered,
             "rccl_comm_ranks": rccl_ranks,
@@ -777,9 +835,9 @@ def main():
             "host_buffers": host,
         }
         line = out
-    # multi-rank lines: the train-sharded C-ABI path over a real RCCL communicator of all ranks,
-    # checked against the whole-train path (KNN_BENCH_XCHECK=1 runs it at one rank too)
-    if (world > 1 and not share) or os.environ.get("KNN_BENCH_XCHECK") == "1":
+    # multi-rank --full lines: the train-sharded C-ABI path over a real RCCL communicator of all
+    # ranks, checked against the whole-train path (KNN_BENCH_XCHECK=1 runs it at one rank too)
+    if (args.full and world > 1 and not share) or os.environ.get("KNN_BENCH_XCHECK") == "1":
         xc = run_with_watchdog(lambda: rccl_exchange_check(knn, torch, dist, local, world, rank, share, seed),
                                XCHECK_LIMIT_S, line, rank)
         if line is not None:

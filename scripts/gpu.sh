@@ -33,7 +33,7 @@ for spec in "${SPECS[@]}"; do
   tag=${W[0]}; cfg=${W[1]}
   EV=(); AR=()
   for w in "${W[@]:2}"; do if [[ $w == --* ]]; then AR+=("$w"); else EV+=("$w"); fi; done
-  env "${EV[@]}" timeout -k 10 400 python -u bench.py --config $cfg --steps ${STEPS:-3} --warmup ${WARMUP:-1} \
+  env "${EV[@]}" timeout -k 10 400 python -u bench.py --full --config $cfg --steps ${STEPS:-3} --warmup ${WARMUP:-1} \
       --no-cpu-baseline --no-host-path --no-bit-match --no-uncached "${AR[@]}" > gpurun_out/${TAG}_$tag.log 2>&1 \
       || { echo "bench $tag failed"; tail -5 gpurun_out/${TAG}_$tag.log; exit 1; }
   summ gpurun_out/${TAG}_$tag.log
@@ -59,7 +59,7 @@ if [ "$TESTS" = 1 ]; then
 fi
 
 for cfg in $BENCHES; do
-  extra=""
+  extra="--full"
   timeout -k 10 600 python -u bench.py --config $cfg $extra > gpurun_out/${TAG}_bench_$cfg.log 2>&1 \
       || { echo "bench $cfg failed"; tail -5 gpurun_out/${TAG}_bench_$cfg.log; exit 1; }
   echo "$cfg: $(tail -1 gpurun_out/${TAG}_bench_$cfg.log | cut -c1-300)"

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd /tmp && export TMPDIR=/tmp
 OUT=$R/gpurun_out
 ARGS=${BENCH_ARGS:-"--config C1 --nq 64000"}
-BENCH="$R/bench.py $ARGS --steps 1 --warmup 0 --no-cpu-baseline"
+BENCH="$R/bench.py --full $ARGS --steps 1 --warmup 0 --no-cpu-baseline"
 if [ -n "$LIST" ]; then timeout -s KILL 60 rocprofv3 -L > $OUT/pmc_list.txt 2>&1; fi
 i=0
 while read -r SET; do

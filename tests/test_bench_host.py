@@ -52,8 +52,31 @@ def test_bench_flags():
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True,
                        timeout=120)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--config", "--shard", "--strong", "--data", "--no-bit-match"):
+    for flag in ("--gpus", "--steps", "--warmup", "--config", "--shard", "--strong", "--data", "--no-bit-match",
+                 "--full", "--dump-outputs"):
         assert flag in r.stdout
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files of the whole array, or of a fixed seeded sample of its
+    rows (the same rows in every run) when it is over its share of the size limit."""
+    import numpy as np
+    b = _bench()
+    pred = (np.arange(1000) % 10).astype(np.int32)
+    b.dump_outputs(str(tmp_path / "a"), {"pred": pred})
+    got = np.load(tmp_path / "a" / "pred.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, pred)
+    b.dump_outputs(str(tmp_path / "a"), {"pred": pred}, rank=1, world=2)
+    assert np.array_equal(np.load(tmp_path / "a" / "pred_rank1.npy"), pred)
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 400)
+    two_d = np.arange(2000, dtype=np.int32).reshape(1000, 2)
+    for name in ("b", "c"):
+        b.dump_outputs(str(tmp_path / name), {"pred": pred, "idx": two_d})
+    s1, s2 = np.load(tmp_path / "b" / "pred.npy"), np.load(tmp_path / "c" / "pred.npy")
+    i1 = np.load(tmp_path / "b" / "idx.npy")
+    assert s1.shape == (50,) and i1.shape == (25, 2) and np.array_equal(s1, s2)
+    assert s1.nbytes + i1.nbytes <= 400
+    assert np.array_equal(i1[:, 1], i1[:, 0] + 1) and np.all(np.diff(i1[:, 0]) > 0)
 
 
 def test_default_scaling_is_strong():
