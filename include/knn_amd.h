@@ -256,6 +256,57 @@ knn_status knn_shard_policy(int64_t n_train, int64_t n_query, int32_t d, int32_t
 knn_status knn_exchange_layout(int64_t nq, int32_t k, int32_t world, int32_t rank, int64_t* send_off,
                                int64_t* send_cnt, int64_t* recv_off, int64_t* recv_cnt);
 
+/*
+ * k-sweep: the predictions (and accuracy) for EVERY k in 1..kmax from one top-kmax pass.
+ * The neighbour lists ascend by (distance, train index), so the k nearest of a query are the
+ * first k entries of its kmax nearest; only the vote (main.cpp:64-78) is redone per prefix
+ * (k_vote_sweep).  Row k - 1 of pred_all, laid out [kmax][nq], is exactly what the predict
+ * entry points return for that k, and can go straight into knn_confusion_matrix_device.
+ *
+ * Leave-one-out (self_base >= 0): query q is train row self_base + q, and that row is taken
+ * out of its own neighbour list.  The prediction for row i at k then equals the reference's
+ * KNN (main.cpp:25) on the train set with row i removed: removing a row keeps the order of the
+ * others, so the lower-index tie rule is unchanged.  The pass asks for kin = kmax + 1
+ * neighbours; the entry equal to self_base + q is removed, and when it is absent -- at least
+ * kin rows with a lower index tie or beat the self row -- the last entry is dropped, the first
+ * kmax being right already.  The caller passes as `test` the slice of train rows
+ * [self_base, self_base + nq).  self_base < 0: no exclusion, kin = kmax.
+ *
+ * knn_vote_sweep_device: the vote alone, on lists the caller already holds: d_idx[nq][idx_stride]
+ *   (the first kin entries of a row: train rows ascending by (distance, index), -1 = none), as
+ *   written by knn_predict_device (d_topk_idx), knn_merge_vote_device or
+ *   knn_predict_train_sharded -- a train-sharded run gets its sweep without a new collective.
+ *   d_train_labels is indexed by the list's (global) train rows.  With self_base >= 0 the
+ *   effective list has kmax = kin - 1 entries, else kmax = kin.
+ * knn_sweep_device: one top-kin pass over device datasets (the pipeline of knn_predict_device,
+ *   without its vote) into context workspace, then k_vote_sweep on the same stream; one
+ *   synchronisation.  d_topk_dist / d_topk_idx (optional) receive the [nq][kmax] lists after
+ *   self-removal.  Needs 1 <= kmax, kin <= n_train, kin <= 1024, and with self_base:
+ *   self_base + nq <= n_train.  With profile = 1 the stage times hold the pass's stages and
+ *   "vote_sweep".
+ * knn_sweep: host buffers in and out (the reference-style callers).  Train is uploaded and
+ *   cached as in knn_predict; the queries go through one device slot, one batch after another:
+ *   this path is NOT pipelined (no upload / compute / download overlap).  out_correct is summed
+ *   over the batches on the host.
+ * Outputs: d_query_labels (int32[nq]), d_pred_all (int32[kmax][nq]) and d_correct
+ *   (int64[kmax], overwritten: correct[k - 1] = queries whose prediction for k equals their
+ *   label; needs the query labels) are each optional, but not all three may be NULL.
+ * KNN_ERANGE if a prefix reaches a missing entry (that k predicts 0), KNN_EINVAL for a train
+ * label outside [0, num_classes).  There is no multi-rank driver: test-sharded callers run the
+ * sweep on their own queries and sum `correct` over the ranks themselves.
+ */
+knn_status knn_vote_sweep_device(knn_ctx* ctx, int64_t nq, int32_t kin, int32_t num_classes,
+                                 const int32_t* d_idx, int64_t idx_stride, const int32_t* d_train_labels,
+                                 int64_t self_base, const int32_t* d_query_labels, int32_t* d_pred_all,
+                                 int64_t* d_correct, void* hip_stream);
+knn_status knn_sweep_device(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test, int32_t kmax,
+                            int32_t num_classes, int64_t self_base, const int32_t* d_query_labels,
+                            int32_t* d_pred_all, int64_t* d_correct, float* d_topk_dist, int32_t* d_topk_idx,
+                            void* hip_stream);
+knn_status knn_sweep(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test, int32_t kmax,
+                     int32_t num_classes, int64_t self_base, const int32_t* query_labels,
+                     int32_t* out_pred_all, int64_t* out_correct);
+
 /* Per-stage device times (ms) of the last predict call when opts.profile >= 1.
  * names: optional array of n const char* to receive stage names. Returns the
  * number of stages recorded (<= n). */

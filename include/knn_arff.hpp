@@ -169,6 +169,13 @@ private:
 int* KNN(ArffData* train, ArffData* test, int k);
 // mpi.cpp:26 -- predictions for test rows [start, end), malloc'd int[end-start].
 int* KNN(ArffData* train, ArffData* test, int k, int start, int end);
+// k-sweep (knn_sweep; no reference counterpart): the predictions of KNN(train, test, k) for
+// every k in 1..kmax from one pass, malloc'd int[kmax * n_test] laid out [kmax][n_test] (row
+// k - 1 is KNN(train, test, k)'s result), caller frees.  Runs on the first device.
+int* KNN_sweep(ArffData* train, ArffData* test, int kmax);
+// Leave-one-out on the train set: row i's predictions for every k in 1..kmax with row i taken
+// out of the train set, malloc'd int[kmax * n_train] laid out [kmax][n_train].
+int* KNN_sweep_loo(ArffData* train, int kmax);
 // main.cpp:87 -- calloc'd int[C*C], C = dataset->num_classes(), row = true class.
 int* computeConfusionMatrix(int* predictions, ArffData* dataset);
 // main.cpp:102

@@ -12,6 +12,8 @@ Names follow the reference (srna99/KNN-using-p_threads-and-MPI):
 * ``shard_range(n, world, rank)``              multi-thread.cpp:154-158 / mpi.cpp:141-170
 * ``train_sharded_predict(...)``               train-sharded KNN over ranks:
   per-shard exact top-k -> all-to-all of neighbour lists -> merge + vote
+* ``Context.sweep_device / loo_device / vote_sweep_device / sweep`` and ``best_k``: the
+  predictions and correct counts for every k <= K from one top-K pass (no reference counterpart)
 
 Features are fp32 or bf16.  Host bf16 arrays are numpy ``uint16`` holding bf16 bits
 (``to_bf16_bits`` / ``bf16_bits_to_f32``); device tensors are ``torch.bfloat16``.
@@ -102,6 +104,9 @@ def load_library(path=LIB_PATH):
         "knn_predict_device": (I32, [P, DS, DS, I32, I32, P, P, P, P]),
         "knn_shard_topk_device": (I32, [P, DS, DS, I32, I32, I64, P, P]),
         "knn_merge_vote_device": (I32, [P, I32, I64, I32, I32, P, P, P, P, P]),
+        "knn_vote_sweep_device": (I32, [P, I64, I32, I32, P, I64, P, I64, P, P, P, P]),
+        "knn_sweep_device": (I32, [P, DS, DS, I32, I32, I64, P, P, P, P, P, P]),
+        "knn_sweep": (I32, [P, DS, DS, I32, I32, I64, P, P, P]),
         "knn_stage_times": (I32, [P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(F), I32]),
         "knn_last_stats": (I32, [P, ctypes.POINTER(I64), I32]),
         "knn_generate": (I32, [P, P, P, I64, I64, I32, I32, I32, I32, ctypes.c_uint64,
@@ -446,6 +451,89 @@ class Context:
             None if dist is None else dist.data_ptr(), None if idx is None else idx.data_ptr(),
             self._stream(stream, rec)))
 
+    def sweep_device(self, train, labels, test, kmax, num_classes, query_labels=None, pred_all=None,
+                     self_base=None, dist=None, idx=None, stream=None, d=None):
+        """Predictions (and correct counts) for every k in 1..kmax from one top-kmax pass
+        (knn_sweep_device).  Returns (pred_all int32 [kmax][nq], correct int64 [kmax] or None
+        without query_labels) as device tensors; pred_all[k - 1] is predict_device's pred for k.
+        self_base: query q is train row self_base + q and is left out of its own neighbours
+        (test must be those train rows).  dist / idx (optional) receive the [nq][kmax] lists."""
+        import torch
+        self._on_device(train)
+        self._note_train(train)
+        tr = _device_dataset(train, labels, d)
+        te = _device_dataset(test, None, d)
+        if pred_all is None:
+            pred_all = torch.empty((kmax, te.n), dtype=torch.int32, device=test.device)
+        _check_tensor(pred_all, "pred_all", torch.int32, kmax * te.n)
+        _outputs(te.n, kmax, None, dist, idx)
+        correct = None
+        if query_labels is not None:
+            _check_tensor(query_labels, "query_labels", torch.int32, te.n)
+            correct = torch.empty(kmax, dtype=torch.int64, device=test.device)
+        self._check(self.lib.knn_sweep_device(
+            self.h, ctypes.byref(tr), ctypes.byref(te), kmax, num_classes, -1 if self_base is None else self_base,
+            None if query_labels is None else query_labels.data_ptr(), pred_all.data_ptr(),
+            None if correct is None else correct.data_ptr(), None if dist is None else dist.data_ptr(),
+            None if idx is None else idx.data_ptr(), self._stream(stream, test)))
+        return pred_all, correct
+
+    def loo_device(self, train, labels, kmax, num_classes, pred_all=None, dist=None, idx=None, stream=None,
+                   d=None):
+        """Leave-one-out on the train set: sweep_device with the train tensor as the queries,
+        every row left out of its own neighbours, scored against its own label."""
+        return self.sweep_device(train, labels, train, kmax, num_classes, query_labels=labels, pred_all=pred_all,
+                                 self_base=0, dist=dist, idx=idx, stream=stream, d=d)
+
+    def vote_sweep_device(self, idx, train_labels, num_classes, query_labels=None, pred_all=None,
+                          self_base=None, kin=None, stream=None):
+        """The prefix votes alone (knn_vote_sweep_device) on neighbour lists idx int32
+        [nq][stride] -- predict_device's idx, merge_vote_device's, ... -- of which the first kin
+        entries per row are read (default: all).  train_labels is indexed by the lists' train
+        rows.  Returns (pred_all [kmax][nq], correct or None); kmax = kin, or kin - 1 with
+        self_base."""
+        import torch
+        self._on_device(idx)
+        if idx.dim() != 2:
+            raise KnnError(KNN_EINVAL, "idx must be a 2-D [nq][stride] tensor")
+        _check_tensor(idx, "idx", torch.int32)
+        _check_tensor(train_labels, "train_labels", torch.int32)
+        nq, stride = idx.shape
+        kin = stride if kin is None else kin
+        kmax = kin - (0 if self_base is None else 1)
+        if pred_all is None:
+            pred_all = torch.empty((max(kmax, 0), nq), dtype=torch.int32, device=idx.device)
+        _check_tensor(pred_all, "pred_all", torch.int32, max(kmax, 0) * nq)
+        correct = None
+        if query_labels is not None:
+            _check_tensor(query_labels, "query_labels", torch.int32, nq)
+            correct = torch.empty(max(kmax, 0), dtype=torch.int64, device=idx.device)
+        self._check(self.lib.knn_vote_sweep_device(
+            self.h, nq, kin, num_classes, idx.data_ptr(), stride, train_labels.data_ptr(),
+            -1 if self_base is None else self_base, None if query_labels is None else query_labels.data_ptr(),
+            pred_all.data_ptr(), None if correct is None else correct.data_ptr(), self._stream(stream, idx)))
+        return pred_all, correct
+
+    def sweep(self, train_feat, train_labels, test_feat, kmax, num_classes=None, query_labels=None,
+              self_base=None):
+        """Host arrays in, host arrays out (knn_sweep; not pipelined): (pred_all int32
+        [kmax][nq], correct int64 [kmax] or None without query_labels)."""
+        tr, keep1 = _dataset(train_feat, train_labels)
+        te, keep2 = _dataset(test_feat)
+        if num_classes is None:
+            num_classes = int(keep1[1].max()) + 1 if keep1[1].size else 1
+        pred_all = np.zeros((max(kmax, 0), te.n), np.int32)
+        ql = None if query_labels is None else np.ascontiguousarray(query_labels, dtype=np.int32)
+        if ql is not None and ql.size < te.n:
+            raise KnnError(KNN_EINVAL, f"query_labels holds {ql.size} elements, needs {te.n}")
+        correct = None if ql is None else np.zeros(max(kmax, 0), np.int64)
+        if self.cache_train:
+            self._train_key = keep1
+        self._check(self.lib.knn_sweep(self.h, ctypes.byref(tr), ctypes.byref(te), kmax, num_classes,
+                                       -1 if self_base is None else self_base, _ptr(ql), _ptr(pred_all),
+                                       _ptr(correct)))
+        return pred_all, correct
+
     def generate(self, feat, labels, row0, d, kind, seed, stream_id, num_classes, dtype=None,
                  stream=None):
         """Fill a device tensor [n][ld] (and labels) with the synthetic rows of SURVEY.md 8d.
@@ -714,6 +802,15 @@ def KNN_range(train, test, k, start, end, ctx=None):
     if k <= 0:
         return np.zeros(end - start, np.int32)
     return (ctx or default_context()).predict(tf, tl, qf, k, int(np.max(tl)) + 1, start, end)
+
+
+def best_k(correct):
+    """The k a sweep's correct counts choose: the smallest k among those with the most correct
+    (correct[k - 1] belongs to k; a numpy array, a list or a tensor)."""
+    c = correct.cpu().numpy() if hasattr(correct, "cpu") else np.asarray(correct)
+    if c.ndim != 1 or c.size == 0:
+        raise KnnError(KNN_EINVAL, "correct must be a non-empty 1-D array")
+    return int(np.argmax(c)) + 1  # argmax returns the first maximum
 
 
 def computeConfusionMatrix(predictions, labels, num_classes):

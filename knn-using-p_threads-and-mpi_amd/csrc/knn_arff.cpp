@@ -775,6 +775,41 @@ int* KNN(ArffData* train, ArffData* test, int k, int start, int end) {
     return pred;
 }
 
+// the k-sweep on the first device: test == train with self-exclusion for leave-one-out
+static int* sweep_on_device0(ArffData* train, ArffData* test, int kmax, bool loo) {
+    const KnnFlatView& tr = train->flat();
+    const KnnFlatView& te = test->flat();
+    if (kmax < 1) throwf("KNN_sweep: kmax=%d must be >= 1", kmax);
+    if (tr.d != te.d) throwf("KNN_sweep: train has %d features, test has %d", tr.d, te.d);
+    int* pred = (int*)std::malloc(sizeof(int) * (size_t)kmax * (size_t)(te.n > 0 ? te.n : 1));
+    if (!pred) throwf("KNN_sweep: out of memory");
+    knn_dataset dtr{tr.feat.data(), tr.labels.data(), tr.n, tr.d, tr.ld, KNN_F32};
+    knn_dataset dte{te.feat.data(), nullptr, te.n, te.d, te.ld, KNN_F32};
+    std::string why;
+    knn_status s = KNN_OK;
+    try {
+        std::vector<knn_ctx*>& cs = contexts();
+        std::lock_guard<std::mutex> busy(*devices().busy[0]);
+        s = knn_set_generation(cs[0], tr.uid);
+        if (s == KNN_OK)
+            s = knn_sweep(cs[0], &dtr, &dte, kmax, (int)train->num_classes(), loo ? 0 : -1, nullptr,
+                          reinterpret_cast<int32_t*>(pred), nullptr);
+        if (s != KNN_OK) why = knn_last_error(cs[0]);
+    } catch (...) {
+        std::free(pred);
+        throw;
+    }
+    if (s != KNN_OK) {
+        std::free(pred);
+        throwf("KNN_sweep: %s (status %d)", why.c_str(), (int)s);
+    }
+    return pred;
+}
+
+int* KNN_sweep(ArffData* train, ArffData* test, int kmax) { return sweep_on_device0(train, test, kmax, false); }
+
+int* KNN_sweep_loo(ArffData* train, int kmax) { return sweep_on_device0(train, train, kmax, true); }
+
 void* KNN(void* params) {
     arguments* a = static_cast<arguments*>(params);
     predict_range(a->train, a->test, a->k, a->start, a->end, predictions + a->start);

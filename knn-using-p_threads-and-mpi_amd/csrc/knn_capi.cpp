@@ -95,6 +95,9 @@ struct knn_ctx {
     uint32_t finish_seq = 0;
     int32_t* ctrl_host_dev = nullptr;  // its device address (k_finish writes it)
     bool ctrl_clean = false;  // the status words are zero (the last call ended in k_finish)
+    // k-sweep (knn_sweep_device / knn_sweep): the top-kin lists of the pass, and the host entry
+    // point's device copies of its outputs and query labels; sized once and grown like the others
+    DBuf sw_dist, sw_idx, sw_pred, sw_ql, sw_correct;
     DBuf arrive;              // k_direct_rows' fused merge: per query group, segments finished
     bool arrive_clean = false;  // arrive is all zero (the last launch ran to completion)
     bool merge_kernel = false;  // study switch KNN_DIRECT_MERGE_KERNEL=1: k_direct_rows' segments via k_merge_vote
@@ -355,8 +358,10 @@ knn_status run_direct_tile(knn_ctx* c, const knn_dataset* tr, const knn_dataset*
         // one launch, no k_merge_vote pass (config L: 0.012 ms of merge + a launch, round 6)
         const int64_t groups = knn_direct_rows_groups(te->n);
         const void* before = c->arrive.p;
+        const size_t had = c->arrive.bytes;
         HIP_OR_FAIL(c, c->arrive.ensure(sizeof(int32_t) * (size_t)groups));
-        if (c->arrive.p != before) c->arrive_clean = false;
+        // (a grown buffer may come back at the old address: its new tail is not zero yet)
+        if (c->arrive.p != before || c->arrive.bytes != had) c->arrive_clean = false;
         if (!c->arrive_clean) HIP_OR_FAIL(c, hipMemsetAsync(c->arrive.p, 0, c->arrive.bytes, st));
         c->arrive_clean = false;  // (set again when the call's stream synchronises)
         a.arrive = c->arrive.as<int32_t>();
@@ -859,7 +864,7 @@ void knn_destroy(knn_ctx* c) {
     (void)hipSetDevice(c->device);
     for (DBuf* b : {&c->tnorm, &c->tnp, &c->qnorm, &c->gthr, &c->cnt, &c->cand,
                     &c->fb_list, &c->ctrl, &c->scratch, &c->split_t, &c->split_q, &c->pad_t, &c->seg_rec, &c->arrive, &c->tmax, &c->tsmax, &c->qstat, &c->tblk, &c->tctrl, &c->cursor, &c->lshare, &c->h_train, &c->h_labels, &c->h_test, &c->h_pred,
-                    &c->h_dist, &c->h_idx})
+                    &c->h_dist, &c->h_idx, &c->sw_dist, &c->sw_idx, &c->sw_pred, &c->sw_ql, &c->sw_correct})
         b->release();
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; i++) {
@@ -888,8 +893,10 @@ knn_status knn_merge_vote_append(knn_ctx* c, int32_t nsrc, int64_t nq, int32_t k
 namespace {
 
 // Validation shared by the device entry points.
+// need_pred = false: the k-sweep's internal top-k pass, which votes in k_vote_sweep instead
+// (the public predict entry points always pass true).
 knn_status validate_call(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t k, int32_t C,
-                         const QueryOut& out, bool shard) {
+                         const QueryOut& out, bool shard, bool need_pred = true) {
     knn_status s;
     if ((s = check_dataset(c, tr, "train", true)) != KNN_OK) return s;
     if ((s = check_dataset(c, te, "test", false)) != KNN_OK) return s;
@@ -905,7 +912,7 @@ knn_status validate_call(knn_ctx* c, const knn_dataset* tr, const knn_dataset* t
     if (((int64_t)tr->ld * es) % 16 || ((int64_t)te->ld * es) % 16 || (((uintptr_t)tr->feat) & 15) ||
         (((uintptr_t)te->feat) & 15))
         return fail(c, KNN_EINVAL, "device rows must be 16-byte aligned (ld * element size %% 16 == 0)");
-    if (te->n > 0 && !shard && !out.pred) return fail(c, KNN_EINVAL, "pred is NULL");
+    if (te->n > 0 && !shard && need_pred && !out.pred) return fail(c, KNN_EINVAL, "pred is NULL");
     // the exact scan (KNN_ALGO_DIRECT_SCAN, and every GEMM path's fallback) stages the query
     // row in LDS: bound d by it up front instead of failing at a launch
     if (knn_exact_scan_lds(tr->d, k, C) > 160 * 1024)
@@ -1101,6 +1108,198 @@ knn_status knn_merge_vote_append(knn_ctx* c, int32_t nsrc, int64_t nq, int32_t k
     stage_end(c, st);
     return finish_call(c, st);
 }
+
+namespace {
+
+// what the sweep entry points share: the outputs asked for and the list length
+knn_status sweep_check(knn_ctx* c, int32_t kmax, int64_t self_base, const void* qlabels, const void* pred_all,
+                       const void* correct) {
+    if (kmax < 1) return fail(c, KNN_EINVAL, "sweep: kmax=%d must be >= 1", kmax);
+    if (!qlabels && !pred_all && !correct)
+        return fail(c, KNN_EINVAL, "sweep: query labels, pred_all and correct are all NULL");
+    if (correct && !qlabels) return fail(c, KNN_EINVAL, "sweep: correct needs the query labels");
+    if (self_base >= 0 && kmax + 1 > 1024)
+        return fail(c, KNN_EINVAL, "sweep: kmax=%d + the self row exceeds the supported maximum 1024", kmax);
+    return KNN_OK;
+}
+
+// k_vote_sweep on lists in device memory, enqueued on st (no synchronisation)
+knn_status vote_sweep_enqueue(knn_ctx* c, int64_t nq, int kin, int C, const int32_t* idx, int64_t idx_stride,
+                              const int32_t* labels, int64_t self_base, const int32_t* qlabels, int32_t* pred_all,
+                              int64_t pred_stride, int64_t* correct, const float* dist_in, float* dist_out,
+                              int32_t* idx_out, hipStream_t st) {
+    VoteSweepArgs v{};
+    v.idx = idx; v.idx_stride = idx_stride; v.labels = labels;
+    v.nq = nq; v.kin = kin; v.kmax = self_base >= 0 ? kin - 1 : kin; v.C = C; v.self_base = self_base;
+    v.qlabels = qlabels; v.pred_all = pred_all; v.pred_stride = pred_stride;
+    v.correct = reinterpret_cast<unsigned long long*>(correct);
+    v.dist_in = dist_in; v.dist_out = dist_in ? dist_out : nullptr; v.idx_out = idx_out;
+    v.status = c->ctrl.as<int32_t>();
+    stage_begin(c, st, "vote_sweep");
+    HIP_OR_FAIL(c, knn_launch_vote_sweep(v, st));
+    stage_end(c, st);
+    return KNN_OK;
+}
+
+// The sweep over device datasets: one top-kin pass with no vote (QueryOut.pred == NULL) into the
+// context's list workspace, k_vote_sweep behind it on the same stream, one finish_call.  (The
+// GEMM path runs more than c->ws_queries queries in passes, like predict_core; each pass ends
+// in its own finish_call and adds into d_correct.)  d_pred_all rows are pred_stride apart.
+knn_status sweep_core(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
+                      int64_t self_base, const int32_t* d_qlabels, int32_t* d_pred_all, int64_t pred_stride,
+                      int64_t* d_correct, float* d_dist, int32_t* d_idx, hipStream_t st) {
+    knn_status s;
+    const int kin = kmax + (self_base >= 0 ? 1 : 0);
+    QueryOut out{nullptr, nullptr, nullptr, nullptr, kin, 0};
+    if ((s = validate_call(c, tr, te, kin, C, out, false, false)) != KNN_OK) return s;
+    if (self_base >= 0 && self_base + te->n > tr->n)
+        return fail(c, KNN_EINVAL, "sweep: self rows [%lld, %lld) outside the %lld train rows", (long long)self_base,
+                    (long long)(self_base + te->n), (long long)tr->n);
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    if (d_correct) HIP_OR_FAIL(c, hipMemsetAsync(d_correct, 0, sizeof(int64_t) * (size_t)kmax, st));
+    if (te->n == 0) {
+        HIP_OR_FAIL(c, hipStreamSynchronize(st));
+        return KNN_OK;
+    }
+    const int algo = choose_algo(c, tr->n, te->n, tr->d, kin, tr->dtype);
+    const bool gemm = is_gemm(algo);
+    const int64_t pass = gemm ? std::max<int64_t>(1, c->ws_queries) : te->n;
+    const int64_t rows = std::min(pass, te->n);
+    HIP_OR_FAIL(c, c->sw_idx.ensure(sizeof(int32_t) * (size_t)rows * kin));
+    if (d_dist) HIP_OR_FAIL(c, c->sw_dist.ensure(sizeof(float) * (size_t)rows * kin));
+    out.idx = c->sw_idx.as<int32_t>();
+    out.dist = d_dist ? c->sw_dist.as<float>() : nullptr;
+    for (int64_t q0 = 0; q0 < te->n; q0 += pass) {
+        const int64_t n = std::min(pass, te->n - q0);
+        const knn_dataset tq = offset_rows(*te, q0, n);
+        if ((s = predict_enqueue(c, tr, &tq, kin, C, out, st, algo, nullptr)) != KNN_OK ||
+            (s = vote_sweep_enqueue(c, n, kin, C, out.idx, kin, tr->labels, self_base >= 0 ? self_base + q0 : -1,
+                                    d_qlabels ? d_qlabels + q0 : nullptr, d_pred_all ? d_pred_all + q0 : nullptr,
+                                    pred_stride, d_correct, out.dist, d_dist ? d_dist + q0 * kmax : nullptr,
+                                    d_idx ? d_idx + q0 * kmax : nullptr, st)) != KNN_OK ||
+            (s = finish_call(c, st)) != KNN_OK) {
+            if (s != KNN_EINVAL && s != KNN_ERANGE) c->tprep.valid = c->tpad.valid = false;  // a HIP failure: the operands may be partial
+            return s;
+        }
+        pass_stats(c, c->ctrl_host, gemm);
+    }
+    return KNN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+knn_status knn_vote_sweep_device(knn_ctx* c, int64_t nq, int32_t kin, int32_t C, const int32_t* d_idx,
+                                 int64_t idx_stride, const int32_t* d_train_labels, int64_t self_base,
+                                 const int32_t* d_query_labels, int32_t* d_pred_all, int64_t* d_correct,
+                                 void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    c->stages.clear();
+    const int32_t kmax = self_base >= 0 ? kin - 1 : kin;
+    if (nq < 0 || kin < 1 || kin > 1024 || idx_stride < kin || C < 1 || C > 16384)
+        return fail(c, KNN_EINVAL, "vote sweep: bad nq=%lld kin=%d idx_stride=%lld C=%d", (long long)nq, kin,
+                    (long long)idx_stride, C);
+    knn_status s;
+    if ((s = sweep_check(c, kmax, self_base, d_query_labels, d_pred_all, d_correct)) != KNN_OK) return s;
+    if (nq > 0 && (!d_idx || !d_train_labels)) return fail(c, KNN_EINVAL, "vote sweep: d_idx / d_train_labels is NULL");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    if (d_correct) HIP_OR_FAIL(c, hipMemsetAsync(d_correct, 0, sizeof(int64_t) * (size_t)kmax, st));
+    if ((s = vote_sweep_enqueue(c, nq, kin, C, d_idx, idx_stride, d_train_labels, self_base, d_query_labels,
+                                d_pred_all, nq, d_correct, nullptr, nullptr, nullptr, st)) != KNN_OK)
+        return s;
+    return finish_call(c, st);
+}
+
+knn_status knn_sweep_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
+                            int64_t self_base, const int32_t* d_query_labels, int32_t* d_pred_all,
+                            int64_t* d_correct, float* d_topk_dist, int32_t* d_topk_idx, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    knn_status s;
+    if ((s = sweep_check(c, kmax, self_base, d_query_labels, d_pred_all, d_correct)) != KNN_OK) return s;
+    reset_stats(c);
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    return sweep_core(c, tr, te, kmax, C, self_base, d_query_labels, d_pred_all, te ? te->n : 0, d_correct,
+                      d_topk_dist, d_topk_idx, st);
+}
+
+knn_status knn_sweep(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
+                     int64_t self_base, const int32_t* query_labels, int32_t* out_pred_all, int64_t* out_correct) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    knn_status s;
+    if ((s = check_dataset(c, tr, "train", true)) != KNN_OK) return s;
+    if ((s = check_dataset(c, te, "test", false)) != KNN_OK) return s;
+    if ((s = sweep_check(c, kmax, self_base, query_labels, out_pred_all, out_correct)) != KNN_OK) return s;
+    if (tr->d != te->d) return fail(c, KNN_EINVAL, "feature count mismatch: train d=%d test d=%d", tr->d, te->d);
+    if (tr->dtype != te->dtype) return fail(c, KNN_EINVAL, "train and test dtypes differ");
+    const int64_t nq = te->n;
+    const int kin = kmax + (self_base >= 0 ? 1 : 0);
+    if (kin > tr->n) return fail(c, KNN_EINVAL, "k=%d outside [1, n_train=%lld]", kin, (long long)tr->n);
+    if (self_base >= 0 && self_base + nq > tr->n)
+        return fail(c, KNN_EINVAL, "sweep: self rows [%lld, %lld) outside the %lld train rows", (long long)self_base,
+                    (long long)(self_base + nq), (long long)tr->n);
+    reset_stats(c);
+    if (out_correct) std::memset(out_correct, 0, sizeof(int64_t) * (size_t)kmax);
+    if (nq == 0) return KNN_OK;
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int d = tr->d;
+    const size_t es = (size_t)elem_size(tr->dtype);
+    const int ldd = (int)((d + (int)(16 / es) - 1) / (int)(16 / es) * (int)(16 / es));  // device rows padded to 16 B
+    const int64_t B = std::min<int64_t>(nq, c->batch_rows);
+    {
+        // the device call's checks on the shapes it will see, before anything is enqueued
+        const knn_dataset vtr{(const void*)(uintptr_t)256, tr->labels, tr->n, d, ldd, tr->dtype};
+        const knn_dataset vq{(const void*)(uintptr_t)256, nullptr, B, d, ldd, te->dtype};
+        const QueryOut vo{nullptr, nullptr, nullptr, nullptr, kin, 0};
+        if ((s = validate_call(c, &vtr, &vq, kin, C, vo, false, false)) != KNN_OK) return s;
+    }
+    // every error from here on drains the stream (no copy from or to the caller's buffers
+    // outlives the call) and drops the train cache entry (its upload may not have run)
+    auto abort_call = [&](knn_status e) {
+        (void)hipStreamSynchronize(st);
+        c->tcache.valid = false;
+        c->tprep.valid = c->tpad.valid = false;
+        return e;
+    };
+    knn_dataset dtr;
+    if ((s = train_device(c, tr, st, &dtr)) != KNN_OK) return abort_call(s);
+    HIP_OR_ABORT(c->q_slot[0].ensure(es * (size_t)ldd * B));
+    if (out_pred_all) HIP_OR_ABORT(c->sw_pred.ensure(sizeof(int32_t) * (size_t)kmax * B));
+    if (query_labels) HIP_OR_ABORT(c->sw_ql.ensure(sizeof(int32_t) * (size_t)B));
+    if (out_correct) HIP_OR_ABORT(c->sw_correct.ensure(sizeof(int64_t) * (size_t)kmax));
+    std::vector<int64_t> part(out_correct ? kmax : 0);
+    // one batch after another, each uploaded, swept and downloaded before the next starts
+    for (int64_t q0 = 0; q0 < nq; q0 += B) {
+        const int64_t n = std::min(B, nq - q0);
+        const unsigned char* src = (const unsigned char*)te->feat + es * (size_t)q0 * (size_t)te->ld;
+        HIP_OR_ABORT(hipMemcpy2DAsync(c->q_slot[0].p, es * ldd, src, es * te->ld, es * d, n, hipMemcpyHostToDevice, st));
+        if (query_labels)
+            HIP_OR_ABORT(hipMemcpyAsync(c->sw_ql.p, query_labels + q0, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+        c->stats[7] += (int64_t)(es * d * n);
+        const knn_dataset dq{c->q_slot[0].p, nullptr, n, d, ldd, te->dtype};
+        s = sweep_core(c, &dtr, &dq, kmax, C, self_base >= 0 ? self_base + q0 : -1,
+                       query_labels ? c->sw_ql.as<int32_t>() : nullptr, out_pred_all ? c->sw_pred.as<int32_t>() : nullptr,
+                       n, out_correct ? c->sw_correct.as<int64_t>() : nullptr, nullptr, nullptr, st);
+        if (s != KNN_OK) return abort_call(s);
+        // (synchronous copies on the null stream: ordered after the context's blocking stream)
+        if (out_pred_all)
+            HIP_OR_ABORT(hipMemcpy2D(out_pred_all + q0, sizeof(int32_t) * (size_t)nq, c->sw_pred.p, sizeof(int32_t) * (size_t)n,
+                                     sizeof(int32_t) * (size_t)n, kmax, hipMemcpyDeviceToHost));
+        if (out_correct) {
+            HIP_OR_ABORT(hipMemcpy(part.data(), c->sw_correct.p, sizeof(int64_t) * (size_t)kmax, hipMemcpyDeviceToHost));
+            for (int i = 0; i < kmax; i++) out_correct[i] += part[i];
+        }
+    }
+    return KNN_OK;
+}
+
+}  // extern "C"
 
 extern "C" {
 

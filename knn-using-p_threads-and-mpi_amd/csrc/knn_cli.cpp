@@ -1,6 +1,6 @@
 // knn_cli.cpp -- command-line driver with the reference's contract.
 //
-//   knn_cli train.arff test.arff k [numDevices] [--shard=test|train|auto]
+//   knn_cli train.arff test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]]
 //
 // Same positional arguments as ./main (main.cpp:114-122; k parsed with strtol) plus the
 // optional worker count of ./multi-thread (multi-thread.cpp:135-143), here the number of
@@ -8,6 +8,10 @@
 // --shard=train the train set (per-shard top-k merged), --shard=auto knn_shard_policy.  The timed region is the reference's: the KNN()
 // call only (main.cpp:133-137), after parsing and device initialisation.  The report
 // line is printed verbatim (main.cpp:146), "CPU time" wording included.
+// --sweep: one KNN_sweep call for every k in 1..K, then the report line once per k with that
+// k's accuracy (computeConfusionMatrix / computeAccuracy on row k - 1, so the float is the
+// reference's) and the one call's time on every line.  --sweep=loo: leave-one-out on the
+// train file (KNN_sweep_loo); the test path keeps its position and is not read.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -21,13 +25,16 @@
 int main(int argc, char* argv[]) {
     // --shard=... may sit anywhere; the rest are the reference's positional arguments
     int n = 0;
+    bool sweep = false, loo = false;
     for (int i = 0; i < argc; i++) {
         if (!std::strncmp(argv[i], "--shard=", 8)) setenv("KNN_AMD_SHARD", argv[i] + 8, 1);
+        else if (!std::strcmp(argv[i], "--sweep")) sweep = true;
+        else if (!std::strcmp(argv[i], "--sweep=loo")) sweep = loo = true;
         else argv[n++] = argv[i];
     }
     argc = n;
     if (argc != 4 && argc != 5) {
-        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto]"
+        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]]"
                   << std::endl;
         std::exit(0);
     }
@@ -37,10 +44,34 @@ int main(int argc, char* argv[]) {
     ArffParser parserTrain(argv[1]);
     ArffParser parserTest(argv[2]);
     ArffData* train = parserTrain.parse();
-    ArffData* test = parserTest.parse();
+    ArffData* test = loo ? train : parserTest.parse();
     knn_amd_init();
 
     struct timespec start, end;
+    if (sweep) {
+        clock_gettime(CLOCK_MONOTONIC_RAW, &start);
+        int* all = loo ? KNN_sweep_loo(train, k) : KNN_sweep(train, test, k);
+        clock_gettime(CLOCK_MONOTONIC_RAW, &end);
+        uint64_t diff = (1000000000L * (end.tv_sec - start.tv_sec) + end.tv_nsec - start.tv_nsec) / 1e6;
+        const long nq = test->num_instances();
+        for (int kk = 1; kk <= k; kk++) {
+            int* confusionMatrix = computeConfusionMatrix(all + (size_t)(kk - 1) * nq, test);
+            float accuracy = computeAccuracy(confusionMatrix, test);
+            printf("The %i-NN classifier for %lu test instances on %lu train instances required %llu ms CPU time. Accuracy was %.4f\n",
+                   kk, (unsigned long)nq, (unsigned long)train->num_instances(), (long long unsigned int)diff, accuracy);
+            std::free(confusionMatrix);
+        }
+        if (const char* p = std::getenv("KNN_CLI_PRED_OUT")) {  // test hook: K lines of n predictions
+            FILE* f = std::fopen(p, "w");
+            for (int kk = 0; kk < k; kk++) {
+                for (long q = 0; q < nq; q++) std::fprintf(f, q ? " %d" : "%d", all[(size_t)kk * nq + q]);
+                std::fprintf(f, "\n");
+            }
+            std::fclose(f);
+        }
+        std::free(all);
+        return 0;
+    }
     clock_gettime(CLOCK_MONOTONIC_RAW, &start);
     int* predictions = KNN(train, test, k);
     clock_gettime(CLOCK_MONOTONIC_RAW, &end);

@@ -94,6 +94,23 @@ struct MergeArgs {
     const int32_t* labels;
 };
 
+// k_vote_sweep: the vote over every prefix of a query's ascending neighbour list.
+// idx: [nq][idx_stride] train rows (-1 = none), the first kin entries of a row are read;
+// labels[idx] gives an entry's label.  self_base >= 0: the entry equal to self_base + q is
+// skipped (none equal: the last is dropped), the effective list has kmax = kin - 1 entries;
+// self_base < 0: kmax = kin.  pred_all (optional) [kmax][pred_stride >= nq]; correct (optional, needs
+// qlabels) [kmax], zeroed by the caller; dist_in / dist_out / idx_out (optional): the lists
+// after self-removal, [nq][kmax] (dist_in has idx's stride).
+struct VoteSweepArgs {
+    const int32_t* idx; int64_t idx_stride; const int32_t* labels;
+    int64_t nq; int kin; int kmax; int C; int64_t self_base;
+    const int32_t* qlabels; int32_t* pred_all; int64_t pred_stride; unsigned long long* correct;
+    const float* dist_in; float* dist_out; int32_t* idx_out;
+    int32_t* status;
+    int qb;  // queries per LDS tile (set by the launcher)
+};
+hipError_t knn_launch_vote_sweep(const VoteSweepArgs& a, hipStream_t st);
+
 // class counts up to this many live in a per-wave LDS table; above it the vote runs
 // table-free (vote_ballot), so every path accepts any num_classes
 #define KNN_VOTE_LDS_MAX_C 1024

@@ -23,6 +23,7 @@
 //                  running per-query threshold
 //   k_rescore      exact direct-form rescore of the surviving candidates + top-k + vote
 //   k_merge_vote   merge of per-train-shard neighbour lists (train-sharded runs) + vote
+//   k_vote_sweep   the vote for every prefix k <= K of a neighbour list (k-sweep, leave-one-out)
 //   k_generate     counter-based synthetic rows (same formula as oracle/knn_oracle.c)
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -2068,6 +2069,168 @@ __global__ __launch_bounds__(256) void k_confusion(const int32_t* __restrict__ p
 }
 
 // ---------------------------------------------------------------------------------
+// k_vote_sweep<R>: the vote of main.cpp:64-78 for EVERY prefix of a neighbour list.  The
+// lists ascend by (distance, train index), so the k nearest of a query are the first k
+// entries of its K nearest: one top-K pass holds the answer for every k <= K and only the
+// vote is redone per prefix.  One wave per query, element e = 64 r + lane in register r;
+// a block works through tiles of a.qb queries.
+//  * Labels are read as labels[idx] (the list's train rows index the label array; no
+//    label list is needed, so lists from any entry point serve).
+//  * Self-removal (leave-one-out, a.self_base >= 0): the entry equal to self_base + q is
+//    skipped -- the elements behind it move up one place -- and when no entry equals it the
+//    last one is dropped.  The self row (distance 0) is absent only when at least kin rows
+//    with a lower index tie it, and then the first kin - 1 entries are the answer already.
+//  * cnt_j = the number of i <= j with label_i == label_j, one round per DISTINCT label:
+//    a ballot per register gives the label's occurrence masks, a lane's count is the
+//    popcount of the bits at or below its own element.  No C-sized table, any class count.
+//  * The prediction for k is the label in the maximum over j < k of the key
+//    (cnt_j << 32) | (0xffffffff - label_j) -- an inclusive prefix-max scan over the list.
+//    This is the reference's argmax: within a prefix a label's largest cnt sits at its last
+//    occurrence there and equals its bincount, its earlier occurrences carry smaller counts,
+//    so the maximum over elements is the maximum over labels of (count, -label): the largest
+//    count, ties to the smallest label.
+//  * A prefix that reaches a missing entry (-1) predicts 0 and sets KNN_STATUS_TOO_FEW; a
+//    label outside [0, C) sets KNN_STATUS_BAD_LABEL (both as finish_query).
+//  * pred_all is [kmax][nq]: a wave alone would scatter one word into each of kmax rows, so
+//    the block stages its [k][query] tile in LDS (row stride qb + 1, odd: the waves' column
+//    writes and the per-k reads below fall on distinct banks) and stores it with consecutive
+//    lanes on consecutive queries of a row.  correct[k - 1] is counted per thread over the
+//    block's tiles and added once per k per block.
+// LDS: tile [kmax][qb + 1] i32 | query labels [qb] i32
+// ---------------------------------------------------------------------------------
+template <int R>
+__global__ __launch_bounds__(256) void k_vote_sweep(VoteSweepArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int S = a.qb + 1;
+    int32_t* tile = reinterpret_cast<int32_t*>(smem);
+    int32_t* ql = tile + (size_t)a.kmax * S;
+    const int lane = lane_id();
+    const int wave = threadIdx.x >> 6;
+    const u64 at_or_below = (2ull << lane) - 1ull;  // lanes <= this one
+    const int64_t ntiles = (a.nq + a.qb - 1) / a.qb;
+    unsigned long long ok[4] = {0, 0, 0, 0};  // prefix k - 1 = threadIdx.x + 256 i
+
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int64_t q0 = t * a.qb;
+        const int nqv = (int)std::min<int64_t>(a.qb, a.nq - q0);
+        if (a.qlabels)
+            for (int j = threadIdx.x; j < nqv; j += 256) ql[j] = a.qlabels[q0 + j];
+        for (int j = wave; j < nqv; j += 4) {
+            const int64_t q = q0 + j;
+            const int32_t* __restrict__ row = a.idx + q * a.idx_stride;
+            // the place of the skipped entry (kin: none)
+            int skip = a.kin;
+            if (a.self_base >= 0) {
+                const int64_t self = a.self_base + q;
+                skip = a.kin - 1;
+#pragma unroll
+                for (int r = R - 1; r >= 0; r--) {
+                    const int e = 64 * r + lane;
+                    const u64 m = __ballot(e < a.kin && (int64_t)row[e] == self);
+                    if (m) skip = 64 * r + __ffsll(m) - 1;
+                }
+            }
+            int lab[R];
+            int first_missing = a.kmax;
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                const int e = 64 * r + lane;
+                lab[r] = -1;
+                bool miss = false;
+                if (e < a.kmax) {
+                    const int src = e + (e >= skip ? 1 : 0);
+                    const int32_t idx = row[src];
+                    if (idx >= 0) {
+                        const int l = a.labels[idx];
+                        if (l >= 0 && l < a.C) lab[r] = l;
+                        else atomicOr(a.status, KNN_STATUS_BAD_LABEL);
+                    } else {
+                        miss = true;
+                    }
+                    if (a.idx_out) a.idx_out[q * a.kmax + e] = idx;
+                    if (a.dist_out) a.dist_out[q * a.kmax + e] = a.dist_in[q * a.idx_stride + src];
+                }
+                const u64 mm = __ballot(miss);
+                if (mm && first_missing == a.kmax) first_missing = 64 * r + __ffsll(mm) - 1;
+            }
+            // occurrence counts, one round per distinct label
+            uint32_t cnt[R];
+            u64 pend[R];
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                cnt[r] = 0;
+                pend[r] = __ballot(lab[r] >= 0);
+            }
+            for (;;) {
+                int re = -1;
+                u64 pm = 0;
+#pragma unroll
+                for (int r = R - 1; r >= 0; r--)
+                    if (pend[r]) { re = r; pm = pend[r]; }
+                if (re < 0) break;
+                int le = lab[0];
+#pragma unroll
+                for (int r = 1; r < R; r++)
+                    if (r == re) le = lab[r];
+                le = __shfl(le, __ffsll(pm) - 1);
+                uint32_t before = 0;
+#pragma unroll
+                for (int r = 0; r < R; r++) {
+                    const bool eq = lab[r] == le;
+                    const u64 m = __ballot(eq);
+                    if (eq) cnt[r] = before + (uint32_t)__popcll(m & at_or_below);
+                    before += (uint32_t)__popcll(m);
+                    pend[r] &= ~m;
+                }
+            }
+            // prefix max of the keys, carried from register to register
+            u64 carry = 0;
+#pragma unroll
+            for (int r = 0; r < R; r++) {
+                u64 key = lab[r] >= 0 ? ((u64)cnt[r] << 32) | (u64)(0xffffffffu - (uint32_t)lab[r]) : 0;
+#pragma unroll
+                for (int s = 1; s < 64; s <<= 1) {
+                    const u64 o = __shfl_up(key, s);
+                    if (lane >= s) key = umax64(key, o);
+                }
+                key = umax64(key, carry);
+                carry = __shfl(key, 63);
+                const int e = 64 * r + lane;
+                if (e < a.kmax)
+                    tile[e * S + j] = (e < first_missing && key) ? (int32_t)(0xffffffffu - (uint32_t)(key & 0xffffffffull)) : 0;
+            }
+            if (lane == 0 && first_missing < a.kmax) atomicOr(a.status, KNN_STATUS_TOO_FEW);
+        }
+        __syncthreads();
+        if (a.pred_all) {
+            for (int i = threadIdx.x; i < a.kmax * nqv; i += 256) {
+                const int k = i / nqv, jj = i - k * nqv;
+                a.pred_all[(int64_t)k * a.pred_stride + q0 + jj] = tile[k * S + jj];
+            }
+        }
+        if (a.correct) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int k = threadIdx.x + 256 * i;
+                if (k < a.kmax) {
+                    int c = 0;
+                    for (int jj = 0; jj < nqv; jj++) c += tile[k * S + jj] == ql[jj];
+                    ok[i] += (unsigned long long)c;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (a.correct) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int k = threadIdx.x + 256 * i;
+            if (k < a.kmax && ok[i]) atomicAdd(&a.correct[k], ok[i]);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------
 // Device-side control of a predict call (no host round trip inside a call):
 //   k_fill_u32     p[0..n) = v when the gate is open (a gated stage's threshold reset)
 //   k_rerun_decide AUTO's re-run of the rounded filter as split: open the gate when the
@@ -2443,6 +2606,33 @@ hipError_t knn_launch_confusion(const int32_t* pred, const int32_t* labels, int6
     hipLaunchKernelGGL(k_confusion, dim3(grid), dim3(256), 0, st, pred, labels, n, C, cm, correct, status);
     KNN_LAUNCH_CHECK();
     return hipSuccess;
+}
+
+// queries per tile: about 4096 tile words (64 queries for lists of one register), halved
+// while the tiles would not give every CU a block or two -- a short query set spreads over
+// the device at the price of shorter store runs
+template <int R>
+static hipError_t launch_vote_sweep_r(const VoteSweepArgs& a0, hipStream_t st) {
+    VoteSweepArgs a = a0;
+    a.qb = std::max(4, 64 / R);
+    while (a.qb > 4 && (a.nq + a.qb - 1) / a.qb < 512) a.qb >>= 1;
+    const int64_t ntiles = (a.nq + a.qb - 1) / a.qb;
+    const size_t lds = sizeof(int32_t) * ((size_t)a.kmax * (a.qb + 1) + a.qb);
+    hipLaunchKernelGGL(k_vote_sweep<R>, dim3((unsigned)std::min<int64_t>(ntiles, 4096)), dim3(256), lds, st, a);
+    KNN_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+hipError_t knn_launch_vote_sweep(const VoteSweepArgs& a, hipStream_t st) {
+    if (a.nq <= 0) return hipSuccess;
+    if (a.kin < 1 || a.kin > 1024 || a.kmax < 1 || a.kmax > a.kin || a.idx_stride < a.kin) return hipErrorInvalidValue;
+    switch (list_regs(a.kin)) {
+        case 1: return launch_vote_sweep_r<1>(a, st);
+        case 2: return launch_vote_sweep_r<2>(a, st);
+        case 4: return launch_vote_sweep_r<4>(a, st);
+        case 8: return launch_vote_sweep_r<8>(a, st);
+        default: return launch_vote_sweep_r<16>(a, st);
+    }
 }
 
 hipError_t knn_launch_split_rows(const float* x, int64_t n, int ld, int d, uint16_t* out, hipStream_t st,
