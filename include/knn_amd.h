@@ -307,6 +307,65 @@ knn_status knn_sweep(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* 
                      int32_t num_classes, int64_t self_base, const int32_t* query_labels,
                      int32_t* out_pred_all, int64_t* out_correct);
 
+/*
+ * Weighted vote: "should nearer neighbours count more?" and "how sure is the prediction?",
+ * answered from the same ordered neighbour lists as the k-sweep (no reference counterpart; the
+ * uniform kind is the reference's vote, main.cpp:64-78).  The neighbour list is unchanged: the k
+ * smallest (distance, train index) pairs, distances the fp32 squared Euclidean values reported
+ * everywhere else.
+ *   weight    w_j = 1 (KNN_W_UNIFORM), 1.0f / sqrtf(d_j) (KNN_W_INV_DIST: sklearn's
+ *             weights="distance" on the Euclidean distance) or 1.0f / d_j (KNN_W_INV_SQDIST), in
+ *             IEEE binary32: round to nearest, subnormals kept, inf an ordinary value.
+ *   zero rule (sklearn's; the two weighted kinds, after self-removal): when the list's first
+ *             entry has d == 0, every entry with d == 0 gets weight 1 and every other entry 0.
+ *   score     S_c(k) = the sum of w_j over j < k with label_j == c, accumulated in fp32 in
+ *             ascending list position, S = fl(S + w_j): no FMA, no tree, no reordering.
+ *   vote      the prediction for k is the argmax over c of S_c(k), ties (equal inf included) to
+ *             the smallest label.  With KNN_W_UNIFORM this is exactly the k-sweep's vote.
+ *   scores    d_scores (optional) fp32 [nq][num_classes] receives S_c(kmax), +0.0 for absent
+ *             classes; with KNN_W_UNIFORM the bincount as floats.  Probabilities are
+ *             scores / scores.sum(1), left to the caller.
+ * Leave-one-out (self_base >= 0) removes the self row by the k-sweep's rule first; the zero rule
+ * and the sums run on what is left.  A prefix that reaches a missing entry (-1) predicts 0 and
+ * gives KNN_ERANGE, and that query's score row is all zero; a train label outside
+ * [0, num_classes) gives KNN_EINVAL; an unknown `weights` gives KNN_EINVAL.  Limits as the
+ * k-sweep: kin <= 1024, num_classes <= 16384; d_query_labels, d_pred_all, d_correct and d_scores
+ * are each optional (d_correct needs the query labels), but not all may be NULL.
+ *
+ * knn_vote_weighted_device: the vote alone on lists the caller holds, d_idx / d_dist
+ *   [nq][stride] of which the first kin entries of a row are read (as knn_vote_sweep_device's
+ *   d_idx; d_dist may be NULL with KNN_W_UNIFORM) -- from knn_predict_device,
+ *   knn_merge_vote_device or knn_predict_train_sharded, so a train-sharded run gets weighted
+ *   votes with no new collective.  A non-missing entry whose distance is NaN or negative gives
+ *   KNN_EINVAL.  kmax = kin, or kin - 1 with self_base; d_pred_all is [kmax][nq].
+ * knn_sweep_weighted_device: knn_sweep_device's top-kin pass (its distances always kept, in
+ *   context workspace), then k_vote_weighted on the same stream; one synchronisation per pass.
+ *   With profile = 1 the vote's stage is named "vote_weighted".
+ * knn_predict_weighted_device: the single-k form.  Only row k - 1 of the prefix votes is
+ *   staged and stored: d_pred is int32[nq], no [k][nq] buffer exists.  d_pred and d_scores are
+ *   each optional, not both NULL.
+ * knn_sweep_weighted: host buffers, batched like knn_sweep and NOT pipelined; out_scores
+ *   (optional) [nq][num_classes].
+ */
+typedef enum { KNN_W_UNIFORM = 0, KNN_W_INV_DIST = 1, KNN_W_INV_SQDIST = 2 } knn_weight;
+knn_status knn_vote_weighted_device(knn_ctx* ctx, int64_t nq, int32_t kin, int32_t num_classes,
+                                    const int32_t* d_idx, const float* d_dist, int64_t stride,
+                                    const int32_t* d_train_labels, int32_t weights, int64_t self_base,
+                                    const int32_t* d_query_labels, int32_t* d_pred_all, int64_t* d_correct,
+                                    float* d_scores, void* hip_stream);
+knn_status knn_sweep_weighted_device(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test,
+                                     int32_t kmax, int32_t num_classes, int32_t weights, int64_t self_base,
+                                     const int32_t* d_query_labels, int32_t* d_pred_all, int64_t* d_correct,
+                                     float* d_scores, float* d_topk_dist, int32_t* d_topk_idx, void* hip_stream);
+knn_status knn_predict_weighted_device(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test,
+                                       int32_t k, int32_t num_classes, int32_t weights, int32_t* d_pred,
+                                       float* d_scores, float* d_topk_dist, int32_t* d_topk_idx,
+                                       void* hip_stream);
+knn_status knn_sweep_weighted(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test, int32_t kmax,
+                              int32_t num_classes, int32_t weights, int64_t self_base,
+                              const int32_t* query_labels, int32_t* out_pred_all, int64_t* out_correct,
+                              float* out_scores);
+
 /* Per-stage device times (ms) of the last predict call when opts.profile >= 1.
  * names: optional array of n const char* to receive stage names. Returns the
  * number of stages recorded (<= n). */

@@ -176,6 +176,11 @@ int* KNN_sweep(ArffData* train, ArffData* test, int kmax);
 // Leave-one-out on the train set: row i's predictions for every k in 1..kmax with row i taken
 // out of the train set, malloc'd int[kmax * n_train] laid out [kmax][n_train].
 int* KNN_sweep_loo(ArffData* train, int kmax);
+// The same two with the weighted vote (knn_sweep_weighted; weights: knn_weight -- KNN_W_UNIFORM
+// reproduces KNN_sweep / KNN_sweep_loo, KNN_W_INV_DIST is sklearn's weights="distance",
+// KNN_W_INV_SQDIST weighs by 1 / squared distance).
+int* KNN_sweep_weighted(ArffData* train, ArffData* test, int kmax, int weights);
+int* KNN_sweep_loo_weighted(ArffData* train, int kmax, int weights);
 // main.cpp:87 -- calloc'd int[C*C], C = dataset->num_classes(), row = true class.
 int* computeConfusionMatrix(int* predictions, ArffData* dataset);
 // main.cpp:102

@@ -14,6 +14,9 @@ Names follow the reference (srna99/KNN-using-p_threads-and-MPI):
   per-shard exact top-k -> all-to-all of neighbour lists -> merge + vote
 * ``Context.sweep_device / loo_device / vote_sweep_device / sweep`` and ``best_k``: the
   predictions and correct counts for every k <= K from one top-K pass (no reference counterpart)
+* ``Context.sweep_weighted_device / loo_weighted_device / vote_weighted_device /
+  predict_weighted_device / sweep_weighted``, ``WEIGHTS`` and ``proba``: the same with the
+  distance-weighted vote and per-class scores (no reference counterpart)
 
 Features are fp32 or bf16.  Host bf16 arrays are numpy ``uint16`` holding bf16 bits
 (``to_bf16_bits`` / ``bf16_bits_to_f32``); device tensors are ``torch.bfloat16``.
@@ -37,6 +40,8 @@ STATUS_NAMES = {0: "KNN_OK", 1: "KNN_EINVAL", 2: "KNN_ENOMEM", 3: "KNN_EHIP", 4:
 KNN_COMM_ID_BYTES = 128
 KNN_F32, KNN_BF16 = 0, 1
 ALGOS = {"auto": 0, "direct": 1, "gemm": 2, "gemm_split": 3, "gemm_bf16": 4, "direct_scan": 5}
+# knn_weight: the vote's weight kinds ("distance" is sklearn's weights="distance")
+WEIGHTS = {"uniform": 0, "distance": 1, "sqdist": 2}
 FILTER_OPERANDS = {-1: None, 0: "f32", 1: "bf16", 2: "bf16x3 split", 3: "bf16 rounded"}
 
 
@@ -107,6 +112,10 @@ def load_library(path=LIB_PATH):
         "knn_vote_sweep_device": (I32, [P, I64, I32, I32, P, I64, P, I64, P, P, P, P]),
         "knn_sweep_device": (I32, [P, DS, DS, I32, I32, I64, P, P, P, P, P, P]),
         "knn_sweep": (I32, [P, DS, DS, I32, I32, I64, P, P, P]),
+        "knn_vote_weighted_device": (I32, [P, I64, I32, I32, P, P, I64, P, I32, I64, P, P, P, P, P]),
+        "knn_sweep_weighted_device": (I32, [P, DS, DS, I32, I32, I32, I64, P, P, P, P, P, P, P]),
+        "knn_predict_weighted_device": (I32, [P, DS, DS, I32, I32, I32, P, P, P, P, P]),
+        "knn_sweep_weighted": (I32, [P, DS, DS, I32, I32, I32, I64, P, P, P, P]),
         "knn_stage_times": (I32, [P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(F), I32]),
         "knn_last_stats": (I32, [P, ctypes.POINTER(I64), I32]),
         "knn_generate": (I32, [P, P, P, I64, I64, I32, I32, I32, I32, ctypes.c_uint64,
@@ -534,6 +543,131 @@ class Context:
                                        _ptr(correct)))
         return pred_all, correct
 
+    @staticmethod
+    def _scores_arg(scores, nq, num_classes, device):
+        """scores: True = allocate float32 [nq][C], a tensor = use it, False / None = none."""
+        import torch
+        if scores is None or scores is False:
+            return None
+        if scores is True:
+            return torch.empty((nq, num_classes), dtype=torch.float32, device=device)
+        return _check_tensor(scores, "scores", torch.float32, nq * num_classes)
+
+    def sweep_weighted_device(self, train, labels, test, kmax, num_classes, weights="distance", query_labels=None,
+                              pred_all=None, self_base=None, scores=True, dist=None, idx=None, stream=None,
+                              d=None):
+        """sweep_device with the weighted vote (knn_sweep_weighted_device).  weights: a key of
+        WEIGHTS (or its number).  Returns (pred_all int32 [kmax][nq], correct int64 [kmax] or None
+        without query_labels, scores float32 [nq][C] = each class's summed weight over the kmax
+        neighbours, or None with scores=False); ``proba(scores)`` normalises them."""
+        import torch
+        self._on_device(train)
+        self._note_train(train)
+        tr = _device_dataset(train, labels, d)
+        te = _device_dataset(test, None, d)
+        if pred_all is None:
+            pred_all = torch.empty((max(kmax, 0), te.n), dtype=torch.int32, device=test.device)
+        _check_tensor(pred_all, "pred_all", torch.int32, max(kmax, 0) * te.n)
+        _outputs(te.n, kmax, None, dist, idx)
+        scores = self._scores_arg(scores, te.n, num_classes, test.device)
+        correct = None
+        if query_labels is not None:
+            _check_tensor(query_labels, "query_labels", torch.int32, te.n)
+            correct = torch.empty(max(kmax, 0), dtype=torch.int64, device=test.device)
+        self._check(self.lib.knn_sweep_weighted_device(
+            self.h, ctypes.byref(tr), ctypes.byref(te), kmax, num_classes, _weight_kind(weights),
+            -1 if self_base is None else self_base,
+            None if query_labels is None else query_labels.data_ptr(), pred_all.data_ptr(),
+            None if correct is None else correct.data_ptr(), None if scores is None else scores.data_ptr(),
+            None if dist is None else dist.data_ptr(), None if idx is None else idx.data_ptr(),
+            self._stream(stream, test)))
+        return pred_all, correct, scores
+
+    def loo_weighted_device(self, train, labels, kmax, num_classes, weights="distance", pred_all=None, scores=True,
+                            dist=None, idx=None, stream=None, d=None):
+        """Leave-one-out on the train set with the weighted vote (loo_device's sibling)."""
+        return self.sweep_weighted_device(train, labels, train, kmax, num_classes, weights, query_labels=labels,
+                                          pred_all=pred_all, self_base=0, scores=scores, dist=dist, idx=idx,
+                                          stream=stream, d=d)
+
+    def predict_weighted_device(self, train, labels, test, k, num_classes, weights="distance", pred=None,
+                                scores=True, dist=None, idx=None, stream=None, d=None):
+        """The weighted vote for one k (knn_predict_weighted_device): returns (pred int32 [nq],
+        scores float32 [nq][C] or None).  dist / idx (optional) receive the [nq][k] lists."""
+        import torch
+        self._on_device(train)
+        self._note_train(train)
+        tr = _device_dataset(train, labels, d)
+        te = _device_dataset(test, None, d)
+        if pred is None:
+            pred = torch.empty(te.n, dtype=torch.int32, device=test.device)
+        _outputs(te.n, k, pred, dist, idx)
+        scores = self._scores_arg(scores, te.n, num_classes, test.device)
+        self._check(self.lib.knn_predict_weighted_device(
+            self.h, ctypes.byref(tr), ctypes.byref(te), k, num_classes, _weight_kind(weights), pred.data_ptr(),
+            None if scores is None else scores.data_ptr(), None if dist is None else dist.data_ptr(),
+            None if idx is None else idx.data_ptr(), self._stream(stream, test)))
+        return pred, scores
+
+    def vote_weighted_device(self, idx, dist, train_labels, num_classes, weights="distance", query_labels=None,
+                             pred_all=None, self_base=None, kin=None, scores=True, stream=None):
+        """The weighted prefix votes alone (knn_vote_weighted_device) on neighbour lists idx int32
+        / dist float32 [nq][stride] (same shape and strides) of which the first kin entries per
+        row are read (default: all).  Returns (pred_all [kmax][nq], correct or None, scores or
+        None); kmax = kin, or kin - 1 with self_base."""
+        import torch
+        self._on_device(idx)
+        if idx.dim() != 2:
+            raise KnnError(KNN_EINVAL, "idx must be a 2-D [nq][stride] tensor")
+        _check_tensor(idx, "idx", torch.int32)
+        if dist is not None:  # (the uniform kind reads no distances)
+            _check_tensor(dist, "dist", torch.float32)
+            if tuple(dist.shape) != tuple(idx.shape) or dist.stride() != idx.stride():
+                raise KnnError(KNN_EINVAL, "dist must have idx's shape and strides")
+            self._on_device(dist)
+        _check_tensor(train_labels, "train_labels", torch.int32)
+        nq, stride = idx.shape
+        kin = stride if kin is None else kin
+        kmax = kin - (0 if self_base is None else 1)
+        if pred_all is None:
+            pred_all = torch.empty((max(kmax, 0), nq), dtype=torch.int32, device=idx.device)
+        _check_tensor(pred_all, "pred_all", torch.int32, max(kmax, 0) * nq)
+        scores = self._scores_arg(scores, nq, num_classes, idx.device)
+        correct = None
+        if query_labels is not None:
+            _check_tensor(query_labels, "query_labels", torch.int32, nq)
+            correct = torch.empty(max(kmax, 0), dtype=torch.int64, device=idx.device)
+        self._check(self.lib.knn_vote_weighted_device(
+            self.h, nq, kin, num_classes, idx.data_ptr(), None if dist is None else dist.data_ptr(), stride,
+            train_labels.data_ptr(),
+            _weight_kind(weights), -1 if self_base is None else self_base,
+            None if query_labels is None else query_labels.data_ptr(), pred_all.data_ptr(),
+            None if correct is None else correct.data_ptr(), None if scores is None else scores.data_ptr(),
+            self._stream(stream, idx)))
+        return pred_all, correct, scores
+
+    def sweep_weighted(self, train_feat, train_labels, test_feat, kmax, num_classes=None, weights="distance",
+                       query_labels=None, self_base=None, scores=True):
+        """Host arrays in, host arrays out (knn_sweep_weighted; not pipelined): (pred_all int32
+        [kmax][nq], correct int64 [kmax] or None without query_labels, scores float32 [nq][C] or
+        None with scores=False)."""
+        tr, keep1 = _dataset(train_feat, train_labels)
+        te, keep2 = _dataset(test_feat)
+        if num_classes is None:
+            num_classes = int(keep1[1].max()) + 1 if keep1[1].size else 1
+        pred_all = np.zeros((max(kmax, 0), te.n), np.int32)
+        ql = None if query_labels is None else np.ascontiguousarray(query_labels, dtype=np.int32)
+        if ql is not None and ql.size < te.n:
+            raise KnnError(KNN_EINVAL, f"query_labels holds {ql.size} elements, needs {te.n}")
+        correct = None if ql is None else np.zeros(max(kmax, 0), np.int64)
+        sc = np.zeros((te.n, max(num_classes, 0)), np.float32) if scores else None
+        if self.cache_train:
+            self._train_key = keep1
+        self._check(self.lib.knn_sweep_weighted(self.h, ctypes.byref(tr), ctypes.byref(te), kmax, num_classes,
+                                                _weight_kind(weights), -1 if self_base is None else self_base,
+                                                _ptr(ql), _ptr(pred_all), _ptr(correct), _ptr(sc)))
+        return pred_all, correct, sc
+
     def generate(self, feat, labels, row0, d, kind, seed, stream_id, num_classes, dtype=None,
                  stream=None):
         """Fill a device tensor [n][ld] (and labels) with the synthetic rows of SURVEY.md 8d.
@@ -811,6 +945,26 @@ def best_k(correct):
     if c.ndim != 1 or c.size == 0:
         raise KnnError(KNN_EINVAL, "correct must be a non-empty 1-D array")
     return int(np.argmax(c)) + 1  # argmax returns the first maximum
+
+
+def _weight_kind(weights):
+    """A key of WEIGHTS, or a knn_weight number (passed on: the library rejects unknown ones)."""
+    if isinstance(weights, str):
+        if weights not in WEIGHTS:
+            raise KnnError(KNN_EINVAL, f"weights must be one of {sorted(WEIGHTS)}, got {weights!r}")
+        return WEIGHTS[weights]
+    return int(weights)
+
+
+def proba(scores):
+    """Class probabilities from a weighted vote's scores [nq][C] (numpy array or tensor):
+    scores / scores.sum(1), as sklearn's predict_proba.  Rows that sum to 0 (too few neighbours)
+    or hold inf give nan."""
+    if hasattr(scores, "cpu"):
+        return scores / scores.sum(dim=1, keepdim=True)
+    s = np.asarray(scores, np.float32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return s / s.sum(axis=1, keepdims=True)
 
 
 def computeConfusionMatrix(predictions, labels, num_classes):

@@ -776,7 +776,8 @@ int* KNN(ArffData* train, ArffData* test, int k, int start, int end) {
 }
 
 // the k-sweep on the first device: test == train with self-exclusion for leave-one-out
-static int* sweep_on_device0(ArffData* train, ArffData* test, int kmax, bool loo) {
+// (weights < 0: the uniform vote of knn_sweep; else knn_sweep_weighted with that kind)
+static int* sweep_on_device0(ArffData* train, ArffData* test, int kmax, bool loo, int weights = -1) {
     const KnnFlatView& tr = train->flat();
     const KnnFlatView& te = test->flat();
     if (kmax < 1) throwf("KNN_sweep: kmax=%d must be >= 1", kmax);
@@ -791,9 +792,12 @@ static int* sweep_on_device0(ArffData* train, ArffData* test, int kmax, bool loo
         std::vector<knn_ctx*>& cs = contexts();
         std::lock_guard<std::mutex> busy(*devices().busy[0]);
         s = knn_set_generation(cs[0], tr.uid);
-        if (s == KNN_OK)
+        if (s == KNN_OK && weights < 0)
             s = knn_sweep(cs[0], &dtr, &dte, kmax, (int)train->num_classes(), loo ? 0 : -1, nullptr,
                           reinterpret_cast<int32_t*>(pred), nullptr);
+        else if (s == KNN_OK)
+            s = knn_sweep_weighted(cs[0], &dtr, &dte, kmax, (int)train->num_classes(), weights, loo ? 0 : -1, nullptr,
+                                   reinterpret_cast<int32_t*>(pred), nullptr, nullptr);
         if (s != KNN_OK) why = knn_last_error(cs[0]);
     } catch (...) {
         std::free(pred);
@@ -809,6 +813,16 @@ static int* sweep_on_device0(ArffData* train, ArffData* test, int kmax, bool loo
 int* KNN_sweep(ArffData* train, ArffData* test, int kmax) { return sweep_on_device0(train, test, kmax, false); }
 
 int* KNN_sweep_loo(ArffData* train, int kmax) { return sweep_on_device0(train, train, kmax, true); }
+
+int* KNN_sweep_weighted(ArffData* train, ArffData* test, int kmax, int weights) {
+    if (weights < 0) throwf("KNN_sweep_weighted: unknown weights=%d", weights);
+    return sweep_on_device0(train, test, kmax, false, weights);
+}
+
+int* KNN_sweep_loo_weighted(ArffData* train, int kmax, int weights) {
+    if (weights < 0) throwf("KNN_sweep_loo_weighted: unknown weights=%d", weights);
+    return sweep_on_device0(train, train, kmax, true, weights);
+}
 
 void* KNN(void* params) {
     arguments* a = static_cast<arguments*>(params);

@@ -97,7 +97,7 @@ struct knn_ctx {
     bool ctrl_clean = false;  // the status words are zero (the last call ended in k_finish)
     // k-sweep (knn_sweep_device / knn_sweep): the top-kin lists of the pass, and the host entry
     // point's device copies of its outputs and query labels; sized once and grown like the others
-    DBuf sw_dist, sw_idx, sw_pred, sw_ql, sw_correct;
+    DBuf sw_dist, sw_idx, sw_pred, sw_ql, sw_correct, sw_scores;
     DBuf arrive;              // k_direct_rows' fused merge: per query group, segments finished
     bool arrive_clean = false;  // arrive is all zero (the last launch ran to completion)
     bool merge_kernel = false;  // study switch KNN_DIRECT_MERGE_KERNEL=1: k_direct_rows' segments via k_merge_vote
@@ -263,6 +263,7 @@ knn_status check_status(knn_ctx* c, const int32_t* ctrl) {
     if (status & KNN_STATUS_BAD_LABEL) return fail(c, KNN_EINVAL, "a train label is outside [0, num_classes)");
     if (status & KNN_STATUS_UNSORTED)
         return fail(c, KNN_EINVAL, "merge: a source neighbour list is not ascending by (distance, index)");
+    if (status & KNN_STATUS_BAD_DIST) return fail(c, KNN_EINVAL, "weighted vote: a neighbour distance is NaN or negative");
     if (status & KNN_STATUS_TOO_FEW) return fail(c, KNN_ERANGE, "fewer than k train rows have a finite distance (< FLT_MAX)");
     return KNN_OK;
 }
@@ -864,7 +865,7 @@ void knn_destroy(knn_ctx* c) {
     (void)hipSetDevice(c->device);
     for (DBuf* b : {&c->tnorm, &c->tnp, &c->qnorm, &c->gthr, &c->cnt, &c->cand,
                     &c->fb_list, &c->ctrl, &c->scratch, &c->split_t, &c->split_q, &c->pad_t, &c->seg_rec, &c->arrive, &c->tmax, &c->tsmax, &c->qstat, &c->tblk, &c->tctrl, &c->cursor, &c->lshare, &c->h_train, &c->h_labels, &c->h_test, &c->h_pred,
-                    &c->h_dist, &c->h_idx, &c->sw_dist, &c->sw_idx, &c->sw_pred, &c->sw_ql, &c->sw_correct})
+                    &c->h_dist, &c->h_idx, &c->sw_dist, &c->sw_idx, &c->sw_pred, &c->sw_ql, &c->sw_correct, &c->sw_scores})
         b->release();
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; i++) {
@@ -1141,13 +1142,46 @@ knn_status vote_sweep_enqueue(knn_ctx* c, int64_t nq, int kin, int C, const int3
     return KNN_OK;
 }
 
+// the weighted vote behind a pass (sweep_core): the kind, the first prefix row written (pred_all
+// then points at that row) and the per-class scores [nq][C] (optional)
+struct WeightedVote {
+    int weights;
+    int row0;
+    float* scores;
+};
+
+// k_vote_weighted on lists in device memory, enqueued on st (no synchronisation); scores is
+// zeroed here, ahead of the kernel on the same stream
+knn_status vote_weighted_enqueue(knn_ctx* c, int64_t nq, int kin, int C, const int32_t* idx, const float* dist,
+                                 int64_t stride, const int32_t* labels, const WeightedVote& wv, int64_t self_base,
+                                 const int32_t* qlabels, int32_t* pred_all, int64_t pred_stride, int64_t* correct,
+                                 float* dist_out, int32_t* idx_out, bool check_dist, hipStream_t st) {
+    VoteWeightedArgs v{};
+    v.idx = idx; v.dist = dist; v.stride = stride; v.labels = labels;
+    v.nq = nq; v.kin = kin; v.kmax = self_base >= 0 ? kin - 1 : kin; v.C = C; v.weights = wv.weights;
+    v.self_base = self_base;
+    v.qlabels = qlabels; v.pred_all = pred_all; v.pred_stride = pred_stride; v.row0 = wv.row0;
+    v.correct = reinterpret_cast<unsigned long long*>(correct);
+    v.scores = wv.scores; v.dist_out = dist ? dist_out : nullptr; v.idx_out = idx_out;
+    v.check_dist = check_dist ? 1 : 0;
+    v.status = c->ctrl.as<int32_t>();
+    stage_begin(c, st, "vote_weighted");
+    if (wv.scores && nq > 0) HIP_OR_FAIL(c, hipMemsetAsync(wv.scores, 0, sizeof(float) * (size_t)nq * (size_t)C, st));
+    HIP_OR_FAIL(c, knn_launch_vote_weighted(v, st));
+    stage_end(c, st);
+    return KNN_OK;
+}
+
 // The sweep over device datasets: one top-kin pass with no vote (QueryOut.pred == NULL) into the
 // context's list workspace, k_vote_sweep behind it on the same stream, one finish_call.  (The
 // GEMM path runs more than c->ws_queries queries in passes, like predict_core; each pass ends
 // in its own finish_call and adds into d_correct.)  d_pred_all rows are pred_stride apart.
+// wv != NULL: the pass keeps its distances whether or not the caller asked for them, and
+// k_vote_weighted votes instead (knn_sweep_weighted_device / knn_predict_weighted_device).
 knn_status sweep_core(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
                       int64_t self_base, const int32_t* d_qlabels, int32_t* d_pred_all, int64_t pred_stride,
-                      int64_t* d_correct, float* d_dist, int32_t* d_idx, hipStream_t st) {
+                      int64_t* d_correct, float* d_dist, int32_t* d_idx, hipStream_t st,
+                      const WeightedVote* wv = nullptr) {
     knn_status s;
     const int kin = kmax + (self_base >= 0 ? 1 : 0);
     QueryOut out{nullptr, nullptr, nullptr, nullptr, kin, 0};
@@ -1166,18 +1200,28 @@ knn_status sweep_core(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, 
     const int64_t pass = gemm ? std::max<int64_t>(1, c->ws_queries) : te->n;
     const int64_t rows = std::min(pass, te->n);
     HIP_OR_FAIL(c, c->sw_idx.ensure(sizeof(int32_t) * (size_t)rows * kin));
-    if (d_dist) HIP_OR_FAIL(c, c->sw_dist.ensure(sizeof(float) * (size_t)rows * kin));
+    if (d_dist || wv) HIP_OR_FAIL(c, c->sw_dist.ensure(sizeof(float) * (size_t)rows * kin));
     out.idx = c->sw_idx.as<int32_t>();
-    out.dist = d_dist ? c->sw_dist.as<float>() : nullptr;
+    out.dist = (d_dist || wv) ? c->sw_dist.as<float>() : nullptr;
     for (int64_t q0 = 0; q0 < te->n; q0 += pass) {
         const int64_t n = std::min(pass, te->n - q0);
         const knn_dataset tq = offset_rows(*te, q0, n);
-        if ((s = predict_enqueue(c, tr, &tq, kin, C, out, st, algo, nullptr)) != KNN_OK ||
-            (s = vote_sweep_enqueue(c, n, kin, C, out.idx, kin, tr->labels, self_base >= 0 ? self_base + q0 : -1,
-                                    d_qlabels ? d_qlabels + q0 : nullptr, d_pred_all ? d_pred_all + q0 : nullptr,
-                                    pred_stride, d_correct, out.dist, d_dist ? d_dist + q0 * kmax : nullptr,
-                                    d_idx ? d_idx + q0 * kmax : nullptr, st)) != KNN_OK ||
-            (s = finish_call(c, st)) != KNN_OK) {
+        if ((s = predict_enqueue(c, tr, &tq, kin, C, out, st, algo, nullptr)) == KNN_OK) {
+            if (wv) {
+                const WeightedVote w{wv->weights, wv->row0, wv->scores ? wv->scores + q0 * C : nullptr};
+                s = vote_weighted_enqueue(c, n, kin, C, out.idx, out.dist, kin, tr->labels, w,
+                                          self_base >= 0 ? self_base + q0 : -1, d_qlabels ? d_qlabels + q0 : nullptr,
+                                          d_pred_all ? d_pred_all + q0 : nullptr, pred_stride, d_correct,
+                                          d_dist ? d_dist + q0 * kmax : nullptr, d_idx ? d_idx + q0 * kmax : nullptr,
+                                          false, st);
+            } else {
+                s = vote_sweep_enqueue(c, n, kin, C, out.idx, kin, tr->labels, self_base >= 0 ? self_base + q0 : -1,
+                                       d_qlabels ? d_qlabels + q0 : nullptr, d_pred_all ? d_pred_all + q0 : nullptr,
+                                       pred_stride, d_correct, out.dist, d_dist ? d_dist + q0 * kmax : nullptr,
+                                       d_idx ? d_idx + q0 * kmax : nullptr, st);
+            }
+        }
+        if (s != KNN_OK || (s = finish_call(c, st)) != KNN_OK) {
             if (s != KNN_EINVAL && s != KNN_ERANGE) c->tprep.valid = c->tpad.valid = false;  // a HIP failure: the operands may be partial
             return s;
         }
@@ -1227,14 +1271,36 @@ knn_status knn_sweep_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset
                       d_topk_dist, d_topk_idx, st);
 }
 
-knn_status knn_sweep(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
-                     int64_t self_base, const int32_t* query_labels, int32_t* out_pred_all, int64_t* out_correct) {
-    if (!c) return KNN_EINVAL;
-    c->err.clear();
+}  // extern "C"
+
+namespace {
+
+// what the weighted entry points share: the kind, the outputs asked for and the list length
+knn_status weighted_check(knn_ctx* c, int32_t kmax, int32_t weights, int64_t self_base, const void* qlabels,
+                          const void* pred_all, const void* correct, const void* scores) {
+    if (weights != KNN_W_UNIFORM && weights != KNN_W_INV_DIST && weights != KNN_W_INV_SQDIST)
+        return fail(c, KNN_EINVAL, "weighted vote: unknown weights=%d", weights);
+    if (kmax < 1) return fail(c, KNN_EINVAL, "weighted vote: kmax=%d must be >= 1", kmax);
+    if (!qlabels && !pred_all && !correct && !scores)
+        return fail(c, KNN_EINVAL, "weighted vote: query labels, pred_all, correct and scores are all NULL");
+    if (correct && !qlabels) return fail(c, KNN_EINVAL, "weighted vote: correct needs the query labels");
+    if (self_base >= 0 && kmax + 1 > 1024)
+        return fail(c, KNN_EINVAL, "weighted vote: kmax=%d + the self row exceeds the supported maximum 1024", kmax);
+    return KNN_OK;
+}
+
+// knn_sweep and knn_sweep_weighted (wv != NULL: out_scores [nq][C] optional)
+knn_status sweep_host(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
+                      int64_t self_base, const int32_t* query_labels, int32_t* out_pred_all, int64_t* out_correct,
+                      const WeightedVote* wv, float* out_scores) {
     knn_status s;
     if ((s = check_dataset(c, tr, "train", true)) != KNN_OK) return s;
     if ((s = check_dataset(c, te, "test", false)) != KNN_OK) return s;
-    if ((s = sweep_check(c, kmax, self_base, query_labels, out_pred_all, out_correct)) != KNN_OK) return s;
+    if (wv)
+        s = weighted_check(c, kmax, wv->weights, self_base, query_labels, out_pred_all, out_correct, out_scores);
+    else
+        s = sweep_check(c, kmax, self_base, query_labels, out_pred_all, out_correct);
+    if (s != KNN_OK) return s;
     if (tr->d != te->d) return fail(c, KNN_EINVAL, "feature count mismatch: train d=%d test d=%d", tr->d, te->d);
     if (tr->dtype != te->dtype) return fail(c, KNN_EINVAL, "train and test dtypes differ");
     const int64_t nq = te->n;
@@ -1251,7 +1317,9 @@ knn_status knn_sweep(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, i
     const int d = tr->d;
     const size_t es = (size_t)elem_size(tr->dtype);
     const int ldd = (int)((d + (int)(16 / es) - 1) / (int)(16 / es) * (int)(16 / es));  // device rows padded to 16 B
-    const int64_t B = std::min<int64_t>(nq, c->batch_rows);
+    int64_t B = std::min<int64_t>(nq, c->batch_rows);
+    // (the device copy of a batch's scores stays under 256 MiB)
+    if (out_scores && C >= 1) B = std::min<int64_t>(B, std::max<int64_t>(1, ((int64_t)64 << 20) / C));
     {
         // the device call's checks on the shapes it will see, before anything is enqueued
         const knn_dataset vtr{(const void*)(uintptr_t)256, tr->labels, tr->n, d, ldd, tr->dtype};
@@ -1273,6 +1341,8 @@ knn_status knn_sweep(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, i
     if (out_pred_all) HIP_OR_ABORT(c->sw_pred.ensure(sizeof(int32_t) * (size_t)kmax * B));
     if (query_labels) HIP_OR_ABORT(c->sw_ql.ensure(sizeof(int32_t) * (size_t)B));
     if (out_correct) HIP_OR_ABORT(c->sw_correct.ensure(sizeof(int64_t) * (size_t)kmax));
+    if (out_scores) HIP_OR_ABORT(c->sw_scores.ensure(sizeof(float) * (size_t)B * (size_t)C));
+    const WeightedVote wvd{wv ? wv->weights : 0, 0, out_scores ? c->sw_scores.as<float>() : nullptr};
     std::vector<int64_t> part(out_correct ? kmax : 0);
     // one batch after another, each uploaded, swept and downloaded before the next starts
     for (int64_t q0 = 0; q0 < nq; q0 += B) {
@@ -1285,7 +1355,7 @@ knn_status knn_sweep(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, i
         const knn_dataset dq{c->q_slot[0].p, nullptr, n, d, ldd, te->dtype};
         s = sweep_core(c, &dtr, &dq, kmax, C, self_base >= 0 ? self_base + q0 : -1,
                        query_labels ? c->sw_ql.as<int32_t>() : nullptr, out_pred_all ? c->sw_pred.as<int32_t>() : nullptr,
-                       n, out_correct ? c->sw_correct.as<int64_t>() : nullptr, nullptr, nullptr, st);
+                       n, out_correct ? c->sw_correct.as<int64_t>() : nullptr, nullptr, nullptr, st, wv ? &wvd : nullptr);
         if (s != KNN_OK) return abort_call(s);
         // (synchronous copies on the null stream: ordered after the context's blocking stream)
         if (out_pred_all)
@@ -1295,8 +1365,88 @@ knn_status knn_sweep(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, i
             HIP_OR_ABORT(hipMemcpy(part.data(), c->sw_correct.p, sizeof(int64_t) * (size_t)kmax, hipMemcpyDeviceToHost));
             for (int i = 0; i < kmax; i++) out_correct[i] += part[i];
         }
+        if (out_scores)
+            HIP_OR_ABORT(hipMemcpy(out_scores + (size_t)q0 * (size_t)C, c->sw_scores.p, sizeof(float) * (size_t)n * (size_t)C,
+                                   hipMemcpyDeviceToHost));
     }
     return KNN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+knn_status knn_sweep(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
+                     int64_t self_base, const int32_t* query_labels, int32_t* out_pred_all, int64_t* out_correct) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    return sweep_host(c, tr, te, kmax, C, self_base, query_labels, out_pred_all, out_correct, nullptr, nullptr);
+}
+
+knn_status knn_sweep_weighted(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
+                              int32_t weights, int64_t self_base, const int32_t* query_labels, int32_t* out_pred_all,
+                              int64_t* out_correct, float* out_scores) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    const WeightedVote wv{weights, 0, nullptr};
+    return sweep_host(c, tr, te, kmax, C, self_base, query_labels, out_pred_all, out_correct, &wv, out_scores);
+}
+
+knn_status knn_vote_weighted_device(knn_ctx* c, int64_t nq, int32_t kin, int32_t C, const int32_t* d_idx,
+                                    const float* d_dist, int64_t stride, const int32_t* d_train_labels,
+                                    int32_t weights, int64_t self_base, const int32_t* d_query_labels,
+                                    int32_t* d_pred_all, int64_t* d_correct, float* d_scores, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    c->stages.clear();
+    const int32_t kmax = self_base >= 0 ? kin - 1 : kin;
+    if (nq < 0 || kin < 1 || kin > 1024 || stride < kin || C < 1 || C > 16384)
+        return fail(c, KNN_EINVAL, "weighted vote: bad nq=%lld kin=%d stride=%lld C=%d", (long long)nq, kin,
+                    (long long)stride, C);
+    knn_status s;
+    if ((s = weighted_check(c, kmax, weights, self_base, d_query_labels, d_pred_all, d_correct, d_scores)) != KNN_OK)
+        return s;
+    if (nq > 0 && (!d_idx || !d_train_labels || (!d_dist && weights != KNN_W_UNIFORM)))
+        return fail(c, KNN_EINVAL, "weighted vote: d_idx / d_dist / d_train_labels is NULL");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    if (d_correct) HIP_OR_FAIL(c, hipMemsetAsync(d_correct, 0, sizeof(int64_t) * (size_t)kmax, st));
+    const WeightedVote wv{weights, 0, d_scores};
+    if ((s = vote_weighted_enqueue(c, nq, kin, C, d_idx, d_dist, stride, d_train_labels, wv, self_base,
+                                   d_query_labels, d_pred_all, nq, d_correct, nullptr, nullptr, true, st)) != KNN_OK)
+        return s;
+    return finish_call(c, st);
+}
+
+knn_status knn_sweep_weighted_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax,
+                                     int32_t C, int32_t weights, int64_t self_base, const int32_t* d_query_labels,
+                                     int32_t* d_pred_all, int64_t* d_correct, float* d_scores, float* d_topk_dist,
+                                     int32_t* d_topk_idx, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    knn_status s;
+    if ((s = weighted_check(c, kmax, weights, self_base, d_query_labels, d_pred_all, d_correct, d_scores)) != KNN_OK)
+        return s;
+    reset_stats(c);
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const WeightedVote wv{weights, 0, d_scores};
+    return sweep_core(c, tr, te, kmax, C, self_base, d_query_labels, d_pred_all, te ? te->n : 0, d_correct,
+                      d_topk_dist, d_topk_idx, st, &wv);
+}
+
+knn_status knn_predict_weighted_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t k,
+                                       int32_t C, int32_t weights, int32_t* d_pred, float* d_scores,
+                                       float* d_topk_dist, int32_t* d_topk_idx, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    knn_status s;
+    if ((s = weighted_check(c, k, weights, -1, nullptr, d_pred, nullptr, d_scores)) != KNN_OK) return s;
+    reset_stats(c);
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    // only row k - 1 of the prefix votes is staged and stored: d_pred is that row
+    const WeightedVote wv{weights, k - 1, d_scores};
+    return sweep_core(c, tr, te, k, C, -1, nullptr, d_pred, te ? te->n : 0, nullptr, d_topk_dist, d_topk_idx, st, &wv);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // knn_cli.cpp -- command-line driver with the reference's contract.
 //
 //   knn_cli train.arff test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]]
+//           [--weights=uniform|distance|sqdist]
 //
 // Same positional arguments as ./main (main.cpp:114-122; k parsed with strtol) plus the
 // optional worker count of ./multi-thread (multi-thread.cpp:135-143), here the number of
@@ -12,6 +13,9 @@
 // k's accuracy (computeConfusionMatrix / computeAccuracy on row k - 1, so the float is the
 // reference's) and the one call's time on every line.  --sweep=loo: leave-one-out on the
 // train file (KNN_sweep_loo); the test path keeps its position and is not read.
+// --weights=distance|sqdist: the weighted vote (KNN_sweep_weighted / KNN_sweep_loo_weighted),
+// with --sweep a line per k, without it the one line for k (row k - 1 of the same call).
+// --weights=uniform is the default and changes nothing.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -26,15 +30,23 @@ int main(int argc, char* argv[]) {
     // --shard=... may sit anywhere; the rest are the reference's positional arguments
     int n = 0;
     bool sweep = false, loo = false;
+    int weights = 0;  // knn_weight
     for (int i = 0; i < argc; i++) {
         if (!std::strncmp(argv[i], "--shard=", 8)) setenv("KNN_AMD_SHARD", argv[i] + 8, 1);
         else if (!std::strcmp(argv[i], "--sweep")) sweep = true;
         else if (!std::strcmp(argv[i], "--sweep=loo")) sweep = loo = true;
+        else if (!std::strcmp(argv[i], "--weights=uniform")) weights = 0;
+        else if (!std::strcmp(argv[i], "--weights=distance")) weights = 1;
+        else if (!std::strcmp(argv[i], "--weights=sqdist")) weights = 2;
+        else if (!std::strncmp(argv[i], "--weights=", 10)) {
+            std::cerr << "unknown " << argv[i] << " (uniform, distance or sqdist)" << std::endl;
+            std::exit(2);
+        }
         else argv[n++] = argv[i];
     }
     argc = n;
     if (argc != 4 && argc != 5) {
-        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]]"
+        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist]"
                   << std::endl;
         std::exit(0);
     }
@@ -48,13 +60,14 @@ int main(int argc, char* argv[]) {
     knn_amd_init();
 
     struct timespec start, end;
-    if (sweep) {
+    if (sweep || weights) {
         clock_gettime(CLOCK_MONOTONIC_RAW, &start);
-        int* all = loo ? KNN_sweep_loo(train, k) : KNN_sweep(train, test, k);
+        int* all = weights ? (loo ? KNN_sweep_loo_weighted(train, k, weights) : KNN_sweep_weighted(train, test, k, weights))
+                           : (loo ? KNN_sweep_loo(train, k) : KNN_sweep(train, test, k));
         clock_gettime(CLOCK_MONOTONIC_RAW, &end);
         uint64_t diff = (1000000000L * (end.tv_sec - start.tv_sec) + end.tv_nsec - start.tv_nsec) / 1e6;
         const long nq = test->num_instances();
-        for (int kk = 1; kk <= k; kk++) {
+        for (int kk = sweep ? 1 : k; kk <= k; kk++) {
             int* confusionMatrix = computeConfusionMatrix(all + (size_t)(kk - 1) * nq, test);
             float accuracy = computeAccuracy(confusionMatrix, test);
             printf("The %i-NN classifier for %lu test instances on %lu train instances required %llu ms CPU time. Accuracy was %.4f\n",
@@ -63,10 +76,12 @@ int main(int argc, char* argv[]) {
         }
         if (const char* p = std::getenv("KNN_CLI_PRED_OUT")) {  // test hook: K lines of n predictions
             FILE* f = std::fopen(p, "w");
-            for (int kk = 0; kk < k; kk++) {
+            for (int kk = 0; sweep && kk < k; kk++) {
                 for (long q = 0; q < nq; q++) std::fprintf(f, q ? " %d" : "%d", all[(size_t)kk * nq + q]);
                 std::fprintf(f, "\n");
             }
+            // (without --sweep: the single-k dump's layout, one prediction per line)
+            for (long q = 0; !sweep && q < nq; q++) std::fprintf(f, "%d\n", all[(size_t)(k - 1) * nq + q]);
             std::fclose(f);
         }
         std::free(all);

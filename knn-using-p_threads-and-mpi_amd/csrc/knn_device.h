@@ -1,6 +1,7 @@
 // knn_device.h -- device helpers shared by the kernel translation units of libknn_amd
-// (knn_kernels.hip, knn_fused.hip): keys and wave bitonic networks, bf16 helpers,
-// ordered-float bits, LDS-DMA issue and the GEMM filter tile geometry.
+// (knn_kernels.hip, knn_fused.hip, knn_fused16.hip, knn_vote_weighted.hip): keys and wave
+// bitonic networks, bf16 helpers, ordered-float bits, LDS-DMA issue and the GEMM filter tile
+// geometry.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -8,6 +8,7 @@
 #define KNN_STATUS_BAD_LABEL 2     // a neighbour's label is outside [0, C)
 #define KNN_STATUS_GEMM_UNSAFE 4   // a row norm is too large for the GEMM certificate
 #define KNN_STATUS_UNSORTED 8      // k_merge_vote: a source list read was not ascending by (dist, idx)
+#define KNN_STATUS_BAD_DIST 16     // k_vote_weighted: a caller-supplied distance is NaN or negative
 
 // candidate-list capacity per query on the GEMM path (entries = 64 * CAPW)
 #define KNN_RESCORE_CAPW 32
@@ -110,6 +111,27 @@ struct VoteSweepArgs {
     int qb;  // queries per LDS tile (set by the launcher)
 };
 hipError_t knn_launch_vote_sweep(const VoteSweepArgs& a, hipStream_t st);
+
+// k_vote_weighted (knn_vote_weighted.hip): the distance-weighted vote and the per-class scores
+// over every prefix.  idx / dist: [nq][stride] lists (dist may be NULL for the uniform kind),
+// kin / kmax / self_base / labels / qlabels / dist_out / idx_out as VoteSweepArgs.  weights:
+// knn_weight.  Only the prefixes k - 1 >= row0 are written: pred_all (optional) points at row
+// row0 of [kmax][pred_stride]; correct (optional) is the whole [kmax], zeroed by the caller.
+// scores (optional) [nq][C] fp32, zeroed by the caller.  check_dist: flag NaN / negative
+// distances (KNN_STATUS_BAD_DIST).
+#define KNN_VOTE_W_UNIFORM 0
+#define KNN_VOTE_W_INV_DIST 1
+#define KNN_VOTE_W_INV_SQDIST 2
+struct VoteWeightedArgs {
+    const int32_t* idx; const float* dist; int64_t stride; const int32_t* labels;
+    int64_t nq; int kin; int kmax; int C; int weights; int64_t self_base;
+    const int32_t* qlabels; int32_t* pred_all; int64_t pred_stride; int row0; unsigned long long* correct;
+    float* scores; float* dist_out; int32_t* idx_out;
+    int check_dist;
+    int32_t* status;
+    int qb;  // queries per LDS tile (set by the launcher)
+};
+hipError_t knn_launch_vote_weighted(const VoteWeightedArgs& a, hipStream_t st);
 
 // class counts up to this many live in a per-wave LDS table; above it the vote runs
 // table-free (vote_ballot), so every path accepts any num_classes

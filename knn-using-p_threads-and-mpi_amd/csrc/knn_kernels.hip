@@ -24,6 +24,7 @@
 //   k_rescore      exact direct-form rescore of the surviving candidates + top-k + vote
 //   k_merge_vote   merge of per-train-shard neighbour lists (train-sharded runs) + vote
 //   k_vote_sweep   the vote for every prefix k <= K of a neighbour list (k-sweep, leave-one-out)
+//                  (its distance-weighted sibling k_vote_weighted: knn_vote_weighted.hip)
 //   k_generate     counter-based synthetic rows (same formula as oracle/knn_oracle.c)
 #include <hip/hip_runtime.h>
 #include <float.h>
