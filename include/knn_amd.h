@@ -124,6 +124,41 @@ void knn_destroy(knn_ctx* ctx);
 /* Text of the last error on this context ("" if none). */
 const char* knn_last_error(const knn_ctx* ctx);
 
+/*
+ * Metrics.  A context computes one distance, KNN_METRIC_SQEUCLIDEAN (the reference's, and the
+ * default: everything in "Semantics" above, bit for bit as before) or one of
+ *   KNN_METRIC_MANHATTAN  D = sum_{i<d} |q_i - t_i|: sum = +0, then for i ascending
+ *                         df = fl(q_i - t_i), sum = fl(sum + |df|) in IEEE binary32 -- no FMA, no
+ *                         reordering, no tree, subnormals kept;
+ *   KNN_METRIC_CHEBYSHEV  D = max_i |q_i - t_i|: m = +0, then m = fmaxf(m, |fl(q_i - t_i)|).
+ *                         fmaxf ignores a NaN operand, as numpy.fmax does: a NaN difference (a NaN
+ *                         feature, inf - inf) leaves the maximum as it was, so such a row is
+ *                         ranked by its other features.  Under Manhattan it makes the sum NaN and
+ *                         the row never qualifies.
+ * bf16 rows widen exactly to fp32 first.  Everything else is "Semantics": neighbours are the k
+ * smallest (D, train index) pairs, lower index first on ties, with the strict '<' against the
+ * FLT_MAX sentinel (a D that is NaN, inf or >= FLT_MAX never qualifies); the reported distance is
+ * D itself; vote, k-sweep, self-removal, KNN_ERANGE and KNN_EINVAL are unchanged.
+ * Weighted vote under a non-Euclidean metric: the reported distance is no square, so
+ * KNN_W_INV_DIST (sklearn's weights="distance") is w = 1.0f / D, and KNN_W_INV_SQDIST is
+ * KNN_EINVAL (there is no 1 / D^2 kind); knn_vote_weighted_device on lists the caller holds
+ * follows the context's metric in the same way.  The zero rule (D == 0) and the sums are unchanged.
+ *
+ * knn_set_metric may be called between any two calls on the context; every entry point that
+ * runs a top-k pass then uses it (knn_predict, knn_predict_device, knn_shard_topk_device,
+ * knn_predict_train_sharded, knn_sweep, knn_sweep_device and the weighted entry points), through
+ * the direct form's metric kernel (k_metric_tile) for every shape.  KNN_EINVAL for an unknown
+ * metric, and for a non-zero metric on a context created with KNN_ALGO_GEMM, KNN_ALGO_GEMM_SPLIT,
+ * KNN_ALGO_GEMM_BF16 or KNN_ALGO_DIRECT_SCAN (the GEMM form and its certificate are Euclidean,
+ * and the scan kernel has no metric version); KNN_ALGO_AUTO and KNN_ALGO_DIRECT accept it.  Cached
+ * train uploads and filter operands do not depend on the metric and stay valid across a switch.
+ * With profile = 1 the pass's stage is named "metric_tile" (then "merge_vote" when segmented).
+ * Cosine ranking needs no metric: it is Euclidean ranking on rows the caller normalised.
+ */
+typedef enum { KNN_METRIC_SQEUCLIDEAN = 0, KNN_METRIC_MANHATTAN = 1, KNN_METRIC_CHEBYSHEV = 2 } knn_metric;
+knn_status knn_set_metric(knn_ctx* ctx, int32_t metric);
+int32_t knn_get_metric(const knn_ctx* ctx);
+
 /* Invalidates cached train uploads and cached train-side filter operands
  * (KNN_OPT_CACHE_TRAIN): both cache keys include this generation.  The reference has no counterpart (every KNN() call re-reads ArffData,
  * main.cpp:40-43). */
@@ -312,7 +347,7 @@ knn_status knn_sweep(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* 
  * answered from the same ordered neighbour lists as the k-sweep (no reference counterpart; the
  * uniform kind is the reference's vote, main.cpp:64-78).  The neighbour list is unchanged: the k
  * smallest (distance, train index) pairs, distances the fp32 squared Euclidean values reported
- * everywhere else.
+ * everywhere else (the default metric; "Metrics" above gives the mapping under the others).
  *   weight    w_j = 1 (KNN_W_UNIFORM), 1.0f / sqrtf(d_j) (KNN_W_INV_DIST: sklearn's
  *             weights="distance" on the Euclidean distance) or 1.0f / d_j (KNN_W_INV_SQDIST), in
  *             IEEE binary32: round to nearest, subnormals kept, inf an ordinary value.

@@ -190,6 +190,9 @@ float computeAccuracy(int* confusionMatrix, ArffData* dataset);
 // partition over them: env KNN_AMD_SHARD = test (default, the reference's split of the test
 // set, train replicated), train (train rows split by the same rule, per-shard exact top-k
 // merged on device 0 by (distance, global index)) or auto (knn_shard_policy).
+// The distance of every KNN* call: env KNN_AMD_METRIC = euclidean (default: the reference's
+// squared Euclidean distance), manhattan or chebyshev (knn_amd.h "Metrics"), read when the
+// contexts are created; an unknown value throws.
 int knn_amd_num_devices();
 // Create the device contexts up front (the CLI does this before its timed region,
 // as the reference parses and MPI_Init()s before starting its clock).

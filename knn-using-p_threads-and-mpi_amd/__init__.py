@@ -17,6 +17,11 @@ Names follow the reference (srna99/KNN-using-p_threads-and-MPI):
 * ``Context.sweep_weighted_device / loo_weighted_device / vote_weighted_device /
   predict_weighted_device / sweep_weighted``, ``WEIGHTS`` and ``proba``: the same with the
   distance-weighted vote and per-class scores (no reference counterpart)
+* ``METRICS``, ``Context(metric=...)``, ``Context.set_metric`` and ``Context.metric``: the distance a
+  context computes -- "euclidean" (squared Euclidean, the reference's and the default), "manhattan"
+  or "chebyshev"; every predict / top-k / sweep / weighted call of the context follows it (no
+  reference counterpart; the rules are in ``knn_amd.h`` "Metrics").  Under the last two
+  ``weights="distance"`` is 1 / D and ``"sqdist"`` is rejected.
 
 Features are fp32 or bf16.  Host bf16 arrays are numpy ``uint16`` holding bf16 bits
 (``to_bf16_bits`` / ``bf16_bits_to_f32``); device tensors are ``torch.bfloat16``.
@@ -42,6 +47,8 @@ KNN_F32, KNN_BF16 = 0, 1
 ALGOS = {"auto": 0, "direct": 1, "gemm": 2, "gemm_split": 3, "gemm_bf16": 4, "direct_scan": 5}
 # knn_weight: the vote's weight kinds ("distance" is sklearn's weights="distance")
 WEIGHTS = {"uniform": 0, "distance": 1, "sqdist": 2}
+# knn_metric: the distance a context computes ("euclidean" is the reference's squared Euclidean)
+METRICS = {"euclidean": 0, "manhattan": 1, "chebyshev": 2}
 FILTER_OPERANDS = {-1: None, 0: "f32", 1: "bf16", 2: "bf16x3 split", 3: "bf16 rounded"}
 
 
@@ -122,6 +129,8 @@ def load_library(path=LIB_PATH):
                                ctypes.c_uint32, I32, P]),
         "knn_mfma_probe_bf16": (I32, [P, P, P, I32, P, P]),
         "knn_set_generation": (I32, [P, ctypes.c_uint64]),
+        "knn_set_metric": (I32, [P, I32]),
+        "knn_get_metric": (I32, [P]),
         "knn_comm_unique_id": (I32, [P]),
         "knn_comm_create": (I32, [P, P, I32, I32, ctypes.POINTER(P)]),
         "knn_comm_destroy": (None, [P]),
@@ -324,8 +333,10 @@ def train_sharded_predict(ctx, train_shard, labels_shard, idx_base, test, k, num
 class Context:
     """One device, one HIP stream (knn_create / knn_destroy)."""
 
-    def __init__(self, device=0, algo="auto", train_splits=0, profile=False, cache_train=False):
+    def __init__(self, device=0, algo="auto", train_splits=0, profile=False, cache_train=False,
+                 metric="euclidean"):
         self.lib = load_library()
+        # metric: a key of METRICS (or its number), set_metric changes it between calls
         # profile: False/0 off, True/1 per-stage HIP events, 2 = also count filter candidates,
         # 3 = events around the dominant stages only (filter, rescore, ...: knn_amd.h)
         # cache_train: predict() keeps the device copy of train across calls (KNN_OPT_CACHE_TRAIN)
@@ -350,6 +361,12 @@ class Context:
         if st != KNN_OK:
             raise KnnError(st, f"knn_create(device={device}) failed")
         self.h = h
+        if _metric_kind(metric) != 0:
+            try:
+                self.set_metric(metric)
+            except KnnError:
+                self.close()
+                raise
 
     def _check(self, st):
         if st != KNN_OK:
@@ -718,6 +735,18 @@ class Context:
         self._check(self.lib.knn_set_generation(self.h, generation))
         self._generation = int(generation)
 
+    def set_metric(self, metric):
+        """The distance of every later call on this context (knn_set_metric): a key of METRICS or
+        its number.  KnnError(KNN_EINVAL) for an unknown metric, and for a non-Euclidean one on a
+        context whose algo is a GEMM form or "direct_scan"."""
+        self._check(self.lib.knn_set_metric(self.h, _metric_kind(metric)))
+
+    @property
+    def metric(self):
+        """The context's metric as a key of METRICS (knn_get_metric)."""
+        m = self.lib.knn_get_metric(self.h)
+        return next(name for name, v in METRICS.items() if v == m)
+
     def stage_times(self):
         names = (ctypes.c_char_p * 256)()
         ms = (ctypes.c_float * 256)()
@@ -954,6 +983,15 @@ def _weight_kind(weights):
             raise KnnError(KNN_EINVAL, f"weights must be one of {sorted(WEIGHTS)}, got {weights!r}")
         return WEIGHTS[weights]
     return int(weights)
+
+
+def _metric_kind(metric):
+    """A key of METRICS, or a knn_metric number (passed on: the library rejects unknown ones)."""
+    if isinstance(metric, str):
+        if metric not in METRICS:
+            raise KnnError(KNN_EINVAL, f"metric must be one of {sorted(METRICS)}, got {metric!r}")
+        return METRICS[metric]
+    return int(metric)
 
 
 def proba(scores):

@@ -389,10 +389,21 @@ Devices& devices() {
     return *D;
 }
 
+// The metric of the C++ API's contexts: KNN_AMD_METRIC = euclidean (default: the reference's
+// squared Euclidean distance), manhattan or chebyshev (knn_set_metric); anything else is an error
+int env_metric() {
+    const char* e = std::getenv("KNN_AMD_METRIC");
+    if (!e || !std::strcmp(e, "euclidean")) return KNN_METRIC_SQEUCLIDEAN;
+    if (!std::strcmp(e, "manhattan")) return KNN_METRIC_MANHATTAN;
+    if (!std::strcmp(e, "chebyshev")) return KNN_METRIC_CHEBYSHEV;
+    throwf("KNN: KNN_AMD_METRIC=%s (euclidean, manhattan or chebyshev)", e);
+}
+
 std::vector<knn_ctx*>& contexts() {
     Devices& D = devices();
     std::lock_guard<std::mutex> g(D.mu);
     if (D.ctx.empty()) {
+        const int metric = env_metric();
         int n = knn_amd_num_devices();
         int phys = 0;
         if (hipGetDeviceCount(&phys) != hipSuccess || phys < 1) phys = 1;
@@ -403,6 +414,11 @@ std::vector<knn_ctx*>& contexts() {
             if (s != KNN_OK) {
                 if (i == 0) throwf("KNN: no usable gfx950 device (knn_create status %d)", (int)s);
                 break;
+            }
+            if ((s = knn_set_metric(c, metric)) != KNN_OK) {
+                const std::string why = knn_last_error(c);
+                knn_destroy(c);
+                throwf("KNN: %s (status %d)", why.c_str(), (int)s);
             }
             D.ctx.push_back(c);
             D.busy.emplace_back(new std::mutex());

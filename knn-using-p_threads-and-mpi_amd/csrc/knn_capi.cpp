@@ -5,6 +5,7 @@
 // become one device pipeline per context:
 //   DIRECT:  k_exact_scan                                  (fused distance/top-k/vote)
 //   GEMM:    k_row_norms x2 -> k_gemm_filter -> k_rescore -> k_exact_scan(fallback list)
+//   a non-Euclidean metric (knn_set_metric): k_metric_tile (-> k_merge_vote), every shape
 // Train-sharded runs use the same pipeline per shard with the vote
 // replaced by a packed (dist, global idx, label) neighbour list, then k_merge_vote.
 #include <hip/hip_runtime.h>
@@ -21,6 +22,10 @@
 
 #include "../../include/knn_amd.h"
 #include "knn_kernels.h"
+
+static_assert(KNN_METRIC_SQEUCLIDEAN == METRIC_SQEUCLIDEAN && KNN_METRIC_MANHATTAN == METRIC_MANHATTAN &&
+                  KNN_METRIC_CHEBYSHEV == METRIC_CHEBYSHEV,
+              "knn_metric is passed to the launchers as is");
 
 namespace {
 
@@ -54,6 +59,7 @@ struct Stage {
 struct knn_ctx {
     int device = 0;
     int algo = KNN_ALGO_AUTO;
+    int metric = KNN_METRIC_SQEUCLIDEAN;  // knn_set_metric; no cached operand depends on it
     int train_splits = 0;
     int profile = 0;
     hipStream_t stream = nullptr;
@@ -162,7 +168,8 @@ knn_status fail(knn_ctx* c, knn_status s, const char* fmt, ...) {
 // stream a few microseconds: with every stage timed, A's 8-GPU share (12,500 queries) ran
 // 3.44 -> 3.56 ms per step, A 22.58 -> 22.73 (scripts/event_overhead.py, profiles/r04n).
 static bool hot_stage(const char* n) {
-    static const char* const hot[] = {"gemm_filter", "rescore", "direct_tile", "exact_scan", "merge_vote", "exchange"};
+    static const char* const hot[] = {"gemm_filter", "rescore", "direct_tile", "metric_tile", "exact_scan", "merge_vote",
+                                      "exchange"};
     for (const char* h : hot)
         if (!strcmp(n, h)) return true;
     return false;
@@ -216,6 +223,8 @@ bool is_gemm(int algo) {
 }
 
 int choose_algo(const knn_ctx* c, int64_t nt, int64_t nq, int d, int k, int dtype) {
+    // a non-Euclidean metric has the direct form only (k_metric_tile), whatever the shape
+    if (c->metric != KNN_METRIC_SQEUCLIDEAN) return KNN_ALGO_DIRECT;
     if (c->algo == KNN_ALGO_DIRECT || c->algo == KNN_ALGO_DIRECT_SCAN) return c->algo;
     // the LDS-DMA filter stages whole rows: a row must be one of its tile widths
     // (128, 256 or 512 bytes: fp32 d = 32/64/128 (fp32 or split), bf16 d = 64/128/256)
@@ -308,10 +317,15 @@ hipError_t reset_ctrl(knn_ctx* c, hipStream_t st) {
 // one costs a merge pass), at least 4 tiles per segment, records within 2 GB
 int choose_direct_segments(const knn_ctx* c, int64_t nt, int64_t nq, int d, int k, int C, int elem) {
     int qb = 1, occ = 1;
-    if (knn_direct_units(k, elem, d, C, &qb, &occ) != hipSuccess || occ < 1) occ = 1;
+    // (a metric has no rows form: its units are k_metric_tile's blocks for every shape)
+    const bool metric = c->metric != KNN_METRIC_SQEUCLIDEAN;
+    if ((metric ? knn_metric_units(c->metric, k, elem, d, C, &qb, &occ) : knn_direct_units(k, elem, d, C, &qb, &occ)) !=
+            hipSuccess ||
+        occ < 1)
+        occ = 1;
     const int64_t nqb = (nq + qb - 1) / qb;
     const int64_t slots = (int64_t)occ * c->num_cus;
-    if (qb < knn_direct_tile_qb(k)) {
+    if (!metric && qb < knn_direct_tile_qb(k)) {
         // k_direct_rows (a wave per unit): about one round of resident waves -- its waves need
         // no co-residents to hide a barrier, and every segment adds a sorted first tile and a
         // merge source (config L, 859 query pairs, same box: 4 segments 0.092 ms, 5 0.094, 8
@@ -372,6 +386,37 @@ knn_status run_direct_tile(knn_ctx* c, const knn_dataset* tr, const knn_dataset*
     }
     HIP_OR_FAIL(c, knn_launch_direct_tile(a, st));
     // (the merge is its own stage: "direct_tile" times the distance kernel alone)
+    stage_end(c, st);
+    stage_begin(c, st, "merge_vote");
+    MergeArgs m{};
+    m.rec = a.rec; m.nsrc = nseg; m.nq = te->n; m.k = k; m.C = C;
+    m.out = out; m.status = a.status; m.labels = tr->labels;
+    HIP_OR_FAIL(c, knn_launch_merge(m, st));
+    return KNN_OK;
+}
+
+// the direct form under a non-Euclidean metric: k_metric_tile (+ k_merge_vote of its segments,
+// sized from this kernel's units); never the rows form or its arrival counters
+knn_status run_metric_tile(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int k, int C,
+                           const QueryOut& out, hipStream_t st) {
+    DirectTileArgs a{};
+    a.train = tr->feat; a.labels = tr->labels; a.nt = tr->n; a.ld_t = tr->ld;
+    a.test = te->feat; a.ld_q = te->ld; a.nq = te->n;
+    a.d = tr->d; a.k = k; a.C = C; a.elem = tr->dtype;
+    a.status = c->ctrl.as<int32_t>();
+    const int nseg = c->train_splits > 0 ? std::min(32, c->train_splits)
+                                         : choose_direct_segments(c, tr->n, te->n, tr->d, k, C, tr->dtype);
+    a.nseg = nseg;
+    a.seg_len = (tr->n + nseg - 1) / nseg;
+    c->stats[2] = nseg;
+    if (nseg == 1) {
+        a.out = out;
+        HIP_OR_FAIL(c, knn_launch_metric_tile(a, c->metric, st));
+        return KNN_OK;
+    }
+    HIP_OR_FAIL(c, c->seg_rec.ensure(sizeof(int32_t) * 3 * (size_t)k * (size_t)te->n * nseg));
+    a.rec = c->seg_rec.as<int32_t>();
+    HIP_OR_FAIL(c, knn_launch_metric_tile(a, c->metric, st));
     stage_end(c, st);
     stage_begin(c, st, "merge_vote");
     MergeArgs m{};
@@ -928,7 +973,12 @@ knn_status predict_enqueue(knn_ctx* c, const knn_dataset* tr, const knn_dataset*
                            const QueryOut& out, hipStream_t st, int algo, int32_t* ctrl_copy) {
     knn_status s;
     HIP_OR_FAIL(c, reset_ctrl(c, st));
-    if (is_gemm(algo)) {
+    if (c->metric != KNN_METRIC_SQEUCLIDEAN) {
+        // (choose_algo gave KNN_ALGO_DIRECT; knn_set_metric refused the contexts that cannot)
+        stage_begin(c, st, "metric_tile");
+        if ((s = run_metric_tile(c, tr, te, k, C, out, st)) != KNN_OK) return s;
+        stage_end(c, st);
+    } else if (is_gemm(algo)) {
         // AUTO on fp32 data runs the rounded filter first; when more than 1/16 of the queries
         // (at least 256) overflow its candidate lists, the call is re-run with the split
         // filter (every output is rewritten).  The decision is made on the device
@@ -1158,7 +1208,11 @@ knn_status vote_weighted_enqueue(knn_ctx* c, int64_t nq, int kin, int C, const i
                                  float* dist_out, int32_t* idx_out, bool check_dist, hipStream_t st) {
     VoteWeightedArgs v{};
     v.idx = idx; v.dist = dist; v.stride = stride; v.labels = labels;
-    v.nq = nq; v.kin = kin; v.kmax = self_base >= 0 ? kin - 1 : kin; v.C = C; v.weights = wv.weights;
+    v.nq = nq; v.kin = kin; v.kmax = self_base >= 0 ? kin - 1 : kin; v.C = C;
+    // a non-Euclidean metric's distance is no square: KNN_W_INV_DIST is 1.0f / D there, the
+    // kernel's inverse-of-the-value kind (weighted_check refused KNN_W_INV_SQDIST)
+    v.weights = (c->metric != KNN_METRIC_SQEUCLIDEAN && wv.weights == KNN_W_INV_DIST) ? KNN_VOTE_W_INV_SQDIST
+                                                                                      : wv.weights;
     v.self_base = self_base;
     v.qlabels = qlabels; v.pred_all = pred_all; v.pred_stride = pred_stride; v.row0 = wv.row0;
     v.correct = reinterpret_cast<unsigned long long*>(correct);
@@ -1280,6 +1334,9 @@ knn_status weighted_check(knn_ctx* c, int32_t kmax, int32_t weights, int64_t sel
                           const void* pred_all, const void* correct, const void* scores) {
     if (weights != KNN_W_UNIFORM && weights != KNN_W_INV_DIST && weights != KNN_W_INV_SQDIST)
         return fail(c, KNN_EINVAL, "weighted vote: unknown weights=%d", weights);
+    if (weights == KNN_W_INV_SQDIST && c->metric != KNN_METRIC_SQEUCLIDEAN)
+        return fail(c, KNN_EINVAL, "weighted vote: KNN_W_INV_SQDIST needs the squared Euclidean metric (metric=%d)",
+                    c->metric);
     if (kmax < 1) return fail(c, KNN_EINVAL, "weighted vote: kmax=%d must be >= 1", kmax);
     if (!qlabels && !pred_all && !correct && !scores)
         return fail(c, KNN_EINVAL, "weighted vote: query labels, pred_all, correct and scores are all NULL");
@@ -1583,6 +1640,19 @@ knn_status knn_predict(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te,
     }
     return KNN_OK;
 }
+
+knn_status knn_set_metric(knn_ctx* c, int32_t metric) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    if (metric != KNN_METRIC_SQEUCLIDEAN && metric != KNN_METRIC_MANHATTAN && metric != KNN_METRIC_CHEBYSHEV)
+        return fail(c, KNN_EINVAL, "unknown metric=%d", metric);
+    if (metric != KNN_METRIC_SQEUCLIDEAN && c->algo != KNN_ALGO_AUTO && c->algo != KNN_ALGO_DIRECT)
+        return fail(c, KNN_EINVAL, "metric=%d needs KNN_ALGO_AUTO or KNN_ALGO_DIRECT (context algo=%d)", metric, c->algo);
+    c->metric = metric;
+    return KNN_OK;
+}
+
+int32_t knn_get_metric(const knn_ctx* c) { return c ? c->metric : KNN_METRIC_SQEUCLIDEAN; }
 
 knn_status knn_set_generation(knn_ctx* c, uint64_t generation) {
     if (!c) return KNN_EINVAL;

@@ -1,7 +1,7 @@
 // knn_cli.cpp -- command-line driver with the reference's contract.
 //
 //   knn_cli train.arff test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]]
-//           [--weights=uniform|distance|sqdist]
+//           [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev]
 //
 // Same positional arguments as ./main (main.cpp:114-122; k parsed with strtol) plus the
 // optional worker count of ./multi-thread (multi-thread.cpp:135-143), here the number of
@@ -16,17 +16,21 @@
 // --weights=distance|sqdist: the weighted vote (KNN_sweep_weighted / KNN_sweep_loo_weighted),
 // with --sweep a line per k, without it the one line for k (row k - 1 of the same call).
 // --weights=uniform is the default and changes nothing.
+// --metric=manhattan|chebyshev: the distance of the run (KNN_AMD_METRIC; knn_amd.h "Metrics");
+// composes with --sweep[=loo] and --weights=distance (1 / D there).  --weights=sqdist with such
+// a metric prints the library's error and exits 1.  --metric=euclidean is the default.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <exception>
 #include <iostream>
 #include <string>
 
 #include "../../include/knn_arff.hpp"
 
-int main(int argc, char* argv[]) {
+static int run(int argc, char* argv[]) {
     // --shard=... may sit anywhere; the rest are the reference's positional arguments
     int n = 0;
     bool sweep = false, loo = false;
@@ -42,11 +46,17 @@ int main(int argc, char* argv[]) {
             std::cerr << "unknown " << argv[i] << " (uniform, distance or sqdist)" << std::endl;
             std::exit(2);
         }
+        else if (!std::strcmp(argv[i], "--metric=euclidean") || !std::strcmp(argv[i], "--metric=manhattan") ||
+                 !std::strcmp(argv[i], "--metric=chebyshev")) setenv("KNN_AMD_METRIC", argv[i] + 9, 1);
+        else if (!std::strncmp(argv[i], "--metric=", 9)) {
+            std::cerr << "unknown " << argv[i] << " (euclidean, manhattan or chebyshev)" << std::endl;
+            std::exit(2);
+        }
         else argv[n++] = argv[i];
     }
     argc = n;
     if (argc != 4 && argc != 5) {
-        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist]"
+        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev]"
                   << std::endl;
         std::exit(0);
     }
@@ -105,4 +115,15 @@ int main(int argc, char* argv[]) {
     std::free(predictions);
     std::free(confusionMatrix);
     return 0;
+}
+
+// an error of the library (a bad file, an option it refuses, a device failure) is printed and
+// ends the run with status 1
+int main(int argc, char* argv[]) {
+    try {
+        return run(argc, argv);
+    } catch (const std::exception& e) {
+        std::cerr << "knn_cli: " << e.what() << std::endl;
+        return 1;
+    }
 }

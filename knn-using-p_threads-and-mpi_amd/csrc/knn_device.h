@@ -1,6 +1,6 @@
 // knn_device.h -- device helpers shared by the kernel translation units of libknn_amd
-// (knn_kernels.hip, knn_fused.hip, knn_fused16.hip, knn_vote_weighted.hip): keys and wave
-// bitonic networks, bf16 helpers, ordered-float bits, LDS-DMA issue and the GEMM filter tile
+// (knn_kernels.hip, knn_metric.hip, knn_fused.hip, knn_fused16.hip, knn_vote_weighted.hip): keys and
+// wave bitonic networks, the vote and outputs of a finished wave list, the lane-shift insert, bf16 helpers, ordered-float bits, LDS-DMA issue and the GEMM filter tile
 // geometry.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "knn_kernels.h"
+#include "knn_study.h"
 
 typedef unsigned long long u64;
 
@@ -298,3 +299,124 @@ struct FilterTile {
     static constexpr int TILE = DMA_INS * 1024;      // LDS bytes per buffer (>= BN * STRIDE + 16 HS)
     static constexpr int HDR = BN * STRIDE;          // LDS offset of the header
 };
+
+// ---------------------------------------------------------------------------------
+// The vote of main.cpp:64-78 without a C-sized table (any class count): the argmax of
+// the label counts over the list entries, ties to the smallest label.  lab[r] is the
+// label of list element 64r + lane (-1: none / outside the list).  k rounds of one
+// broadcast + R ballots.  Returns (count << 32) | (0xffffffff - label), 0 if empty.
+// ---------------------------------------------------------------------------------
+template <int R>
+__device__ __forceinline__ u64 vote_ballot(const int (&lab)[R], int k) {
+    u64 best = 0;
+    for (int e = 0; e < k; e++) {
+        int le = lab[0];
+#pragma unroll
+        for (int r = 1; r < R; r++)
+            if (r == (e >> 6)) le = lab[r];
+        le = __shfl(le, e & 63);
+        if (le < 0) continue;
+        int cnt = 0;
+#pragma unroll
+        for (int r = 0; r < R; r++) cnt += __popcll(__ballot(lab[r] == le));
+        best = umax64(best, ((u64)(uint32_t)cnt << 32) | (u64)(0xffffffffu - (uint32_t)le));
+    }
+    return best;
+}
+
+// ---------------------------------------------------------------------------------
+// Outputs for one query from a finished wave list: the neighbour list (dist, idx_base +
+// idx, label) and, when o.pred is set, the vote of main.cpp:64-78.
+// counts: wave-private LDS array of C ints, or NULL for the table-free vote_ballot
+// (class counts above KNN_VOTE_LDS_MAX_C).  Runs on one wave.
+// lab0 (optional): the label of element `lane` of T[0], already loaded by the caller.
+// ---------------------------------------------------------------------------------
+template <int R>
+__device__ void finish_query(const u64 (&T)[R], int k, int C, const int32_t* __restrict__ labels,
+                             int* counts, int64_t q, const QueryOut& o, int32_t* __restrict__ status,
+                             const int* lab0 = nullptr) {
+    const int lane = lane_id();
+    const bool vote = o.pred != nullptr;
+    const bool lds_vote = vote && counts != nullptr;
+    if (lds_vote) {
+        for (int c = lane; c < C; c += 64) counts[c] = 0;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    u64 kth = list_at(T, k - 1);
+    bool bad = (kth == KEY_NONE);
+    int labr[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        labr[r] = -1;
+        int e = 64 * r + lane;
+        if (e < k) {
+            const u64 key = T[r];
+            const int64_t off = q * o.stride + e;
+            if (key != KEY_NONE) {
+                int32_t idx = (int32_t)(uint32_t)(key & 0xffffffffull);
+                const int lab = (r == 0 && lab0) ? *lab0 : labels[idx];
+                if (o.dist) o.dist[off] = __uint_as_float((uint32_t)(key >> 32));
+                if (o.idx) o.idx[off] = (int32_t)(o.idx_base + idx);
+                if (o.label) o.label[off] = lab;
+                if (lab >= 0 && lab < C) {
+                    labr[r] = lab;
+                    if (lds_vote) atomicAdd(&counts[lab], 1);
+                } else {
+                    atomicOr(status, KNN_STATUS_BAD_LABEL);
+                }
+            } else {
+                if (o.dist) o.dist[off] = FLT_MAX;
+                if (o.idx) o.idx[off] = -1;
+                if (o.label) o.label[off] = -1;
+            }
+        }
+    }
+    if (!vote) return;
+    u64 best = 0;
+    if (lds_vote) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        // argmax, strict '>' scanning 0..C-1 == max count, smallest label on ties
+        for (int c = lane; c < C; c += 64) {
+            u64 v = ((u64)(uint32_t)counts[c] << 32) | (u64)(0xffffffffu - (uint32_t)c);
+            best = umax64(best, v);
+        }
+#pragma unroll
+        for (int j = 32; j > 0; j >>= 1) best = umax64(best, __shfl_xor(best, j));
+    } else {
+        best = vote_ballot<R>(labr, k);
+    }
+    if (lane == 0) {
+        o.pred[q] = bad ? 0 : (int32_t)(0xffffffffu - (uint32_t)(best & 0xffffffffull));
+        if (bad && !KNN_STUDY_RESULTS_INVALID) atomicOr(status, KNN_STATUS_TOO_FEW);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// ---------------------------------------------------------------------------------
+// The k <= 16 list of the direct-form tile kernels (k_direct_tile, k_direct_rows, k_metric_tile)
+// ---------------------------------------------------------------------------------
+// Insert key y into the ascending list held in lanes 0..15 of T (lanes >= k hold KEY_NONE and
+// are left alone: in_list = lane < k).  y's train index is above every listed one (rows are
+// visited in ascending order), so `T > y` on the 64-bit keys is main.cpp:47's strict `<` on the
+// distance.  Lane e takes lane e-1's key (row_shr:1; lane 0 of a row reads 0 <= y) when both
+// are above y, y itself when only its own is: the first key above y moves up one lane and the
+// k-th falls off.  Needs k <= 16 (one DPP row).
+__device__ __forceinline__ void shift_insert(u64& T, u64 y, bool in_list) {
+    const uint32_t phi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(T >> 32), 0x111, 0xF, 0xF, true);
+    const uint32_t plo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)T, 0x111, 0xF, 0xF, true);
+    const u64 prev = ((u64)phi << 32) | (u64)plo;
+    const bool gt = in_list && T > y;
+    T = gt ? (prev > y ? prev : y) : T;
+}
+// distance of list element k-1 (wave-uniform): the insertion threshold, FLT_MAX while the list
+// has fewer than k keys (main.cpp:33's sentinel)
+__device__ __forceinline__ float kth_dist(u64 T, int k) {
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(T >> 32), k - 1);
+    return hi == 0xffffffffu ? FLT_MAX : __uint_as_float(hi);
+}
+#ifndef DT_SHIFT_MAX
+#define DT_SHIFT_MAX 8  // passing rows per tile and query up to which the lane shift beats the sort
+#endif

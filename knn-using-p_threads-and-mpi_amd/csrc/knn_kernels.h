@@ -160,9 +160,13 @@ struct DirectTileArgs {
     // in the same launch (no k_merge_vote pass)
     int32_t* arrive;
 };
+// k <= 64R selects the wave-list register count R
+inline int knn_list_regs(int k) { return k <= 64 ? 1 : k <= 128 ? 2 : k <= 256 ? 4 : k <= 512 ? 8 : 16; }
 // queries per k_direct_tile block for k (8 * QW, QW = max(1, 8 / list registers))
 int knn_direct_tile_qb(int k);
-// launch geometry: LDS bytes per block and blocks per CU at that LDS
+// launch geometry: dims per staged chunk and the padded LDS row stride (floats), LDS bytes per
+// block and blocks per CU at that LDS
+void knn_direct_tile_geom(int d, int* dc, int* stride);
 size_t knn_direct_tile_lds(int d, int C);
 hipError_t knn_direct_tile_occupancy(int k, int elem, int d, int C, int* blocks_per_cu);
 // work units of the direct form for (k, d): queries per unit and units resident per CU --
@@ -174,6 +178,16 @@ hipError_t knn_launch_direct_tile(DirectTileArgs a, hipStream_t st);
 // whether (k, d) runs k_direct_rows (d <= 16, k <= 16), and its query groups for nq queries
 bool knn_direct_rows_shape(int k, int d);
 int64_t knn_direct_rows_groups(int64_t nq);
+
+// distance metrics (knn_metric of knn_amd.h).  METRIC_SQEUCLIDEAN is every kernel above;
+// the other two run k_metric_tile (knn_metric.hip): k_direct_tile's contract, block shape,
+// LDS layout and segment records (DirectTileArgs, knn_direct_tile_qb / _geom / _lds) with the
+// per-feature step sum = sum + |q_i - t_i| (Manhattan) or m = fmaxf(m, |q_i - t_i|) (Chebyshev).
+// There is no rows form: every (k, d) runs the tile kernel, a block of 8 waves per unit.
+enum { METRIC_SQEUCLIDEAN = 0, METRIC_MANHATTAN = 1, METRIC_CHEBYSHEV = 2 };
+hipError_t knn_metric_units(int metric, int k, int elem, int d, int C, int* queries_per_unit, int* units_per_cu);
+// fills dc / stride / vote_lds / n_qblocks and launches n_qblocks * nseg blocks
+hipError_t knn_launch_metric_tile(DirectTileArgs a, int metric, hipStream_t st);
 
 struct GenerateArgs {
     void* out; int32_t* labels; int64_t row0; int64_t n; int d; int ld;

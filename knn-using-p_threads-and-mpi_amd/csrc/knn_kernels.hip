@@ -26,6 +26,7 @@
 //   k_vote_sweep   the vote for every prefix k <= K of a neighbour list (k-sweep, leave-one-out)
 //                  (its distance-weighted sibling k_vote_weighted: knn_vote_weighted.hip)
 //   k_generate     counter-based synthetic rows (same formula as oracle/knn_oracle.c)
+// (k_metric_tile, the direct form under the Manhattan and Chebyshev metrics: knn_metric.hip)
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <stdint.h>
@@ -138,100 +139,7 @@ __device__ __forceinline__ float direct_dist_grouped(const float* q, const E* __
 }
 #pragma clang fp contract(on)
 
-// ---------------------------------------------------------------------------------
-// The vote of main.cpp:64-78 without a C-sized table (any class count): the argmax of
-// the label counts over the list entries, ties to the smallest label.  lab[r] is the
-// label of list element 64r + lane (-1: none / outside the list).  k rounds of one
-// broadcast + R ballots.  Returns (count << 32) | (0xffffffff - label), 0 if empty.
-// ---------------------------------------------------------------------------------
-template <int R>
-__device__ __forceinline__ u64 vote_ballot(const int (&lab)[R], int k) {
-    u64 best = 0;
-    for (int e = 0; e < k; e++) {
-        int le = lab[0];
-#pragma unroll
-        for (int r = 1; r < R; r++)
-            if (r == (e >> 6)) le = lab[r];
-        le = __shfl(le, e & 63);
-        if (le < 0) continue;
-        int cnt = 0;
-#pragma unroll
-        for (int r = 0; r < R; r++) cnt += __popcll(__ballot(lab[r] == le));
-        best = umax64(best, ((u64)(uint32_t)cnt << 32) | (u64)(0xffffffffu - (uint32_t)le));
-    }
-    return best;
-}
-
-// ---------------------------------------------------------------------------------
-// Outputs for one query from a finished wave list: the neighbour list (dist, idx_base +
-// idx, label) and, when o.pred is set, the vote of main.cpp:64-78.
-// counts: wave-private LDS array of C ints, or NULL for the table-free vote_ballot
-// (class counts above KNN_VOTE_LDS_MAX_C).  Runs on one wave.
-// lab0 (optional): the label of element `lane` of T[0], already loaded by the caller.
-// ---------------------------------------------------------------------------------
-template <int R>
-__device__ void finish_query(const u64 (&T)[R], int k, int C, const int32_t* __restrict__ labels,
-                             int* counts, int64_t q, const QueryOut& o, int32_t* __restrict__ status,
-                             const int* lab0 = nullptr) {
-    const int lane = lane_id();
-    const bool vote = o.pred != nullptr;
-    const bool lds_vote = vote && counts != nullptr;
-    if (lds_vote) {
-        for (int c = lane; c < C; c += 64) counts[c] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    u64 kth = list_at(T, k - 1);
-    bool bad = (kth == KEY_NONE);
-    int labr[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        labr[r] = -1;
-        int e = 64 * r + lane;
-        if (e < k) {
-            const u64 key = T[r];
-            const int64_t off = q * o.stride + e;
-            if (key != KEY_NONE) {
-                int32_t idx = (int32_t)(uint32_t)(key & 0xffffffffull);
-                const int lab = (r == 0 && lab0) ? *lab0 : labels[idx];
-                if (o.dist) o.dist[off] = __uint_as_float((uint32_t)(key >> 32));
-                if (o.idx) o.idx[off] = (int32_t)(o.idx_base + idx);
-                if (o.label) o.label[off] = lab;
-                if (lab >= 0 && lab < C) {
-                    labr[r] = lab;
-                    if (lds_vote) atomicAdd(&counts[lab], 1);
-                } else {
-                    atomicOr(status, KNN_STATUS_BAD_LABEL);
-                }
-            } else {
-                if (o.dist) o.dist[off] = FLT_MAX;
-                if (o.idx) o.idx[off] = -1;
-                if (o.label) o.label[off] = -1;
-            }
-        }
-    }
-    if (!vote) return;
-    u64 best = 0;
-    if (lds_vote) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        // argmax, strict '>' scanning 0..C-1 == max count, smallest label on ties
-        for (int c = lane; c < C; c += 64) {
-            u64 v = ((u64)(uint32_t)counts[c] << 32) | (u64)(0xffffffffu - (uint32_t)c);
-            best = umax64(best, v);
-        }
-#pragma unroll
-        for (int j = 32; j > 0; j >>= 1) best = umax64(best, __shfl_xor(best, j));
-    } else {
-        best = vote_ballot<R>(labr, k);
-    }
-    if (lane == 0) {
-        o.pred[q] = bad ? 0 : (int32_t)(0xffffffffu - (uint32_t)(best & 0xffffffffull));
-        if (bad && !KNN_STUDY_RESULTS_INVALID) atomicOr(status, KNN_STATUS_TOO_FEW);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
+// (vote_ballot and finish_query, shared with knn_metric.hip: knn_device.h)
 
 // ---------------------------------------------------------------------------------
 // k_exact_scan: one 256-thread block per query (grid-stride over the query list).
@@ -323,28 +231,7 @@ __global__ __launch_bounds__(256) void k_exact_scan(ExactScanArgs a) {
 //    (dist bits, local row, label) [nseg][nq][3][k], merged by k_merge_vote.
 // LDS: 2 tile buffers [64][stride] f32 | per-wave class counts [8][Cpad] (vote_lds)
 // ---------------------------------------------------------------------------------
-// Insert key y into the ascending list held in lanes 0..15 of T (lanes >= k hold KEY_NONE and
-// are left alone: in_list = lane < k).  y's train index is above every listed one (rows are
-// visited in ascending order), so `T > y` on the 64-bit keys is main.cpp:47's strict `<` on the
-// distance.  Lane e takes lane e-1's key (row_shr:1; lane 0 of a row reads 0 <= y) when both
-// are above y, y itself when only its own is: the first key above y moves up one lane and the
-// k-th falls off.  Needs k <= 16 (one DPP row).
-__device__ __forceinline__ void shift_insert(u64& T, u64 y, bool in_list) {
-    const uint32_t phi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(T >> 32), 0x111, 0xF, 0xF, true);
-    const uint32_t plo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)T, 0x111, 0xF, 0xF, true);
-    const u64 prev = ((u64)phi << 32) | (u64)plo;
-    const bool gt = in_list && T > y;
-    T = gt ? (prev > y ? prev : y) : T;
-}
-// distance of list element k-1 (wave-uniform): the insertion threshold, FLT_MAX while the list
-// has fewer than k keys (main.cpp:33's sentinel)
-__device__ __forceinline__ float kth_dist(u64 T, int k) {
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(T >> 32), k - 1);
-    return hi == 0xffffffffu ? FLT_MAX : __uint_as_float(hi);
-}
-#ifndef DT_SHIFT_MAX
-#define DT_SHIFT_MAX 8  // passing rows per tile and query up to which the lane shift beats the sort
-#endif
+// (shift_insert, kth_dist and DT_SHIFT_MAX, shared with knn_metric.hip: knn_device.h)
 #pragma clang fp contract(off)
 template <int QW, int R, typename E, bool SH>
 __global__ __launch_bounds__(64 * DT_NW, 4) void k_direct_tile(DirectTileArgs a) {
@@ -2298,7 +2185,7 @@ hipError_t knn_launch_rerun_decide(int32_t* ctrl, int64_t limit, hipStream_t st)
 static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // k <= 64R selects the wave-list register count R
-static int list_regs(int k) { return k <= 64 ? 1 : k <= 128 ? 2 : k <= 256 ? 4 : k <= 512 ? 8 : 16; }
+static int list_regs(int k) { return knn_list_regs(k); }
 
 template <int R, typename E>
 static hipError_t launch_exact_r(const ExactScanArgs& a0, int grid, hipStream_t st) {
@@ -2337,7 +2224,7 @@ static int direct_qw(int k) { return std::max(1, 8 / list_regs(k)); }
 int knn_direct_tile_qb(int k) { return DT_NW * direct_qw(k); }
 
 // dims per staged chunk and the padded LDS row stride (an odd number of 16-B slots)
-static void direct_tile_geom(int d, int* dc, int* stride) {
+void knn_direct_tile_geom(int d, int* dc, int* stride) {
     const int dpad = (d + 3) & ~3;
     *dc = std::min(dpad, DT_MAX_DC);
     int slots = *dc / 4;
@@ -2347,7 +2234,7 @@ static void direct_tile_geom(int d, int* dc, int* stride) {
 
 size_t knn_direct_tile_lds(int d, int C) {
     int dc, stride;
-    direct_tile_geom(d, &dc, &stride);
+    knn_direct_tile_geom(d, &dc, &stride);
     return 2 * 64 * (size_t)stride * 4 + (C <= KNN_VOTE_LDS_MAX_C ? (size_t)DT_NW * ((C + 3) & ~3) * 4 : 0);
 }
 
@@ -2427,7 +2314,7 @@ hipError_t knn_launch_direct_tile(DirectTileArgs a, hipStream_t st) {
         KNN_LAUNCH_CHECK();
         return hipSuccess;
     }
-    direct_tile_geom(a.d, &a.dc, &a.stride);
+    knn_direct_tile_geom(a.d, &a.dc, &a.stride);
     a.vote_lds = a.C <= KNN_VOTE_LDS_MAX_C;
     const int qb = knn_direct_tile_qb(a.k);
     a.n_qblocks = (int)((a.nq + qb - 1) / qb);
