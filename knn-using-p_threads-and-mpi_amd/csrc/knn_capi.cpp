@@ -71,7 +71,8 @@ struct knn_ctx {
     DBuf seg_rec;           // k_direct_tile segment records [nseg][nq][3][k]
     DBuf tmax;              // fused filter: per-64-row train stats {max tn, max |t - rt|, max |rt|, 0}
     DBuf tsmax;             // fused filter: their maxima over all tiles (k_tile_stat_max; cached with tmax)
-    DBuf cursor;            // fused filter: per-XCD scan cursors (64-row units; performance hint only)
+    DBuf cursor;            // fused filter: per-XCD scan cursors (64-row units; performance hint only) on the
+                            // segment schedule, or the per-XCD pacing words (int32 pairs) on the balanced one
     DBuf lshare;            // fused filter: per (query, piece) threshold lists shared between pieces
     DBuf qstat;             // fused filter: per-query {|q|, |q - rq|} upper bounds
     DBuf tblk;              // fused filter: train tile blocks [bn rows rn(t) | bn norms | tile stats]
@@ -93,7 +94,7 @@ struct knn_ctx {
     // KNN_OPT_CACHE_TRAIN_DEVICE (the caller's device buffer may change behind the library)
     int cache_train_device = 0;
     // study switches of run_gemm, read once at knn_create
-    bool no_lshare = false, no_cursor = false, rescore_all = false;
+    bool no_lshare = false, no_cursor = false, rescore_all = false, no_pace = false;
     // host-API staging (device copies of host inputs / outputs)
     DBuf h_train, h_labels, h_test, h_pred, h_dist, h_idx;
     int32_t* ctrl_host = nullptr;  // pinned, mapped, fine-grained: [0] status, [1] fallback count,
@@ -771,6 +772,20 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
         HIP_OR_FAIL(c, hipMemsetAsync(c->cursor.p, 0, sizeof(uint32_t) * 8, st));
         g.cursor = c->cursor.as<uint32_t>();
     }
+    // pacing of each XCD's blocks (fused_pace, knn_fused.hip: A 19.23 -> 18.70 ms, fetch beyond L2
+    // 22.0 -> 4.7 GB) when the balanced schedule is one round of blocks that start and
+    // end together: there a leader's wait costs nothing.  With whole rounds of query tiles before
+    // it a held block keeps its CU from the next round's (A's rows, 200,000 queries: 37.9 -> 41.4
+    // ms), so those grids are not paced.  KNN_NO_FUSED_PACE=1 turns it off (a diagnostic; same
+    // results).  The 64-query register-list shapes at d = 128 only (what was measured: A and
+    // its 2- and 4-GPU shares; B's and C's grids take segments or several rounds; the 32-query
+    // instantiations compile no pacing code).  The two uses of c->cursor exclude each other
+    // (segments: g2 < 0).
+    if (fused && !c->no_pace && g.g2 > 0 && g.p1_blocks == 0 && plan.qg == 2 && plan.kr > 0 && d == 128 && !plan.m16) {
+        HIP_OR_FAIL(c, c->cursor.ensure(sizeof(int32_t) * 16));
+        HIP_OR_FAIL(c, hipMemsetAsync(c->cursor.p, 0, sizeof(int32_t) * 16, st));
+        g.pace = c->cursor.as<int32_t>();
+    }
     // the pieces of a query share their threshold lists, not just their k-th values: the
     // union's k-th smallest U is the bound a single scan would have.  The 32-queries-per-wave
     // shape only -- the small query counts, whose query tiles are cut into many pieces (A's
@@ -861,6 +876,7 @@ knn_status knn_create(knn_ctx** out, const knn_opts* opts) {
     c->fforce.m16 = getenv("KNN_FUSED_MFMA16") != nullptr && std::atoi(getenv("KNN_FUSED_MFMA16")) == 1;
     c->no_lshare = getenv("KNN_NO_LIST_SHARE") != nullptr;
     c->no_cursor = getenv("KNN_NO_SCAN_CURSOR") != nullptr;
+    c->no_pace = getenv("KNN_NO_FUSED_PACE") != nullptr;
     c->rescore_all = getenv("KNN_RESCORE_ALL") != nullptr;
     c->merge_kernel = getenv("KNN_DIRECT_MERGE_KERNEL") != nullptr;
     if (c->device < 0 || c->device >= ndev) { delete c; return KNN_ENODEV; }

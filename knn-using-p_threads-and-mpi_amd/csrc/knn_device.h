@@ -300,6 +300,40 @@ struct FilterTile {
     static constexpr int HDR = BN * STRIDE;          // LDS offset of the header
 };
 
+// LDS byte offset, inside a tile's image of rows of `stride` bytes, of the 16 bytes lane (j, h)
+// reads of row `row` at k-step s (the A fragment of k_gemm_fused: ds_read_b128)
+__host__ __device__ constexpr int fused_frag_off(int row, int h, int s, int stride) {
+    return row * stride + 16 * h + 32 * s;
+}
+// LDS byte offset of the header's norm read of lane half h, row group rg, register group g4
+__host__ __device__ constexpr int fused_norm_off(int hdr, int h, int rg, int g4) {
+    return hdr + 4 * (4 * h) + 4 * (32 * rg + 8 * g4);
+}
+// Tiles a fused-filter piece of `rows` rows scans: whole barrier groups (at least pairs) of bn-row
+// tiles, the extra ones past the piece's end (rejected by index)
+__host__ __device__ constexpr int fused_piece_tiles(int64_t rows, int bn, int grp) {
+    const int ts = grp > 2 ? grp : 2;
+    return rows > 0 ? ((int)((rows + bn - 1) / bn) + ts - 1) / ts * ts : 0;
+}
+// The schedule's rotation of a piece (64-row units, knn_fused_range_piece) in tiles: whole
+// barrier groups, so a tile keeps its place in its group; inside the piece
+__host__ __device__ constexpr int fused_rot_tiles(int64_t rot_units, int bn, int grp, int ntiles) {
+    const int r0 = (int)(rot_units * (64 / bn)) / grp * grp;
+    return r0 < ntiles ? r0 : 0;
+}
+// The 1 KiB DMA pieces of a fused-filter tile (k_gemm_fused): the i-th piece wave w of nw issues
+// (when it is below the tile's piece count)
+__host__ __device__ constexpr int fused_dma_piece(int nw, int w, int i) { return w + nw * i; }
+// byte offset in a tile's source (rows of pitch ldb, then the header) of the 16 bytes that land
+// in slot P of the padded LDS image (slot P -> row P / slots, slot P % slots; the pad slot
+// re-copies slot 0; slots past the header re-read its last slot)
+__host__ __device__ constexpr uint32_t fused_dma_src_off(int P, int bn, int rb, int hs, int64_t ldb) {
+    const int slots = rb / 16 + 1;
+    if (hs > 0 && P >= bn * slots) return (uint32_t)(bn * rb + 16 * (P - bn * slots < hs - 1 ? P - bn * slots : hs - 1));
+    const int row = P / slots < bn - 1 ? P / slots : bn - 1, sl = P % slots;
+    return (uint32_t)(row * ldb + 16 * (sl == slots - 1 ? 0 : sl));
+}
+
 // ---------------------------------------------------------------------------------
 // The vote of main.cpp:64-78 without a C-sized table (any class count): the argmax of
 // the label counts over the list entries, ties to the smallest label.  lab[r] is the

@@ -264,9 +264,29 @@ extern "C" int knn_debug_stamps(unsigned long long* out, int reset) {
 }
 #endif
 
+// Pacing of the blocks of one XCD (a.pace; the balanced schedule): every FUSED_SHARE_EVERY tiles
+// a block adds a step to its XCD's sum, and while it is more than FUSED_PACE_LEAD steps ahead of
+// the average of the XCD's running blocks it sleeps -- at most FUSED_PACE_POLLS times, then
+// goes on regardless.  Only blocks that are running are counted (each registers itself at its
+// start, at the XCD's average then, and takes its steps out at its end), so nothing is assumed
+// about which blocks are resident; the kernel's time is its slowest block's, which is never held.  Thread 0 only: the
+// other waves wait for it at the next group barrier.
+static constexpr int FUSED_PACE_LEAD = 1;
+static constexpr int FUSED_PACE_POLLS = 32;
+__device__ __forceinline__ void fused_pace(int32_t* p, int steps) {
+    __hip_atomic_fetch_add(p, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int poll = 0; poll < FUSED_PACE_POLLS; poll++) {
+        const int sum = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int n = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (n <= 0 || (steps - FUSED_PACE_LEAD) * n <= sum) break;
+        __builtin_amdgcn_s_sleep(127);
+    }
+}
+
 template <int RB, int NBUF, int NW, int QG, int RG, int KR>
 __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int qt, const int seg,
-                                            const int64_t row_begin, const int64_t row_end) {
+                                            const int64_t row_begin, const int64_t row_end,
+                                            const int64_t rot_units, int& steps) {
     // TN (RB = 2d, the product): train tiles carry their rows' norms in a header, and each
     // accumulator starts from them (the MFMA's C operand) -- no augmented k-step.  Otherwise
     // (RB = 2d + 32, the KNN_STUDY_AUG64 build at d = 64) the norm rides in 16 augmented columns
@@ -278,7 +298,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // shapes only): accumulator c holds row group c % RG against query group c / RG, so each A
     // fragment read from LDS feeds QG MFMAs and each tile copy serves 32 QG NW queries
     typedef FilterTile<RB, NW, QG, RG, HS> FT;
-    constexpr int NACC = FT::NACC, BN = FT::BN, BM = FT::BM, STRIDE = FT::STRIDE, SLOTS = FT::SLOTS;
+    constexpr int NACC = FT::NACC, BN = FT::BN, BM = FT::BM, STRIDE = FT::STRIDE;
     constexpr int DMA_INS = FT::DMA_INS, TILE = FT::TILE, HDR = FT::HDR;
     // bytes of one tile in the train operand (TN: a block of rows + header; else rows of pitch RB)
     constexpr int64_t TB = (int64_t)BN * RB + 16 * HS;
@@ -423,7 +443,8 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // place in its group is a compile-time constant; up to 7 extra 32-row tiles, within the 256
     // pad rows past the train grid, run_gemm)
     constexpr int TSTEP = GRP > 2 ? GRP : 2;
-    const int ntiles = (row_end > row_begin) ? ((int)((row_end - row_begin + BN - 1) / BN) + TSTEP - 1) / TSTEP * TSTEP : 0;
+    const int ntiles = fused_piece_tiles(row_end - row_begin, BN, GRP);
+    static_assert(TSTEP == (GRP > 2 ? GRP : 2), "fused_piece_tiles");
     // Scan order (a.cursor set: the host does so for the multi-segment schedule): the piece's
     // tiles rotated to start where this XCD's other blocks are (per XCD: the 64-row unit the last
     // block to publish was at, if inside this piece) -- so the blocks one XCD runs at once
@@ -436,7 +457,9 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     const int xcd = blockIdx.x & 7;
     int* blk_rot = reinterpret_cast<int*>(smem + NBUF * TILE + (RL ? 0 : BM * hs * (int)sizeof(float)));
     if (threadIdx.x == 0) {
-        int r0 = 0;
+        // (the schedule's rotation, knn_fused_range_piece: whole barrier groups, so a tile keeps
+        // its place in its group)
+        int r0 = fused_rot_tiles(rot_units, BN, GRP, ntiles);
         if (a.cursor && ntiles > 0) {
             const int64_t cu =
                 (int64_t)__hip_atomic_load(&a.cursor[xcd], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * 64;
@@ -457,18 +480,14 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // rows) and rejected by index).  Every tile is whole: the train tile blocks are padded to
     // the 64-row grid (run_gemm), so a piece is always the scalar tile base + this lane's fixed
     // offset -- no per-tile address arithmetic in VGPRs.
-    // (piece ins = wave + NW i; rotating the DMA_INS % NW remainder pieces between even and odd
-    // tiles, so no wave issues two more per pair than another, measured no faster: r03r)
+    // (piece ins = wave + NW i: fused_dma_piece.  Rotating the DMA_INS % NW remainder pieces
+    // between the waves measured no faster -- between the two waves of a pair on the round-3
+    // kernel, r03r; with the tile's index over all eight waves on this one)
+    constexpr int DMA_FULL = DMA_INS / NW;
     uint32_t doff[DMA_PER_WAVE];
 #pragma unroll
     for (int i = 0; i < DMA_PER_WAVE; i++) {
-        const int P = (wave + NW * i) * 64 + lane;
-        if (TN && P >= BN * SLOTS) {  // header slot: norms, then the statistics
-            doff[i] = (uint32_t)(BN * RB + 16 * min(P - BN * SLOTS, HS - 1));
-        } else {
-            const int row = min(P / SLOTS, BN - 1), sl = P % SLOTS;
-            doff[i] = (uint32_t)(row * ldb + 16 * (sl == SLOTS - 1 ? 0 : sl));
-        }
+        doff[i] = fused_dma_src_off(fused_dma_piece(NW, wave, i) * 64 + lane, BN, RB, HS, ldb);
     }
     const uint32_t lds_tiles = __builtin_amdgcn_readfirstlane(lds_addr(tiles));
     struct DmaTile { const unsigned char* src; uint32_t lds; };
@@ -484,8 +503,8 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // The last piece of a tile is issued whole: its lanes past the header re-read the header's
     // last slot into the buffer's slack (TILE = DMA_INS KiB), so no piece needs an exec mask.
     auto dma_piece = [&](int i, const DmaTile& d) __attribute__((always_inline)) {
-        const int ins = wave + NW * i;
-        if (NW * (i + 1) <= DMA_INS || ins < DMA_INS) dma16s(doff[i], d.src, d.lds + (uint32_t)ins * 1024u);
+        const int ins = fused_dma_piece(NW, wave, i);
+        if (i < DMA_FULL || ins < DMA_INS) dma16s(doff[i], d.src, d.lds + (uint32_t)ins * 1024u);
     };
     // piece i goes out in k-step (i NS) / DMA_PER_WAVE of the step
     auto dma_at = [&](int s, bool on, const DmaTile& d) __attribute__((always_inline)) {
@@ -506,31 +525,30 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     uint4 pa[PF], pb[PF];                // PAIR: the odd step's first fragments, read early
     auto prefetch = [&](int buf) __attribute__((always_inline)) {
         const unsigned char* tile = tiles + buf * TILE;
-        const unsigned char* a0p = tile + j * STRIDE + 16 * h;
-        const unsigned char* a1p = tile + ((RG == 2 ? 32 : 0) + j) * STRIDE + 16 * h;
+        const unsigned char* a0p = tile + fused_frag_off(j, h, 0, STRIDE);
+        const unsigned char* a1p = tile + fused_frag_off((RG == 2 ? 32 : 0) + j, h, 0, STRIDE);
 #pragma unroll
         for (int s = 0; s < PF && s < NS; s++) {
-            pa[s] = *reinterpret_cast<const uint4*>(a0p + 32 * s);
-            if (RG == 2) pb[s] = *reinterpret_cast<const uint4*>(a1p + 32 * s);
+            pa[s] = *reinterpret_cast<const uint4*>(a0p + fused_frag_off(0, 0, s, STRIDE));
+            if (RG == 2) pb[s] = *reinterpret_cast<const uint4*>(a1p + fused_frag_off(0, 0, s, STRIDE));
         }
     };
     auto step = [&](floatx16 (&X)[NACC], floatx16 (&Y)[NACC], int buf, bool dma_on, const DmaTile& dd,
                     const float (&tf)[QG], bool pre, float (&mn_out)[NACC]) -> uint32_t {
         const unsigned char* tile = tiles + buf * TILE;
-        const unsigned char* a0p = tile + j * STRIDE + 16 * h;
-        const unsigned char* a1p = tile + ((RG == 2 ? 32 : 0) + j) * STRIDE + 16 * h;
+        const unsigned char* a0p = tile + fused_frag_off(j, h, 0, STRIDE);
+        const unsigned char* a1p = tile + fused_frag_off((RG == 2 ? 32 : 0) + j, h, 0, STRIDE);
         // each accumulator's chain starts from its rows' norms: register r of row group rg is row
         // 32 rg + (r & 3) + 8 (r >> 2) + 4h (four broadcast ds_read_b128 per row group; the QG
         // accumulators of a row group share them as the first MFMA's C operand)
         // (the norms land in row group rg's query-group-0 accumulator X[rg]; at k-step 0 the other
         // query groups' MFMAs take them as their C operand first, then X[rg]'s own -- no copy)
         if constexpr (TN && !KNN_STUDY_NO_NORM) {
-            const unsigned char* hn = tile + HDR + 4 * (4 * h);
 #pragma unroll
             for (int rg = 0; rg < RG; rg++) {
 #pragma unroll
                 for (int g4 = 0; g4 < 4; g4++) {
-                    const float4 v = *reinterpret_cast<const float4*>(hn + 4 * (32 * rg + 8 * g4));
+                    const float4 v = *reinterpret_cast<const float4*>(tile + fused_norm_off(HDR, h, rg, g4));
                     X[rg][4 * g4] = v.x;
                     X[rg][4 * g4 + 1] = v.y;
                     X[rg][4 * g4 + 2] = v.z;
@@ -556,16 +574,16 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
                 xa[s] = pa[s];
                 if (RG == 2) xb[s] = pb[s];
             } else {
-                xa[s] = *reinterpret_cast<const uint4*>(a0p + 32 * s);
-                if (RG == 2) xb[s] = *reinterpret_cast<const uint4*>(a1p + 32 * s);
+                xa[s] = *reinterpret_cast<const uint4*>(a0p + fused_frag_off(0, 0, s, STRIDE));
+                if (RG == 2) xb[s] = *reinterpret_cast<const uint4*>(a1p + fused_frag_off(0, 0, s, STRIDE));
             }
         }
 #pragma unroll
         for (int s = 0; s < NS; s++) {
             dma_at(s, dma_on, dd);
             if (s + PF < NS) {
-                xa[s + PF] = *reinterpret_cast<const uint4*>(a0p + 32 * (s + PF));
-                if (RG == 2) xb[s + PF] = *reinterpret_cast<const uint4*>(a1p + 32 * (s + PF));
+                xa[s + PF] = *reinterpret_cast<const uint4*>(a0p + fused_frag_off(0, 0, s + PF, STRIDE));
+                if (RG == 2) xb[s + PF] = *reinterpret_cast<const uint4*>(a1p + fused_frag_off(0, 0, s + PF, STRIDE));
             }
 #pragma unroll
             for (int cc = 0; cc < NACC; cc++) {
@@ -1164,6 +1182,10 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
             if (a.lshare && list_share_now(it)) exchange_lists();
         }
         if (share_now(it)) {
+            if (QG == 2 && a.pace) {  // (the host paces the 64-query shapes only)
+                steps++;
+                if (threadIdx.x == 0) fused_pace(a.pace + 2 * xcd, steps);
+            }
             if (a.cursor && threadIdx.x == 0)
                 __hip_atomic_store(&a.cursor[xcd], (uint32_t)(tile_row(it) >> 6), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
@@ -1344,6 +1366,34 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
 #endif
 }
 
+// One piece of a block's range [x, x1) of the balanced schedule's (query tile, 64-row unit)
+// space, T units per query tile: units [t0, t1) of query tile ql, scanned from unit t0 + rot.
+// A range runs from its END: the head of its later query tile first (from train row 0), then
+// the tail of the earlier one.  At time tau every two-piece block is then at unit tau, and after
+// its switch at tau + g, g = T - (x1 - x) the same for every block: two sweeps that stream the
+// train rows together through the L2s and the Infinity Cache (in range order each block would
+// start from its own row, all 260 MB of A's train operand in use at once, cycling through a
+// 256 MiB cache; KNN_FUSED_FORWARD=1: range order, a study build).  A range inside ONE query
+// tile (about 23 % of A's blocks) has t0 <= g: started at t0 it would be a private stream
+// somewhere between the two sweeps, so it starts at unit g instead, beside the second sweep,
+// and wraps to its first g - t0 units at the end (rot; the scan order is free, fused_piece).
+struct FusedRangePiece { int64_t ql, t0, t1, rot; };
+__host__ __device__ inline FusedRangePiece knn_fused_range_piece(int64_t x, int64_t x1, int64_t T, bool first) {
+    FusedRangePiece p;
+#if KNN_FUSED_FORWARD
+    p.ql = x / T;
+    p.t0 = x - p.ql * T;
+    p.t1 = p.t0 + (x1 - x) < T ? p.t0 + (x1 - x) : T;
+#else
+    p.ql = (x1 - 1) / T;
+    p.t0 = (x > p.ql * T ? x : p.ql * T) - p.ql * T;
+    p.t1 = x1 - p.ql * T;
+#endif
+    const int64_t g = T - (x1 - x);
+    p.rot = first && x / T == (x1 - 1) / T && g > p.t0 && g < p.t1 ? g - p.t0 : 0;
+    return p;
+}
+
 // The grid (knn_fused_schedule): blocks [0, p1) take one whole query tile each (qt = block,
 // every train row) -- whole rounds of the resident blocks, all sweeping the train rows from
 // row 0 together (one L2 stream per XCD); the remaining query tiles' (qtile, 64-row tile)
@@ -1368,15 +1418,25 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_gemm_fused(GemmFilterArgs a) 
         x1 = p1 ? x + T : lo(b2 + 1);
     }
     const int qbase = p1 ? 0 : a.p1_blocks;
-    // A range runs from its END: the head of its later query tile first (from train row 0),
-    // then the tail of the earlier one.  At time tau every block of the balanced schedule is
-    // then near train tile tau (or tau + T - W after its switch), so the blocks stream the
-    // train rows together through the L2s and the Infinity Cache; in range order each would
-    // start from its own row, all 260 MB of A's train operand in use at once, cycling through
-    // a 256 MiB cache.  (KNN_FUSED_FORWARD=1: range order, a study build.)
+    // (a.pace) pacing steps of this block, over its pieces (thread 0's copy is the one used).  A
+    // block joins at its XCD's current average: one that starts when others are far into
+    // their ranges (a later round of blocks) must not hold them back.
+    int steps = 0;
+    // (b & 7: the XCD under round-robin dispatch over eight of them, as the scan cursor assumes;
+    // the two words are read one after the other, not as a pair.  A wrong guess or a torn read
+    // only costs the gain: the waits stay bounded and no result depends on them.)
+    if (QG == 2 && a.pace && threadIdx.x == 0) {
+        int32_t* p = a.pace + 2 * (b & 7);
+        const int sum = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int n = __hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        steps = n > 0 && sum > 0 ? sum / n : 0;
+        __hip_atomic_fetch_add(p, steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(p + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // (the pieces of a range and their order: knn_fused_range_piece)
     for (bool first = true; x < x1; first = false) {
         int qt, seg;
-        int64_t rb, re, adv;
+        int64_t rb, re, adv, rot = 0;
         if (segmode) {
             qt = b % a.n_qtiles;
             seg = b / a.n_qtiles;
@@ -1384,13 +1444,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_gemm_fused(GemmFilterArgs a) 
             re = min(a.nt, rb + a.seg_len);
             adv = 1;
         } else {
-#if KNN_FUSED_FORWARD
-            const int64_t ql = x / T, t0 = x - ql * T;
-            const int64_t t1 = min(T, t0 + (x1 - x));
-#else
-            const int64_t ql = (x1 - 1) / T;
-            const int64_t t0 = max(x, ql * T) - ql * T, t1 = x1 - ql * T;
-#endif
+            const FusedRangePiece p = knn_fused_range_piece(x, x1, T, first);
+            const int64_t ql = p.ql, t0 = p.t0, t1 = p.t1;
+            rot = p.rot;
             qt = qbase + (int)ql;
             // the block whose range holds the query tile's first unit: largest bb with lo(bb) <= ql T
             seg = p1 ? 0 : (int)(b2 - ((ql * T + 1) * a.g2 - 1) / a.w2);
@@ -1399,9 +1455,13 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_gemm_fused(GemmFilterArgs a) 
             adv = t1 - t0;
         }
         if (!first) __syncthreads();  // every wave is done with the previous piece's LDS
-        fused_piece<RB, NBUF, NW, QG, RG, KR>(a, qt, seg, rb, re);
+        fused_piece<RB, NBUF, NW, QG, RG, KR>(a, qt, seg, rb, re, rot, steps);
         if (KNN_FUSED_FORWARD || segmode) x += adv;
         else x1 -= adv;
+    }
+    if (QG == 2 && a.pace && threadIdx.x == 0) {
+        __hip_atomic_fetch_add(a.pace + 2 * (b & 7), -steps, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(a.pace + 2 * (b & 7) + 1, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -1586,4 +1646,92 @@ hipError_t knn_launch_fused(const GemmFilterArgs& a, const FilterPlan& f, hipStr
     if (e != hipSuccess) return e;
     KNN_LAUNCH_CHECK();
     return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------
+// Host views of the tile copy's piece map and of the balanced schedule (the same functions the
+// kernel runs), for tests/test_fused_tile_image.py.  No GPU call.
+// ---------------------------------------------------------------------------------
+// The tile image of the 8-wave shapes, from the kernel's own FilterTile: out[8] = {row bytes, rows
+// per tile, LDS row stride, slots per row, header offset, header slots, DMA pieces, buffer bytes}
+template <int RB, int RG>
+static void fused_image_of(int* out) {
+    constexpr int HS = RB % 64 == 0 ? 32 * RG / 4 + 1 : 0;  // (as fused_piece)
+    typedef FilterTile<RB, 8, 1, RG, HS> FT;
+    const int v[8] = {RB, FT::BN, FT::STRIDE, FT::SLOTS, FT::HDR, HS, FT::DMA_INS, FT::TILE};
+    for (int i = 0; i < 8; i++) out[i] = v[i];
+}
+extern "C" int knn_fused_debug_image(int d, int rg, int* out) {
+    if (!knn_fused_supported(d) || KNN_FUSED_AUG64 || (rg != 1 && rg != 2)) return -1;
+    if (d == 64) rg == 1 ? fused_image_of<128, 1>(out) : fused_image_of<128, 2>(out);
+    else if (d == 128) rg == 1 ? fused_image_of<256, 1>(out) : fused_image_of<256, 2>(out);
+    else rg == 1 ? fused_image_of<512, 1>(out) : fused_image_of<512, 2>(out);
+    return 0;
+}
+// the LDS offsets lane (j, h) reads: the A fragment of row 32 g + j at k-step s, and the norm
+// read of register group g4 (the kernel's fused_frag_off / fused_norm_off on that image)
+extern "C" int knn_fused_debug_read_off(int d, int rg, int g, int j, int h, int s, int g4, int* frag, int* norm) {
+    int im[8];
+    if (knn_fused_debug_image(d, rg, im) != 0) return -1;
+    *frag = fused_frag_off(32 * g + j, h, s, im[2]);
+    *norm = fused_norm_off(im[4], h, g, g4);
+    return 0;
+}
+
+// d features, nw waves, rg 32-row groups per tile.  src_off[64 ins]: the source offset of each
+// 16-byte slot of the LDS image; issued[tiles][ins]: how many waves issue piece ins of tile t;
+// per_wave[nw]: pieces a wave issues over the tiles.  Returns ins, the pieces per tile.
+extern "C" int knn_fused_debug_piece_map(int d, int nw, int rg, int tiles, uint32_t* src_off, int* issued,
+                                         int* per_wave) {
+    int g[8];
+    if (nw != 8 || tiles < 0 || knn_fused_debug_image(d, rg, g) != 0) return -1;
+    const int rb = g[0], bn = g[1], hs = g[5], ins = g[6];
+    for (int P = 0; P < 64 * ins; P++) src_off[P] = fused_dma_src_off(P, bn, rb, hs, rb);
+    for (int i = 0; i < tiles * ins; i++) issued[i] = 0;
+    for (int w = 0; w < nw; w++) {
+        per_wave[w] = 0;
+        for (int t = 0; t < tiles; t++) {
+            for (int i = 0; i < (ins + nw - 1) / nw; i++)
+                if (fused_dma_piece(nw, w, i) < ins) issued[t * ins + fused_dma_piece(nw, w, i)]++, per_wave[w]++;
+        }
+    }
+    return ins;
+}
+
+// The pieces of the balanced schedule of n_qtiles query tiles against nt train rows on `slots`
+// resident blocks, in the order the blocks run them: out[6 i] = {block, query tile, t0, t1,
+// rot, the piece's place in its block} (64-row units); with bn > 0 also out[6 i + 4] in tiles as
+// the kernel scans it (fused_rot_tiles for bn-row tiles in groups of grp) and out[6 i + 5] the
+// piece's tiles (fused_piece_tiles).  Returns the piece count (-1: more than
+// cap); *grid and *nseg as knn_fused_schedule.
+extern "C" int knn_fused_debug_schedule(long long nt, int n_qtiles, int slots, int bn, int grp, long long* out,
+                                        int cap, int* grid, int* nseg) {
+    if (nt < 1 || n_qtiles < 1 || slots < 1) return -1;
+    GemmFilterArgs a{};
+    a.nt = nt;
+    a.n_qtiles = n_qtiles;
+    *grid = knn_fused_schedule(a, slots, nseg);
+    const int64_t T = a.tiles64;
+    int n = 0;
+    for (int b = 0; b < *grid; b++) {
+        const bool p1 = b < a.p1_blocks;
+        const int64_t b2 = b - a.p1_blocks;
+        int64_t x = p1 ? (int64_t)b * T : b2 * a.w2 / a.g2;
+        int64_t x1 = p1 ? x + T : (b2 + 1) * a.w2 / a.g2;
+        int place = 0;
+        for (bool first = true; x < x1; first = false) {
+            const FusedRangePiece p = knn_fused_range_piece(x, x1, T, first);
+            if (n >= cap) return -1;
+            long long* o = out + 6 * (int64_t)n++;
+            o[0] = b; o[1] = (p1 ? 0 : a.p1_blocks) + p.ql; o[2] = p.t0; o[3] = p.t1; o[4] = p.rot; o[5] = place++;
+            if (bn > 0) {  // (rows as the kernel's piece: [64 t0, min(nt, 64 t1)))
+                const int nt_p = fused_piece_tiles(std::min<int64_t>(nt, p.t1 * 64) - p.t0 * 64, bn, grp);
+                o[4] = fused_rot_tiles(p.rot, bn, grp, nt_p);
+                o[5] = nt_p;
+            }
+            if (KNN_FUSED_FORWARD) x += p.t1 - p.t0;
+            else x1 -= p.t1 - p.t0;
+        }
+    }
+    return n;
 }

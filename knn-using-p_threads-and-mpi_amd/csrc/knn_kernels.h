@@ -67,6 +67,10 @@ struct GemmFilterArgs {
     const float4* tsmax;
     const int32_t* status;  // the call's status word: a set GEMM_UNSAFE bit skips the filter
     const int32_t* gate;    // optional: the filter runs only when *gate != 0 (AUTO's re-run)
+    // fused filter, balanced schedule of one round of blocks (optional): per XCD {steps its running blocks have done,
+    // running blocks}, zeroed before the launch -- a block ahead of its XCD's average waits a
+    // bounded time (fused_pace), so the blocks of an XCD stream the same rows through its L2
+    int32_t* pace;
 };
 
 struct RescoreArgs {
