@@ -401,6 +401,77 @@ knn_status knn_sweep_weighted(knn_ctx* ctx, const knn_dataset* train, const knn_
                               const int32_t* query_labels, int32_t* out_pred_all, int64_t* out_correct,
                               float* out_scores);
 
+/*
+ * Regression: a numeric target per train row instead of a class (sklearn's KNeighborsRegressor;
+ * no reference counterpart), predicted for EVERY k in 1..kmax from the same ordered neighbour
+ * lists as the k-sweep and the weighted vote.  The neighbour list is unchanged: the k smallest
+ * (distance, train index) pairs under the context's metric, after the k-sweep's self-removal
+ * when self_base >= 0.
+ *   targets    float (binary32) per train row, indexed by the list's train rows (global rows for
+ *              merged shards).
+ *   weight     w_j is exactly the weighted vote's binary32 weight: the same three kinds
+ *              (knn_weight), the same zero rule, and the same mapping under the non-Euclidean
+ *              metrics (KNN_W_INV_DIST is 1.0f / D, KNN_W_INV_SQDIST is KNN_EINVAL).
+ *   sums       binary64, in ascending list position, no tree and no reordering:
+ *                N_k = N_{k-1} + (double)w_j * (double)y_j,   D_k = D_{k-1} + (double)w_j.
+ *              The product of two binary32 values is exact in binary64, so whether the step is
+ *              contracted to an FMA or not cannot change a bit.
+ *   prediction for k: (float)(N_k / D_k) -- the binary64 division correctly rounded, then rounded
+ *              to binary32.  KNN_W_UNIFORM gives the mean of the k nearest targets; under the zero
+ *              rule it is the mean over the zero-distance entries of the prefix.
+ *   IEEE       a +inf weight (a subnormal squared distance under KNN_W_INV_SQDIST) or a non-finite
+ *              target gives whatever IEEE gives, NaN included (NaN payloads are unspecified).
+ *   missing    a prefix that reaches a missing entry (-1) predicts NaN for that k and every larger
+ *              k, and the call returns KNN_ERANGE (the outputs are written).
+ *   errors     (optional; need the query targets) e_k(q) = (double)pred_k(q) - (double)yq_q,
+ *              sse[k - 1] = sum_q e_k(q)^2 and sae[k - 1] = sum_q |e_k(q)| in binary64 (e * e is
+ *              rounded, then added).  The order over queries is fixed and depends on the query
+ *              numbers alone -- no floating-point atomics: queries are added in ascending order
+ *              within chunks of 16, the chunks in ascending order within spans of 256, and the
+ *              spans in ascending order into the output (block partials in context workspace and
+ *              a second kernel).  The same call on the same inputs returns the same bits, and so
+ *              does every entry point below on the same lists.  A NaN prediction makes that k's
+ *              sums NaN.  RMSE = sqrt(sse / nq) and MAE = sae / nq are left to the caller.
+ * Outputs: d_pred_all fp32 [kmax][nq] (row k - 1 is what knn_regress_device returns for k), d_sse /
+ *   d_sae double[kmax] (overwritten) are each optional, but not all may be NULL; sse / sae need
+ *   d_query_targets (fp32 [nq]).  Limits are the sweep's: kin <= 1024, kin <= n_train,
+ *   self_base + nq <= n_train.  train->labels is not read and may be NULL on these entry points
+ *   (the pass runs with a context-owned all-zero label array and one class).  An unknown `weights`
+ *   gives KNN_EINVAL.
+ *
+ * knn_regress_vote_device: the regression alone on lists the caller holds (as
+ *   knn_vote_weighted_device: d_idx / d_dist [nq][stride], the first kin entries of a row; d_dist
+ *   may be NULL with KNN_W_UNIFORM) -- from knn_predict_device, knn_merge_vote_device or
+ *   knn_predict_train_sharded, so a train-sharded run gets regression with no new collective.
+ *   A non-missing entry whose distance is NaN or negative gives KNN_EINVAL.  kmax = kin, or
+ *   kin - 1 with self_base.
+ * knn_regress_sweep_device: knn_sweep_device's top-kin pass, then k_regress_sweep on the same
+ *   stream; one synchronisation per pass.  The GEMM path's passes are cut at multiples of 4096
+ *   queries, so the sums do not depend on them.  d_topk_dist / d_topk_idx (optional) receive the
+ *   [nq][kmax] lists after self-removal.  With profile = 1 the stage is named "regress".
+ * knn_regress_device: the single-k form; only row k - 1 is staged and stored (d_pred fp32 [nq]).
+ * knn_regress_sweep: host buffers, batched like knn_sweep_weighted and NOT pipelined.  Batches
+ *   are cut at multiples of 4096 queries and sse / sae stay on the device, added into batch after
+ *   batch in batch order: they are the bits knn_regress_sweep_device returns for all queries.
+ * There is no multi-rank driver: test-sharded callers sum sse / sae over the ranks themselves.
+ */
+knn_status knn_regress_vote_device(knn_ctx* ctx, int64_t nq, int32_t kin, const int32_t* d_idx,
+                                   const float* d_dist, int64_t stride, const float* d_train_targets,
+                                   int32_t weights, int64_t self_base, const float* d_query_targets,
+                                   float* d_pred_all, double* d_sse, double* d_sae, void* hip_stream);
+knn_status knn_regress_sweep_device(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test,
+                                    const float* d_train_targets, int32_t kmax, int32_t weights,
+                                    int64_t self_base, const float* d_query_targets, float* d_pred_all,
+                                    double* d_sse, double* d_sae, float* d_topk_dist, int32_t* d_topk_idx,
+                                    void* hip_stream);
+knn_status knn_regress_device(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test,
+                              const float* d_train_targets, int32_t k, int32_t weights, float* d_pred,
+                              float* d_topk_dist, int32_t* d_topk_idx, void* hip_stream);
+knn_status knn_regress_sweep(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test,
+                             const float* train_targets, int32_t kmax, int32_t weights, int64_t self_base,
+                             const float* query_targets, float* out_pred_all, double* out_sse,
+                             double* out_sae);
+
 /* Per-stage device times (ms) of the last predict call when opts.profile >= 1.
  * names: optional array of n const char* to receive stage names. Returns the
  * number of stages recorded (<= n). */
@@ -465,6 +536,9 @@ void knn_arff_shape(const knn_arff* h, int64_t* n_instances, int32_t* n_attribut
                     int32_t* num_classes);
 /* Copies features [n][ld] (pad zeroed) and (int)(float) labels of the last attribute. */
 knn_status knn_arff_copy(const knn_arff* h, float* feat, int32_t ld, int32_t* labels);
+/* The same with the last attribute as a float, not truncated (regression targets): any finite
+ * value, negative or fractional; num_classes is not meaningful for such a file. */
+knn_status knn_arff_copy_targets(const knn_arff* h, float* feat, int32_t ld, float* targets);
 void knn_arff_close(knn_arff* h);
 
 #ifdef __cplusplus

@@ -120,6 +120,7 @@ struct KnnFlatView {
     int64_t n = 0;
     int d = 0;
     int ld = 0;
+    std::vector<float> targets;   // the class attribute as a float, not truncated (KNN_regress_sweep)
 };
 
 // libarff/arff_data.h:27
@@ -181,6 +182,15 @@ int* KNN_sweep_loo(ArffData* train, int kmax);
 // KNN_W_INV_SQDIST weighs by 1 / squared distance).
 int* KNN_sweep_weighted(ArffData* train, ArffData* test, int kmax, int weights);
 int* KNN_sweep_loo_weighted(ArffData* train, int kmax, int weights);
+// k-NN regression (knn_regress_sweep; knn_amd.h "Regression"): the target of a row is the float
+// value of its last attribute, not truncated (any finite value; num_classes() is not meaningful
+// for such a file).  Returns the predictions for every k in 1..kmax, malloc'd float[kmax * n]
+// laid out [kmax][n], caller frees.  sse / sae (each optional, double[kmax]): the sums of squared
+// and absolute errors against the test rows' own targets.  weights: knn_weight.  Runs on the
+// first device.
+float* KNN_regress_sweep(ArffData* train, ArffData* test, int kmax, int weights, double* sse, double* sae);
+// Leave-one-out on the train set: row i predicted with row i taken out, scored against its target.
+float* KNN_regress_sweep_loo(ArffData* train, int kmax, int weights, double* sse, double* sae);
 // main.cpp:87 -- calloc'd int[C*C], C = dataset->num_classes(), row = true class.
 int* computeConfusionMatrix(int* predictions, ArffData* dataset);
 // main.cpp:102

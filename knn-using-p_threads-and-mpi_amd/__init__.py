@@ -22,6 +22,11 @@ Names follow the reference (srna99/KNN-using-p_threads-and-MPI):
   or "chebyshev"; every predict / top-k / sweep / weighted call of the context follows it (no
   reference counterpart; the rules are in ``knn_amd.h`` "Metrics").  Under the last two
   ``weights="distance"`` is 1 / D and ``"sqdist"`` is rejected.
+* ``Context.regress_sweep_device / regress_loo_device / regress_device / regress_vote_device /
+  regress_sweep``, ``best_k_error`` and ``read_arff_targets``: k-NN regression on float32 targets
+  -- the prediction for every k <= K from the same lists, under the same weight kinds and metrics,
+  with the per-k sums of squared and absolute errors (no reference counterpart; the rules are in
+  ``knn_amd.h`` "Regression")
 
 Features are fp32 or bf16.  Host bf16 arrays are numpy ``uint16`` holding bf16 bits
 (``to_bf16_bits`` / ``bf16_bits_to_f32``); device tensors are ``torch.bfloat16``.
@@ -123,6 +128,11 @@ def load_library(path=LIB_PATH):
         "knn_sweep_weighted_device": (I32, [P, DS, DS, I32, I32, I32, I64, P, P, P, P, P, P, P]),
         "knn_predict_weighted_device": (I32, [P, DS, DS, I32, I32, I32, P, P, P, P, P]),
         "knn_sweep_weighted": (I32, [P, DS, DS, I32, I32, I32, I64, P, P, P, P]),
+        "knn_regress_vote_device": (I32, [P, I64, I32, P, P, I64, P, I32, I64, P, P, P, P, P]),
+        "knn_regress_sweep_device": (I32, [P, DS, DS, P, I32, I32, I64, P, P, P, P, P, P, P]),
+        "knn_regress_device": (I32, [P, DS, DS, P, I32, I32, P, P, P, P]),
+        "knn_regress_sweep": (I32, [P, DS, DS, P, I32, I32, I64, P, P, P, P]),
+        "knn_arff_copy_targets": (I32, [P, P, I32, P]),
         "knn_stage_times": (I32, [P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(F), I32]),
         "knn_last_stats": (I32, [P, ctypes.POINTER(I64), I32]),
         "knn_generate": (I32, [P, P, P, I64, I64, I32, I32, I32, I32, ctypes.c_uint64,
@@ -685,6 +695,118 @@ class Context:
                                                 _ptr(ql), _ptr(pred_all), _ptr(correct), _ptr(sc)))
         return pred_all, correct, sc
 
+    def regress_sweep_device(self, train, targets, test, kmax, weights="uniform", query_targets=None,
+                             pred_all=None, self_base=None, dist=None, idx=None, stream=None, d=None):
+        """k-NN regression for every k in 1..kmax from one top-kmax pass (knn_regress_sweep_device).
+        targets: float32 [n_train].  Returns (pred_all float32 [kmax][nq], sse, sae float64 [kmax]
+        = the sums of squared / absolute errors against query_targets, or None, None without
+        them); pred_all[k - 1] is regress_device's pred for k.  self_base, dist, idx as
+        sweep_device."""
+        import torch
+        self._on_device(train)
+        self._note_train(train)
+        tr = _device_dataset(train, None, d)
+        te = _device_dataset(test, None, d)
+        _check_tensor(targets, "targets", torch.float32, tr.n)
+        if pred_all is None:
+            pred_all = torch.empty((max(kmax, 0), te.n), dtype=torch.float32, device=test.device)
+        _check_tensor(pred_all, "pred_all", torch.float32, max(kmax, 0) * te.n)
+        _outputs(te.n, kmax, None, dist, idx)
+        sse = sae = None
+        if query_targets is not None:
+            _check_tensor(query_targets, "query_targets", torch.float32, te.n)
+            sse = torch.empty(max(kmax, 0), dtype=torch.float64, device=test.device)
+            sae = torch.empty(max(kmax, 0), dtype=torch.float64, device=test.device)
+        self._check(self.lib.knn_regress_sweep_device(
+            self.h, ctypes.byref(tr), ctypes.byref(te), targets.data_ptr(), kmax, _weight_kind(weights),
+            -1 if self_base is None else self_base,
+            None if query_targets is None else query_targets.data_ptr(), pred_all.data_ptr(),
+            None if sse is None else sse.data_ptr(), None if sae is None else sae.data_ptr(),
+            None if dist is None else dist.data_ptr(), None if idx is None else idx.data_ptr(),
+            self._stream(stream, test)))
+        return pred_all, sse, sae
+
+    def regress_loo_device(self, train, targets, kmax, weights="uniform", pred_all=None, dist=None, idx=None,
+                           stream=None, d=None):
+        """Leave-one-out regression on the train set: every row predicted from the others and
+        scored against its own target (loo_device's sibling)."""
+        return self.regress_sweep_device(train, targets, train, kmax, weights, query_targets=targets,
+                                         pred_all=pred_all, self_base=0, dist=dist, idx=idx, stream=stream, d=d)
+
+    def regress_device(self, train, targets, test, k, weights="uniform", pred=None, dist=None, idx=None,
+                       stream=None, d=None):
+        """The regression for one k (knn_regress_device): returns pred float32 [nq].  dist / idx
+        (optional) receive the [nq][k] lists."""
+        import torch
+        self._on_device(train)
+        self._note_train(train)
+        tr = _device_dataset(train, None, d)
+        te = _device_dataset(test, None, d)
+        _check_tensor(targets, "targets", torch.float32, tr.n)
+        if pred is None:
+            pred = torch.empty(te.n, dtype=torch.float32, device=test.device)
+        _check_tensor(pred, "pred", torch.float32, te.n)
+        _outputs(te.n, k, None, dist, idx)
+        self._check(self.lib.knn_regress_device(
+            self.h, ctypes.byref(tr), ctypes.byref(te), targets.data_ptr(), k, _weight_kind(weights),
+            pred.data_ptr(), None if dist is None else dist.data_ptr(), None if idx is None else idx.data_ptr(),
+            self._stream(stream, test)))
+        return pred
+
+    def regress_vote_device(self, idx, dist, train_targets, weights="uniform", query_targets=None, pred_all=None,
+                            self_base=None, kin=None, stream=None):
+        """The regression alone (knn_regress_vote_device) on neighbour lists idx int32 / dist
+        float32 [nq][stride] (dist may be None with "uniform") of which the first kin entries per
+        row are read (default: all).  train_targets is indexed by the lists' train rows.  Returns
+        (pred_all [kmax][nq], sse, sae or None, None); kmax = kin, or kin - 1 with self_base."""
+        import torch
+        self._on_device(idx)
+        if idx.dim() != 2:
+            raise KnnError(KNN_EINVAL, "idx must be a 2-D [nq][stride] tensor")
+        _check_tensor(idx, "idx", torch.int32)
+        if dist is not None:  # (the uniform kind reads no distances)
+            _check_tensor(dist, "dist", torch.float32)
+            if tuple(dist.shape) != tuple(idx.shape) or dist.stride() != idx.stride():
+                raise KnnError(KNN_EINVAL, "dist must have idx's shape and strides")
+            self._on_device(dist)
+        _check_tensor(train_targets, "train_targets", torch.float32)
+        nq, stride = idx.shape
+        kin = stride if kin is None else kin
+        kmax = kin - (0 if self_base is None else 1)
+        if pred_all is None:
+            pred_all = torch.empty((max(kmax, 0), nq), dtype=torch.float32, device=idx.device)
+        _check_tensor(pred_all, "pred_all", torch.float32, max(kmax, 0) * nq)
+        sse = sae = None
+        if query_targets is not None:
+            _check_tensor(query_targets, "query_targets", torch.float32, nq)
+            sse = torch.empty(max(kmax, 0), dtype=torch.float64, device=idx.device)
+            sae = torch.empty(max(kmax, 0), dtype=torch.float64, device=idx.device)
+        self._check(self.lib.knn_regress_vote_device(
+            self.h, nq, kin, idx.data_ptr(), None if dist is None else dist.data_ptr(), stride,
+            train_targets.data_ptr(), _weight_kind(weights), -1 if self_base is None else self_base,
+            None if query_targets is None else query_targets.data_ptr(), pred_all.data_ptr(),
+            None if sse is None else sse.data_ptr(), None if sae is None else sae.data_ptr(),
+            self._stream(stream, idx)))
+        return pred_all, sse, sae
+
+    def regress_sweep(self, train_feat, train_targets, test_feat, kmax, weights="uniform", query_targets=None,
+                      self_base=None):
+        """Host arrays in, host arrays out (knn_regress_sweep; not pipelined): (pred_all float32
+        [kmax][nq], sse, sae float64 [kmax] or None, None without query_targets)."""
+        tr, keep1 = _dataset(train_feat)
+        te, keep2 = _dataset(test_feat)
+        tt = _host_targets(train_targets, "train_targets", tr.n)
+        qt = None if query_targets is None else _host_targets(query_targets, "query_targets", te.n)
+        pred_all = np.zeros((max(kmax, 0), te.n), np.float32)
+        sse = None if qt is None else np.zeros(max(kmax, 0), np.float64)
+        sae = None if qt is None else np.zeros(max(kmax, 0), np.float64)
+        if self.cache_train:
+            self._train_key = keep1
+        self._check(self.lib.knn_regress_sweep(self.h, ctypes.byref(tr), ctypes.byref(te), _ptr(tt), kmax,
+                                               _weight_kind(weights), -1 if self_base is None else self_base,
+                                               _ptr(qt), _ptr(pred_all), _ptr(sse), _ptr(sae)))
+        return pred_all, sse, sae
+
     def generate(self, feat, labels, row0, d, kind, seed, stream_id, num_classes, dtype=None,
                  stream=None):
         """Fill a device tensor [n][ld] (and labels) with the synthetic rows of SURVEY.md 8d.
@@ -948,6 +1070,29 @@ def read_arff(path):
         lib.knn_arff_close(h)
 
 
+def read_arff_targets(path):
+    """(features float32 [n][d], targets float32 [n]): read_arff with the last attribute kept as
+    a float, not truncated to a class (any finite value, negative or fractional)."""
+    lib = load_library()
+    h = ctypes.c_void_p()
+    err = ctypes.create_string_buffer(512)
+    st = lib.knn_arff_open(os.fsencode(path), ctypes.byref(h), err, len(err))
+    if st != KNN_OK:
+        raise KnnError(st, err.value.decode(errors="replace"))
+    try:
+        n, na, C = ctypes.c_int64(), ctypes.c_int32(), ctypes.c_int32()
+        lib.knn_arff_shape(h, ctypes.byref(n), ctypes.byref(na), ctypes.byref(C))
+        d = na.value - 1
+        feat = np.zeros((n.value, d), np.float32)
+        targets = np.zeros(n.value, np.float32)
+        st = lib.knn_arff_copy_targets(h, _ptr(feat), d, _ptr(targets))
+        if st != KNN_OK:
+            raise KnnError(st, "non-numeric or missing value in " + str(path))
+        return feat, targets
+    finally:
+        lib.knn_arff_close(h)
+
+
 def KNN(train, test, k, ctx=None):
     """main.cpp:25 -- train = (features, labels), test = features or (features, labels).
     k <= 0 gives all-zero predictions like the reference."""
@@ -974,6 +1119,29 @@ def best_k(correct):
     if c.ndim != 1 or c.size == 0:
         raise KnnError(KNN_EINVAL, "correct must be a non-empty 1-D array")
     return int(np.argmax(c)) + 1  # argmax returns the first maximum
+
+
+def best_k_error(err):
+    """The smallest k with the least error in a regression's sse or sae [kmax] (numpy array or
+    tensor); NaN entries (a prefix that reached a missing entry, a non-finite target) are ignored.
+    KnnError when every entry is NaN."""
+    e = np.asarray(err.cpu() if hasattr(err, "cpu") else err, dtype=np.float64)
+    ok = ~np.isnan(e)
+    if not ok.any():
+        raise KnnError(KNN_EINVAL, "best_k_error: every entry is NaN")
+    at = np.flatnonzero(ok)
+    return int(at[np.argmin(e[at])]) + 1  # argmin returns the first minimum
+
+
+def _host_targets(t, name, n):
+    """A host target array: float32 and contiguous as it stands -- no silent cast."""
+    if not isinstance(t, np.ndarray) or t.dtype != np.float32:
+        raise KnnError(KNN_EINVAL, f"{name} must be a float32 numpy array, got {getattr(t, 'dtype', type(t))}")
+    if not t.flags["C_CONTIGUOUS"]:
+        raise KnnError(KNN_EINVAL, f"{name} must be contiguous")
+    if t.size < n:
+        raise KnnError(KNN_EINVAL, f"{name} holds {t.size} elements, needs {n}")
+    return t
 
 
 def _weight_kind(weights):

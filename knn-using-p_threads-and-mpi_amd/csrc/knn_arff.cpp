@@ -362,13 +362,17 @@ void flatten(const ParsedArff& P, KnnFlatView* out) {
     if (out->ld == 0) out->ld = 4;
     out->feat.assign((size_t)out->n * out->ld, 0.f);
     out->labels.assign((size_t)out->n, 0);
+    out->targets.assign((size_t)out->n, 0.f);
     for (int64_t r = 0; r < P.n; r++) {
         for (int c = 0; c < na; c++) {
             uint8_t k = P.kinds[(size_t)r * na + c];
             if (k != K_FLOAT) throwf("operator float cannot work on type '%s'!", kind_name(k));
             float v = P.values[(size_t)r * na + c];
             if (c < na - 1) out->feat[(size_t)r * out->ld + c] = v;
-            else out->labels[(size_t)r] = (int32_t)v;
+            else {
+                out->labels[(size_t)r] = (int32_t)v;
+                out->targets[(size_t)r] = v;
+            }
         }
     }
 }
@@ -695,10 +699,12 @@ const KnnFlatView& ArffData::flat() const {
         v->ld = std::max(4, (v->d + 3) & ~3);
         v->feat.assign((size_t)v->n * v->ld, 0.f);
         v->labels.assign((size_t)v->n, 0);
+        v->targets.assign((size_t)v->n, 0.f);
         for (int64_t r = 0; r < v->n; r++) {
             const ArffInstance* in = m_instances[(size_t)r];
             for (int c = 0; c < na - 1; c++) v->feat[(size_t)r * v->ld + c] = (float)(*in->get(c));
             v->labels[(size_t)r] = (int32_t)(float)(*in->get(na - 1));  // main.cpp:57,66
+            v->targets[(size_t)r] = (float)(*in->get(na - 1));
         }
         m_flat = std::move(v);
     });
@@ -840,6 +846,47 @@ int* KNN_sweep_loo_weighted(ArffData* train, int kmax, int weights) {
     return sweep_on_device0(train, train, kmax, true, weights);
 }
 
+// k-NN regression on the first device (knn_regress_sweep): the targets are the float value of the
+// last attribute; test == train with self-exclusion for leave-one-out
+static float* regress_on_device0(ArffData* train, ArffData* test, int kmax, bool loo, int weights, double* sse,
+                                 double* sae) {
+    const KnnFlatView& tr = train->flat();
+    const KnnFlatView& te = test->flat();
+    if (kmax < 1) throwf("KNN_regress_sweep: kmax=%d must be >= 1", kmax);
+    if (tr.d != te.d) throwf("KNN_regress_sweep: train has %d features, test has %d", tr.d, te.d);
+    float* pred = (float*)std::malloc(sizeof(float) * (size_t)kmax * (size_t)(te.n > 0 ? te.n : 1));
+    if (!pred) throwf("KNN_regress_sweep: out of memory");
+    knn_dataset dtr{tr.feat.data(), nullptr, tr.n, tr.d, tr.ld, KNN_F32};
+    knn_dataset dte{te.feat.data(), nullptr, te.n, te.d, te.ld, KNN_F32};
+    std::string why;
+    knn_status s = KNN_OK;
+    try {
+        std::vector<knn_ctx*>& cs = contexts();
+        std::lock_guard<std::mutex> busy(*devices().busy[0]);
+        s = knn_set_generation(cs[0], tr.uid);
+        if (s == KNN_OK)
+            s = knn_regress_sweep(cs[0], &dtr, &dte, tr.targets.data(), kmax, weights, loo ? 0 : -1,
+                                  (sse || sae) ? te.targets.data() : nullptr, pred, sse, sae);
+        if (s != KNN_OK) why = knn_last_error(cs[0]);
+    } catch (...) {
+        std::free(pred);
+        throw;
+    }
+    if (s != KNN_OK) {
+        std::free(pred);
+        throwf("KNN_regress_sweep: %s (status %d)", why.c_str(), (int)s);
+    }
+    return pred;
+}
+
+float* KNN_regress_sweep(ArffData* train, ArffData* test, int kmax, int weights, double* sse, double* sae) {
+    return regress_on_device0(train, test, kmax, false, weights, sse, sae);
+}
+
+float* KNN_regress_sweep_loo(ArffData* train, int kmax, int weights, double* sse, double* sae) {
+    return regress_on_device0(train, train, kmax, true, weights, sse, sae);
+}
+
 void* KNN(void* params) {
     arguments* a = static_cast<arguments*>(params);
     predict_range(a->train, a->test, a->k, a->start, a->end, predictions + a->start);
@@ -915,6 +962,23 @@ knn_status knn_arff_copy(const knn_arff* h, float* feat, int32_t ld, int32_t* la
             float v = h->P->values[o];
             if (c < na - 1) { if (feat) feat[r * ld + c] = v; }
             else if (labels) labels[r] = (int32_t)v;
+        }
+        if (feat) for (int c = na - 1; c < ld; c++) feat[r * ld + c] = 0.f;
+    }
+    return KNN_OK;
+}
+
+knn_status knn_arff_copy_targets(const knn_arff* h, float* feat, int32_t ld, float* targets) {
+    if (!h) return KNN_EINVAL;
+    const int na = (int)h->P->attrs.size();
+    if (na < 1 || ld < na - 1) return KNN_EINVAL;
+    for (int64_t r = 0; r < h->P->n; r++) {
+        for (int c = 0; c < na; c++) {
+            size_t o = (size_t)r * na + c;
+            if (h->P->kinds[o] != K_FLOAT) return KNN_EINVAL;
+            float v = h->P->values[o];
+            if (c < na - 1) { if (feat) feat[r * ld + c] = v; }
+            else if (targets) targets[r] = v;
         }
         if (feat) for (int c = na - 1; c < ld; c++) feat[r * ld + c] = 0.f;
     }

@@ -105,6 +105,10 @@ struct knn_ctx {
     // k-sweep (knn_sweep_device / knn_sweep): the top-kin lists of the pass, and the host entry
     // point's device copies of its outputs and query labels; sized once and grown like the others
     DBuf sw_dist, sw_idx, sw_pred, sw_ql, sw_correct, sw_scores;
+    // regression (knn_regress_*): the error partials [2][kmax][chunks], the all-zero label array
+    // the vote-less pass runs with (the caller has no classes), and the host entry point's device
+    // copies of the train / query targets and of sse | sae
+    DBuf rg_part, rg_zero, rg_targets, rg_qt, rg_sums;
     DBuf arrive;              // k_direct_rows' fused merge: per query group, segments finished
     bool arrive_clean = false;  // arrive is all zero (the last launch ran to completion)
     bool merge_kernel = false;  // study switch KNN_DIRECT_MERGE_KERNEL=1: k_direct_rows' segments via k_merge_vote
@@ -926,7 +930,8 @@ void knn_destroy(knn_ctx* c) {
     (void)hipSetDevice(c->device);
     for (DBuf* b : {&c->tnorm, &c->tnp, &c->qnorm, &c->gthr, &c->cnt, &c->cand,
                     &c->fb_list, &c->ctrl, &c->scratch, &c->split_t, &c->split_q, &c->pad_t, &c->seg_rec, &c->arrive, &c->tmax, &c->tsmax, &c->qstat, &c->tblk, &c->tctrl, &c->cursor, &c->lshare, &c->h_train, &c->h_labels, &c->h_test, &c->h_pred,
-                    &c->h_dist, &c->h_idx, &c->sw_dist, &c->sw_idx, &c->sw_pred, &c->sw_ql, &c->sw_correct, &c->sw_scores})
+                    &c->h_dist, &c->h_idx, &c->sw_dist, &c->sw_idx, &c->sw_pred, &c->sw_ql, &c->sw_correct, &c->sw_scores,
+                    &c->rg_part, &c->rg_zero, &c->rg_targets, &c->rg_qt, &c->rg_sums})
         b->release();
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; i++) {
@@ -1112,7 +1117,11 @@ knn_status train_device(knn_ctx* c, const knn_dataset* tr, hipStream_t st, knn_d
         HIP_OR_FAIL(c, c->h_labels.ensure(sizeof(int32_t) * tr->n));
         HIP_OR_FAIL(c, hipMemcpy2DAsync(c->h_train.p, es * ldd, tr->feat, es * tr->ld, es * tr->d, tr->n,
                                         hipMemcpyHostToDevice, st));
-        HIP_OR_FAIL(c, hipMemcpyAsync(c->h_labels.p, tr->labels, sizeof(int32_t) * tr->n, hipMemcpyHostToDevice, st));
+        // (knn_regress_sweep has no classes: labels == NULL, and the pass runs with zeros)
+        if (tr->labels)
+            HIP_OR_FAIL(c, hipMemcpyAsync(c->h_labels.p, tr->labels, sizeof(int32_t) * tr->n, hipMemcpyHostToDevice, st));
+        else
+            HIP_OR_FAIL(c, hipMemsetAsync(c->h_labels.p, 0, sizeof(int32_t) * tr->n, st));
         c->stats[6] += (int64_t)(es * tr->d * tr->n + sizeof(int32_t) * tr->n);
         if (c->cache_train) {
             tc = {tr->feat, tr->labels, tr->n, tr->d, tr->ld, tr->dtype, ldd, c->generation, true};
@@ -1520,6 +1529,268 @@ knn_status knn_predict_weighted_device(knn_ctx* c, const knn_dataset* tr, const 
     // only row k - 1 of the prefix votes is staged and stored: d_pred is that row
     const WeightedVote wv{weights, k - 1, d_scores};
     return sweep_core(c, tr, te, k, C, -1, nullptr, d_pred, te ? te->n : 0, nullptr, d_topk_dist, d_topk_idx, st, &wv);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// Regression (knn_amd.h "Regression"): k_regress_sweep on the lists of the same top-kin pass
+// ---------------------------------------------------------------------------------
+namespace {
+
+// what the regression entry points share: the kind, the outputs asked for and the list length
+knn_status regress_check(knn_ctx* c, int32_t kmax, int32_t weights, int64_t self_base, const void* qtargets,
+                         const void* pred_all, const void* sse, const void* sae) {
+    if (weights != KNN_W_UNIFORM && weights != KNN_W_INV_DIST && weights != KNN_W_INV_SQDIST)
+        return fail(c, KNN_EINVAL, "regression: unknown weights=%d", weights);
+    if (weights == KNN_W_INV_SQDIST && c->metric != KNN_METRIC_SQEUCLIDEAN)
+        return fail(c, KNN_EINVAL, "regression: KNN_W_INV_SQDIST needs the squared Euclidean metric (metric=%d)",
+                    c->metric);
+    if (kmax < 1) return fail(c, KNN_EINVAL, "regression: kmax=%d must be >= 1", kmax);
+    if (!pred_all && !sse && !sae) return fail(c, KNN_EINVAL, "regression: pred_all, sse and sae are all NULL");
+    if ((sse || sae) && !qtargets) return fail(c, KNN_EINVAL, "regression: sse / sae need the query targets");
+    if (self_base >= 0 && kmax + 1 > 1024)
+        return fail(c, KNN_EINVAL, "regression: kmax=%d + the self row exceeds the supported maximum 1024", kmax);
+    return KNN_OK;
+}
+
+// k_regress_sweep (+ k_regress_reduce, which adds into sse / sae) on lists in device memory,
+// enqueued on st (no synchronisation)
+knn_status regress_enqueue(knn_ctx* c, int64_t nq, int kin, const int32_t* idx, const float* dist, int64_t stride,
+                           const float* targets, int weights, int row0, int64_t self_base, const float* qtargets,
+                           float* pred_all, int64_t pred_stride, double* sse, double* sae, float* dist_out,
+                           int32_t* idx_out, bool check_dist, hipStream_t st) {
+    RegressArgs v{};
+    v.idx = idx; v.dist = dist; v.stride = stride; v.targets = targets;
+    v.nq = nq; v.kin = kin; v.kmax = self_base >= 0 ? kin - 1 : kin;
+    // (the metric's mapping of the kind: vote_weighted_enqueue)
+    v.weights = (c->metric != KNN_METRIC_SQEUCLIDEAN && weights == KNN_W_INV_DIST) ? KNN_VOTE_W_INV_SQDIST : weights;
+    v.self_base = self_base;
+    v.qtargets = qtargets; v.pred_all = pred_all; v.pred_stride = pred_stride; v.row0 = row0;
+    v.dist_out = dist ? dist_out : nullptr; v.idx_out = idx_out;
+    v.check_dist = check_dist ? 1 : 0;
+    v.status = c->ctrl.as<int32_t>();
+    if ((sse || sae) && nq > 0) {
+        HIP_OR_FAIL(c, c->rg_part.ensure(sizeof(double) * 2 * (size_t)v.kmax * (size_t)knn_regress_chunks(nq)));
+        v.part = c->rg_part.as<double>();
+    }
+    stage_begin(c, st, "regress");
+    HIP_OR_FAIL(c, knn_launch_regress(v, st));
+    if (v.part) HIP_OR_FAIL(c, knn_launch_regress_reduce(v.part, nq, v.kmax, row0, sse, sae, st));
+    stage_end(c, st);
+    return KNN_OK;
+}
+
+// the train view the vote-less pass runs with: the caller's features, and -- regression has no
+// classes -- a context-owned all-zero label array with C = 1
+knn_status regress_train(knn_ctx* c, const knn_dataset* tr, hipStream_t st, knn_dataset* out) {
+    *out = *tr;
+    const size_t need = sizeof(int32_t) * (size_t)std::max<int64_t>(tr->n, 1);
+    if (need > c->rg_zero.bytes || !c->rg_zero.p) {
+        HIP_OR_FAIL(c, c->rg_zero.ensure(need));
+        HIP_OR_FAIL(c, hipMemsetAsync(c->rg_zero.p, 0, need, st));
+    }
+    out->labels = c->rg_zero.as<int32_t>();
+    return KNN_OK;
+}
+
+// sweep_core's sibling: one top-kin pass with no vote into the context's list workspace,
+// k_regress_sweep behind it on the same stream, one finish_call per pass.  The GEMM path's passes
+// are cut at multiples of the reduce's span, so that sse / sae -- zeroed here when zero_sums,
+// then added into pass after pass on the stream -- are the bits of a single pass.
+knn_status regress_core(knn_ctx* c, const knn_dataset* tr0, const knn_dataset* te, const float* d_targets,
+                        int32_t kmax, int32_t weights, int row0, int64_t self_base, const float* d_qtargets,
+                        float* d_pred_all, int64_t pred_stride, double* d_sse, double* d_sae, bool zero_sums,
+                        float* d_dist, int32_t* d_idx, hipStream_t st) {
+    knn_status s;
+    if (!tr0) return fail(c, KNN_EINVAL, "train dataset is NULL");
+    const int kin = kmax + (self_base >= 0 ? 1 : 0);
+    const knn_dataset probe{tr0->feat, reinterpret_cast<const int32_t*>(tr0->feat), tr0->n, tr0->d, tr0->ld, tr0->dtype};
+    QueryOut out{nullptr, nullptr, nullptr, nullptr, kin, 0};
+    if ((s = validate_call(c, &probe, te, kin, 1, out, false, false)) != KNN_OK) return s;
+    if (self_base >= 0 && self_base + te->n > tr0->n)
+        return fail(c, KNN_EINVAL, "regression: self rows [%lld, %lld) outside the %lld train rows",
+                    (long long)self_base, (long long)(self_base + te->n), (long long)tr0->n);
+    if (te->n > 0 && !d_targets) return fail(c, KNN_EINVAL, "regression: the train targets are NULL");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    if (zero_sums) {
+        if (d_sse) HIP_OR_FAIL(c, hipMemsetAsync(d_sse, 0, sizeof(double) * (size_t)kmax, st));
+        if (d_sae) HIP_OR_FAIL(c, hipMemsetAsync(d_sae, 0, sizeof(double) * (size_t)kmax, st));
+    }
+    if (te->n == 0) {
+        HIP_OR_FAIL(c, hipStreamSynchronize(st));
+        return KNN_OK;
+    }
+    knn_dataset trz;
+    if ((s = regress_train(c, tr0, st, &trz)) != KNN_OK) return s;
+    const knn_dataset* tr = &trz;
+    const int algo = choose_algo(c, tr->n, te->n, tr->d, kin, tr->dtype);
+    const bool gemm = is_gemm(algo);
+    const int64_t span = (int64_t)KNN_REGRESS_CHUNK * KNN_REGRESS_SPAN;
+    int64_t pass = gemm ? std::max<int64_t>(1, c->ws_queries) : te->n;
+    if (gemm && pass >= span) pass -= pass % span;
+    const int64_t rows = std::min(pass, te->n);
+    HIP_OR_FAIL(c, c->sw_idx.ensure(sizeof(int32_t) * (size_t)rows * kin));
+    HIP_OR_FAIL(c, c->sw_dist.ensure(sizeof(float) * (size_t)rows * kin));
+    out.idx = c->sw_idx.as<int32_t>();
+    out.dist = c->sw_dist.as<float>();
+    for (int64_t q0 = 0; q0 < te->n; q0 += pass) {
+        const int64_t n = std::min(pass, te->n - q0);
+        const knn_dataset tq = offset_rows(*te, q0, n);
+        if ((s = predict_enqueue(c, tr, &tq, kin, 1, out, st, algo, nullptr)) == KNN_OK)
+            s = regress_enqueue(c, n, kin, out.idx, out.dist, kin, d_targets, weights, row0,
+                                self_base >= 0 ? self_base + q0 : -1, d_qtargets ? d_qtargets + q0 : nullptr,
+                                d_pred_all ? d_pred_all + q0 : nullptr, pred_stride, d_sse, d_sae,
+                                d_dist ? d_dist + q0 * kmax : nullptr, d_idx ? d_idx + q0 * kmax : nullptr, false, st);
+        if (s != KNN_OK || (s = finish_call(c, st)) != KNN_OK) {
+            if (s != KNN_EINVAL && s != KNN_ERANGE) c->tprep.valid = c->tpad.valid = false;  // a HIP failure: the operands may be partial
+            return s;
+        }
+        pass_stats(c, c->ctrl_host, gemm);
+    }
+    return KNN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+knn_status knn_regress_vote_device(knn_ctx* c, int64_t nq, int32_t kin, const int32_t* d_idx, const float* d_dist,
+                                   int64_t stride, const float* d_train_targets, int32_t weights, int64_t self_base,
+                                   const float* d_query_targets, float* d_pred_all, double* d_sse, double* d_sae,
+                                   void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    c->stages.clear();
+    const int32_t kmax = self_base >= 0 ? kin - 1 : kin;
+    if (nq < 0 || kin < 1 || kin > 1024 || stride < kin)
+        return fail(c, KNN_EINVAL, "regression: bad nq=%lld kin=%d stride=%lld", (long long)nq, kin, (long long)stride);
+    knn_status s;
+    if ((s = regress_check(c, kmax, weights, self_base, d_query_targets, d_pred_all, d_sse, d_sae)) != KNN_OK) return s;
+    if (nq > 0 && (!d_idx || !d_train_targets || (!d_dist && weights != KNN_W_UNIFORM)))
+        return fail(c, KNN_EINVAL, "regression: d_idx / d_dist / d_train_targets is NULL");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    if (d_sse) HIP_OR_FAIL(c, hipMemsetAsync(d_sse, 0, sizeof(double) * (size_t)kmax, st));
+    if (d_sae) HIP_OR_FAIL(c, hipMemsetAsync(d_sae, 0, sizeof(double) * (size_t)kmax, st));
+    if ((s = regress_enqueue(c, nq, kin, d_idx, d_dist, stride, d_train_targets, weights, 0, self_base, d_query_targets,
+                             d_pred_all, nq, d_sse, d_sae, nullptr, nullptr, true, st)) != KNN_OK)
+        return s;
+    return finish_call(c, st);
+}
+
+knn_status knn_regress_sweep_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te,
+                                    const float* d_train_targets, int32_t kmax, int32_t weights, int64_t self_base,
+                                    const float* d_query_targets, float* d_pred_all, double* d_sse, double* d_sae,
+                                    float* d_topk_dist, int32_t* d_topk_idx, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    knn_status s;
+    if ((s = regress_check(c, kmax, weights, self_base, d_query_targets, d_pred_all, d_sse, d_sae)) != KNN_OK) return s;
+    reset_stats(c);
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    return regress_core(c, tr, te, d_train_targets, kmax, weights, 0, self_base, d_query_targets, d_pred_all,
+                        te ? te->n : 0, d_sse, d_sae, true, d_topk_dist, d_topk_idx, st);
+}
+
+knn_status knn_regress_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, const float* d_train_targets,
+                              int32_t k, int32_t weights, float* d_pred, float* d_topk_dist, int32_t* d_topk_idx,
+                              void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    knn_status s;
+    if ((s = regress_check(c, k, weights, -1, nullptr, d_pred, nullptr, nullptr)) != KNN_OK) return s;
+    reset_stats(c);
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    // only row k - 1 of the prefix predictions is staged and stored: d_pred is that row
+    return regress_core(c, tr, te, d_train_targets, k, weights, k - 1, -1, nullptr, d_pred, te ? te->n : 0, nullptr,
+                        nullptr, false, d_topk_dist, d_topk_idx, st);
+}
+
+knn_status knn_regress_sweep(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, const float* train_targets,
+                             int32_t kmax, int32_t weights, int64_t self_base, const float* query_targets,
+                             float* out_pred_all, double* out_sse, double* out_sae) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    knn_status s;
+    if ((s = check_dataset(c, tr, "train", false)) != KNN_OK) return s;
+    if ((s = check_dataset(c, te, "test", false)) != KNN_OK) return s;
+    if ((s = regress_check(c, kmax, weights, self_base, query_targets, out_pred_all, out_sse, out_sae)) != KNN_OK)
+        return s;
+    if (tr->d != te->d) return fail(c, KNN_EINVAL, "feature count mismatch: train d=%d test d=%d", tr->d, te->d);
+    if (tr->dtype != te->dtype) return fail(c, KNN_EINVAL, "train and test dtypes differ");
+    const int64_t nq = te->n;
+    const int kin = kmax + (self_base >= 0 ? 1 : 0);
+    if (kin > tr->n) return fail(c, KNN_EINVAL, "k=%d outside [1, n_train=%lld]", kin, (long long)tr->n);
+    if (self_base >= 0 && self_base + nq > tr->n)
+        return fail(c, KNN_EINVAL, "regression: self rows [%lld, %lld) outside the %lld train rows",
+                    (long long)self_base, (long long)(self_base + nq), (long long)tr->n);
+    if (tr->n > 0 && !train_targets) return fail(c, KNN_EINVAL, "regression: the train targets are NULL");
+    reset_stats(c);
+    if (out_sse) std::memset(out_sse, 0, sizeof(double) * (size_t)kmax);
+    if (out_sae) std::memset(out_sae, 0, sizeof(double) * (size_t)kmax);
+    if (nq == 0) return KNN_OK;
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int d = tr->d;
+    const size_t es = (size_t)elem_size(tr->dtype);
+    const int ldd = (int)((d + (int)(16 / es) - 1) / (int)(16 / es) * (int)(16 / es));  // device rows padded to 16 B
+    // batches are cut at multiples of the reduce's span: the sums, which stay on the device and are
+    // added into batch after batch, then are the bits knn_regress_sweep_device gives for all queries
+    const int64_t span = (int64_t)KNN_REGRESS_CHUNK * KNN_REGRESS_SPAN;
+    const int64_t B = std::min<int64_t>(nq, std::max<int64_t>(span, c->batch_rows - c->batch_rows % span));
+    {
+        // the device call's checks on the shapes it will see, before anything is enqueued
+        const knn_dataset vtr{(const void*)(uintptr_t)256, (const int32_t*)(uintptr_t)256, tr->n, d, ldd, tr->dtype};
+        const knn_dataset vq{(const void*)(uintptr_t)256, nullptr, B, d, ldd, te->dtype};
+        const QueryOut vo{nullptr, nullptr, nullptr, nullptr, kin, 0};
+        if ((s = validate_call(c, &vtr, &vq, kin, 1, vo, false, false)) != KNN_OK) return s;
+    }
+    // every error from here on drains the stream (no copy from or to the caller's buffers
+    // outlives the call) and drops the train cache entry (its upload may not have run)
+    auto abort_call = [&](knn_status e) {
+        (void)hipStreamSynchronize(st);
+        c->tcache.valid = false;
+        c->tprep.valid = c->tpad.valid = false;
+        return e;
+    };
+    const knn_dataset trn{tr->feat, nullptr, tr->n, tr->d, tr->ld, tr->dtype};  // no classes here
+    knn_dataset dtr;
+    if ((s = train_device(c, &trn, st, &dtr)) != KNN_OK) return abort_call(s);
+    HIP_OR_ABORT(c->rg_targets.ensure(sizeof(float) * (size_t)tr->n));
+    HIP_OR_ABORT(hipMemcpyAsync(c->rg_targets.p, train_targets, sizeof(float) * (size_t)tr->n, hipMemcpyHostToDevice, st));
+    HIP_OR_ABORT(c->q_slot[0].ensure(es * (size_t)ldd * B));
+    if (out_pred_all) HIP_OR_ABORT(c->sw_pred.ensure(sizeof(float) * (size_t)kmax * B));
+    if (query_targets) HIP_OR_ABORT(c->rg_qt.ensure(sizeof(float) * (size_t)B));
+    double *d_sse = nullptr, *d_sae = nullptr;
+    if (out_sse || out_sae) {
+        HIP_OR_ABORT(c->rg_sums.ensure(sizeof(double) * 2 * (size_t)kmax));
+        HIP_OR_ABORT(hipMemsetAsync(c->rg_sums.p, 0, sizeof(double) * 2 * (size_t)kmax, st));
+        if (out_sse) d_sse = c->rg_sums.as<double>();
+        if (out_sae) d_sae = c->rg_sums.as<double>() + kmax;
+    }
+    // one batch after another, each uploaded, swept and downloaded before the next starts
+    for (int64_t q0 = 0; q0 < nq; q0 += B) {
+        const int64_t n = std::min(B, nq - q0);
+        const unsigned char* src = (const unsigned char*)te->feat + es * (size_t)q0 * (size_t)te->ld;
+        HIP_OR_ABORT(hipMemcpy2DAsync(c->q_slot[0].p, es * ldd, src, es * te->ld, es * d, n, hipMemcpyHostToDevice, st));
+        if (query_targets)
+            HIP_OR_ABORT(hipMemcpyAsync(c->rg_qt.p, query_targets + q0, sizeof(float) * n, hipMemcpyHostToDevice, st));
+        c->stats[7] += (int64_t)(es * d * n);
+        const knn_dataset dq{c->q_slot[0].p, nullptr, n, d, ldd, te->dtype};
+        s = regress_core(c, &dtr, &dq, c->rg_targets.as<float>(), kmax, weights, 0, self_base >= 0 ? self_base + q0 : -1,
+                         query_targets ? c->rg_qt.as<float>() : nullptr, out_pred_all ? c->sw_pred.as<float>() : nullptr,
+                         n, d_sse, d_sae, false, nullptr, nullptr, st);
+        if (s != KNN_OK) return abort_call(s);
+        // (a synchronous copy on the null stream: ordered after the context's blocking stream)
+        if (out_pred_all)
+            HIP_OR_ABORT(hipMemcpy2D(out_pred_all + q0, sizeof(float) * (size_t)nq, c->sw_pred.p, sizeof(float) * (size_t)n,
+                                     sizeof(float) * (size_t)n, kmax, hipMemcpyDeviceToHost));
+    }
+    if (out_sse) HIP_OR_ABORT(hipMemcpy(out_sse, d_sse, sizeof(double) * (size_t)kmax, hipMemcpyDeviceToHost));
+    if (out_sae) HIP_OR_ABORT(hipMemcpy(out_sae, d_sae, sizeof(double) * (size_t)kmax, hipMemcpyDeviceToHost));
+    return KNN_OK;
 }
 
 }  // extern "C"

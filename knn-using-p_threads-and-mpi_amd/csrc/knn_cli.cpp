@@ -1,7 +1,7 @@
 // knn_cli.cpp -- command-line driver with the reference's contract.
 //
 //   knn_cli train.arff test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]]
-//           [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev]
+//           [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress]
 //
 // Same positional arguments as ./main (main.cpp:114-122; k parsed with strtol) plus the
 // optional worker count of ./multi-thread (multi-thread.cpp:135-143), here the number of
@@ -19,26 +19,32 @@
 // --metric=manhattan|chebyshev: the distance of the run (KNN_AMD_METRIC; knn_amd.h "Metrics");
 // composes with --sweep[=loo] and --weights=distance (1 / D there).  --weights=sqdist with such
 // a metric prints the library's error and exits 1.  --metric=euclidean is the default.
+// --regress: k-NN regression (KNN_regress_sweep / KNN_regress_sweep_loo): the last attribute is a
+// numeric target, read as a float.  Composes with --sweep[=loo], --weights= and --metric=; prints
+// the regressor's line per k (or the one line for K) with RMSE = sqrt(sse / n) and MAE = sae / n.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <ctime>
 #include <exception>
 #include <iostream>
 #include <string>
+#include <vector>
 
 #include "../../include/knn_arff.hpp"
 
 static int run(int argc, char* argv[]) {
     // --shard=... may sit anywhere; the rest are the reference's positional arguments
     int n = 0;
-    bool sweep = false, loo = false;
+    bool sweep = false, loo = false, regress = false;
     int weights = 0;  // knn_weight
     for (int i = 0; i < argc; i++) {
         if (!std::strncmp(argv[i], "--shard=", 8)) setenv("KNN_AMD_SHARD", argv[i] + 8, 1);
         else if (!std::strcmp(argv[i], "--sweep")) sweep = true;
         else if (!std::strcmp(argv[i], "--sweep=loo")) sweep = loo = true;
+        else if (!std::strcmp(argv[i], "--regress")) regress = true;
         else if (!std::strcmp(argv[i], "--weights=uniform")) weights = 0;
         else if (!std::strcmp(argv[i], "--weights=distance")) weights = 1;
         else if (!std::strcmp(argv[i], "--weights=sqdist")) weights = 2;
@@ -56,7 +62,7 @@ static int run(int argc, char* argv[]) {
     }
     argc = n;
     if (argc != 4 && argc != 5) {
-        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev]"
+        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress]"
                   << std::endl;
         std::exit(0);
     }
@@ -70,6 +76,30 @@ static int run(int argc, char* argv[]) {
     knn_amd_init();
 
     struct timespec start, end;
+    if (regress) {
+        std::vector<double> sse((size_t)(k > 0 ? k : 1)), sae((size_t)(k > 0 ? k : 1));
+        clock_gettime(CLOCK_MONOTONIC_RAW, &start);
+        float* all = loo ? KNN_regress_sweep_loo(train, k, weights, sse.data(), sae.data())
+                         : KNN_regress_sweep(train, test, k, weights, sse.data(), sae.data());
+        clock_gettime(CLOCK_MONOTONIC_RAW, &end);
+        uint64_t diff = (1000000000L * (end.tv_sec - start.tv_sec) + end.tv_nsec - start.tv_nsec) / 1e6;
+        const long nq = test->num_instances();
+        for (int kk = sweep ? 1 : k; kk <= k; kk++)
+            printf("The %i-NN regressor for %lu test instances on %lu train instances required %llu ms CPU time. RMSE was %.4f, MAE %.4f\n",
+                   kk, (unsigned long)nq, (unsigned long)train->num_instances(), (long long unsigned int)diff,
+                   std::sqrt(sse[(size_t)kk - 1] / (double)nq), sae[(size_t)kk - 1] / (double)nq);
+        if (const char* p = std::getenv("KNN_CLI_PRED_OUT")) {  // test hook: the two layouts below, as %.9g
+            FILE* f = std::fopen(p, "w");
+            for (int kk = 0; sweep && kk < k; kk++) {
+                for (long q = 0; q < nq; q++) std::fprintf(f, q ? " %.9g" : "%.9g", all[(size_t)kk * nq + q]);
+                std::fprintf(f, "\n");
+            }
+            for (long q = 0; !sweep && q < nq; q++) std::fprintf(f, "%.9g\n", all[(size_t)(k - 1) * nq + q]);
+            std::fclose(f);
+        }
+        std::free(all);
+        return 0;
+    }
     if (sweep || weights) {
         clock_gettime(CLOCK_MONOTONIC_RAW, &start);
         int* all = weights ? (loo ? KNN_sweep_loo_weighted(train, k, weights) : KNN_sweep_weighted(train, test, k, weights))

@@ -454,3 +454,12 @@ __device__ __forceinline__ float kth_dist(u64 T, int k) {
 #ifndef DT_SHIFT_MAX
 #define DT_SHIFT_MAX 8  // passing rows per tile and query up to which the lane shift beats the sort
 #endif
+
+// the binary32 weight of a neighbour at distance d (knn_amd.h "Weighted vote"; k_vote_weighted
+// and k_regress_sweep): 1, 1 / sqrtf(d) or 1 / d, correctly rounded (no fast-math flag on the
+// files that use it); under the zero rule 1 for d == 0 and 0 otherwise
+__device__ __forceinline__ float vote_weight(int kind, bool zero_mode, float d) {
+    if (kind == KNN_VOTE_W_UNIFORM) return 1.0f;
+    if (zero_mode) return d == 0.0f ? 1.0f : 0.0f;
+    return kind == KNN_VOTE_W_INV_DIST ? 1.0f / sqrtf(d) : 1.0f / d;
+}

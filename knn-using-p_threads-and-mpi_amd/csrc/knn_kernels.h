@@ -137,6 +137,32 @@ struct VoteWeightedArgs {
 };
 hipError_t knn_launch_vote_weighted(const VoteWeightedArgs& a, hipStream_t st);
 
+// k_regress_sweep (knn_regress.hip): the k-NN regression prediction over every prefix.  idx /
+// dist / stride / kin / kmax / weights / self_base / row0 / dist_out / idx_out / check_dist as
+// VoteWeightedArgs; targets[idx] is an entry's fp32 target.  pred_all (optional) fp32, points at
+// row row0 of [kmax][pred_stride].  part (optional, needs qtargets): the error partials
+// [2][kmax][knn_regress_chunks(nq)] binary64 -- [0]: the sum of e^2, [1]: of |e|, over the
+// chunk's queries -- which k_regress_reduce adds INTO sse / sae [kmax] (each optional) in a fixed
+// order: chunks of KNN_REGRESS_CHUNK queries ascending within spans of KNN_REGRESS_SPAN chunks,
+// then the spans ascending.  The order depends on the query numbers alone, so a call on
+// queries [0, n) followed by one on [n, n2) leaves the bits of one call on [0, n2) whenever n is
+// a multiple of KNN_REGRESS_CHUNK * KNN_REGRESS_SPAN.
+#define KNN_REGRESS_CHUNK 16
+#define KNN_REGRESS_SPAN 256
+struct RegressArgs {
+    const int32_t* idx; const float* dist; int64_t stride; const float* targets;
+    int64_t nq; int kin; int kmax; int weights; int64_t self_base;
+    const float* qtargets; float* pred_all; int64_t pred_stride; int row0;
+    double* part; float* dist_out; int32_t* idx_out;
+    int check_dist;
+    int32_t* status;
+    int qb;  // queries per LDS tile (set by the launcher)
+};
+inline int64_t knn_regress_chunks(int64_t nq) { return (nq + KNN_REGRESS_CHUNK - 1) / KNN_REGRESS_CHUNK; }
+hipError_t knn_launch_regress(const RegressArgs& a, hipStream_t st);
+hipError_t knn_launch_regress_reduce(const double* part, int64_t nq, int kmax, int row0, double* sse, double* sae,
+                                     hipStream_t st);
+
 // class counts up to this many live in a per-wave LDS table; above it the vote runs
 // table-free (vote_ballot), so every path accepts any num_classes
 #define KNN_VOTE_LDS_MAX_C 1024

@@ -12,13 +12,8 @@
 
 // every weight and every sum below is one IEEE binary32 operation: no contraction, and the
 // default correctly rounded 1.0f / x and sqrtf (no fast-math flag on this file)
+// (the weight itself is vote_weight, knn_device.h: k_regress_sweep uses the same values)
 #pragma clang fp contract(off)
-
-__device__ __forceinline__ float vote_weight(int kind, bool zero_mode, float d) {
-    if (kind == KNN_VOTE_W_UNIFORM) return 1.0f;
-    if (zero_mode) return d == 0.0f ? 1.0f : 0.0f;
-    return kind == KNN_VOTE_W_INV_DIST ? 1.0f / sqrtf(d) : 1.0f / d;
-}
 
 // ---------------------------------------------------------------------------------
 // k_vote_weighted<R>: k_vote_sweep's skeleton -- one wave per query, element e = 64 r + lane
