@@ -173,6 +173,16 @@ def _ptr(a):
     return None if a is None else ctypes.c_void_p(a.ctypes.data)
 
 
+def _opt_ptr(t):
+    """An optional device tensor's address (None: NULL)."""
+    return None if t is None else t.data_ptr()
+
+
+def _self_base(self_base):
+    """The C ABI's self_base: -1 without self-removal."""
+    return -1 if self_base is None else self_base
+
+
 def to_bf16_bits(x):
     """float32 array -> uint16 bf16 bits (round to nearest even; exact for bf16 values)."""
     u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
@@ -234,7 +244,7 @@ def _device_dataset(feat, labels=None, d=None):
         raise KnnError(KNN_EINVAL, f"d={d} exceeds the tensor's {feat.shape[1]} columns")
     if labels is not None:
         _check_tensor(labels, "labels", torch.int32, feat.shape[0])
-    return knn_dataset(feat.data_ptr(), None if labels is None else labels.data_ptr(), feat.shape[0], d,
+    return knn_dataset(feat.data_ptr(), _opt_ptr(labels), feat.shape[0], d,
                        ld, _tensor_dtype(feat))
 
 
@@ -456,7 +466,7 @@ class Context:
         _outputs(te.n, k, pred, dist, idx)
         self._check(self.lib.knn_predict_device(
             self.h, ctypes.byref(tr), ctypes.byref(te), k, num_classes, pred.data_ptr(),
-            None if dist is None else dist.data_ptr(), None if idx is None else idx.data_ptr(),
+            _opt_ptr(dist), _opt_ptr(idx),
             self._stream(stream, test)))
 
     def shard_topk_device(self, train, labels, test, k, num_classes, idx_base, rec, stream=None, d=None):
@@ -484,8 +494,68 @@ class Context:
         _outputs(nq, k, pred, dist, idx)
         self._check(self.lib.knn_merge_vote_device(
             self.h, nsrc, nq, k, num_classes, rec.data_ptr(), pred.data_ptr(),
-            None if dist is None else dist.data_ptr(), None if idx is None else idx.data_ptr(),
+            _opt_ptr(dist), _opt_ptr(idx),
             self._stream(stream, rec)))
+
+    # what the sweep-shaped calls (the k-sweep, the weighted vote, regression) share
+    def _datasets_arg(self, train, labels, test, d):
+        """The train / test knn_datasets of a device call; the train tensor is on this device and
+        noted for the cache."""
+        self._on_device(train)
+        self._note_train(train)
+        return _device_dataset(train, labels, d), _device_dataset(test, None, d)
+
+    def _lists_arg(self, idx, dist, kin, self_base):
+        """Neighbour lists idx int32 [nq][stride] and, optional, dist float32 of the same shape
+        and strides (the uniform kind reads no distances), of which the first kin entries per row
+        are read (None: all): returns nq, stride, kin, kmax (kin, or kin - 1 with self_base)."""
+        import torch
+        self._on_device(idx)
+        if idx.dim() != 2:
+            raise KnnError(KNN_EINVAL, "idx must be a 2-D [nq][stride] tensor")
+        _check_tensor(idx, "idx", torch.int32)
+        if dist is not None:
+            _check_tensor(dist, "dist", torch.float32)
+            if tuple(dist.shape) != tuple(idx.shape) or dist.stride() != idx.stride():
+                raise KnnError(KNN_EINVAL, "dist must have idx's shape and strides")
+            self._on_device(dist)
+        nq, stride = idx.shape
+        kin = stride if kin is None else kin
+        return nq, stride, kin, kin - (0 if self_base is None else 1)
+
+    @staticmethod
+    def _pred_all_arg(pred_all, kmax, nq, dtype, device):
+        """The caller's pred_all [kmax][nq], or a new one."""
+        import torch
+        if pred_all is None:
+            pred_all = torch.empty((max(kmax, 0), nq), dtype=dtype, device=device)
+        return _check_tensor(pred_all, "pred_all", dtype, max(kmax, 0) * nq)
+
+    @staticmethod
+    def _accum(side, name, side_dtype, nq, kmax, dtype, n=1):
+        """The n per-k accumulators [kmax] that go with the queries' side input (labels -> correct,
+        targets -> sse, sae), on its device; n Nones without it."""
+        import torch
+        if side is None:
+            return [None] * n
+        _check_tensor(side, name, side_dtype, nq)
+        return [torch.empty(max(kmax, 0), dtype=dtype, device=side.device) for _ in range(n)]
+
+    def _host_class_args(self, train_feat, train_labels, test_feat, kmax, num_classes, query_labels):
+        """sweep's and sweep_weighted's host arguments: (train, test, num_classes, pred_all, query
+        labels, correct, the arrays the datasets point into: held by the caller over its call)."""
+        tr, keep = _dataset(train_feat, train_labels)
+        te, keep2 = _dataset(test_feat)
+        if num_classes is None:
+            num_classes = int(keep[1].max()) + 1 if keep[1].size else 1
+        pred_all = np.zeros((max(kmax, 0), te.n), np.int32)
+        ql = None if query_labels is None else np.ascontiguousarray(query_labels, dtype=np.int32)
+        if ql is not None and ql.size < te.n:
+            raise KnnError(KNN_EINVAL, f"query_labels holds {ql.size} elements, needs {te.n}")
+        correct = None if ql is None else np.zeros(max(kmax, 0), np.int64)
+        if self.cache_train:
+            self._train_key = keep
+        return tr, te, num_classes, pred_all, ql, correct, (keep, keep2)
 
     def sweep_device(self, train, labels, test, kmax, num_classes, query_labels=None, pred_all=None,
                      self_base=None, dist=None, idx=None, stream=None, d=None):
@@ -495,23 +565,14 @@ class Context:
         self_base: query q is train row self_base + q and is left out of its own neighbours
         (test must be those train rows).  dist / idx (optional) receive the [nq][kmax] lists."""
         import torch
-        self._on_device(train)
-        self._note_train(train)
-        tr = _device_dataset(train, labels, d)
-        te = _device_dataset(test, None, d)
-        if pred_all is None:
-            pred_all = torch.empty((kmax, te.n), dtype=torch.int32, device=test.device)
-        _check_tensor(pred_all, "pred_all", torch.int32, kmax * te.n)
+        tr, te = self._datasets_arg(train, labels, test, d)
+        pred_all = self._pred_all_arg(pred_all, kmax, te.n, torch.int32, test.device)
         _outputs(te.n, kmax, None, dist, idx)
-        correct = None
-        if query_labels is not None:
-            _check_tensor(query_labels, "query_labels", torch.int32, te.n)
-            correct = torch.empty(kmax, dtype=torch.int64, device=test.device)
+        correct, = self._accum(query_labels, "query_labels", torch.int32, te.n, kmax, torch.int64)
         self._check(self.lib.knn_sweep_device(
-            self.h, ctypes.byref(tr), ctypes.byref(te), kmax, num_classes, -1 if self_base is None else self_base,
-            None if query_labels is None else query_labels.data_ptr(), pred_all.data_ptr(),
-            None if correct is None else correct.data_ptr(), None if dist is None else dist.data_ptr(),
-            None if idx is None else idx.data_ptr(), self._stream(stream, test)))
+            self.h, ctypes.byref(tr), ctypes.byref(te), kmax, num_classes, _self_base(self_base),
+            _opt_ptr(query_labels), pred_all.data_ptr(), _opt_ptr(correct), _opt_ptr(dist), _opt_ptr(idx),
+            self._stream(stream, test)))
         return pred_all, correct
 
     def loo_device(self, train, labels, kmax, num_classes, pred_all=None, dist=None, idx=None, stream=None,
@@ -529,45 +590,24 @@ class Context:
         rows.  Returns (pred_all [kmax][nq], correct or None); kmax = kin, or kin - 1 with
         self_base."""
         import torch
-        self._on_device(idx)
-        if idx.dim() != 2:
-            raise KnnError(KNN_EINVAL, "idx must be a 2-D [nq][stride] tensor")
-        _check_tensor(idx, "idx", torch.int32)
+        nq, stride, kin, kmax = self._lists_arg(idx, None, kin, self_base)
         _check_tensor(train_labels, "train_labels", torch.int32)
-        nq, stride = idx.shape
-        kin = stride if kin is None else kin
-        kmax = kin - (0 if self_base is None else 1)
-        if pred_all is None:
-            pred_all = torch.empty((max(kmax, 0), nq), dtype=torch.int32, device=idx.device)
-        _check_tensor(pred_all, "pred_all", torch.int32, max(kmax, 0) * nq)
-        correct = None
-        if query_labels is not None:
-            _check_tensor(query_labels, "query_labels", torch.int32, nq)
-            correct = torch.empty(max(kmax, 0), dtype=torch.int64, device=idx.device)
+        pred_all = self._pred_all_arg(pred_all, kmax, nq, torch.int32, idx.device)
+        correct, = self._accum(query_labels, "query_labels", torch.int32, nq, kmax, torch.int64)
         self._check(self.lib.knn_vote_sweep_device(
             self.h, nq, kin, num_classes, idx.data_ptr(), stride, train_labels.data_ptr(),
-            -1 if self_base is None else self_base, None if query_labels is None else query_labels.data_ptr(),
-            pred_all.data_ptr(), None if correct is None else correct.data_ptr(), self._stream(stream, idx)))
+            _self_base(self_base), _opt_ptr(query_labels), pred_all.data_ptr(), _opt_ptr(correct),
+            self._stream(stream, idx)))
         return pred_all, correct
 
     def sweep(self, train_feat, train_labels, test_feat, kmax, num_classes=None, query_labels=None,
               self_base=None):
         """Host arrays in, host arrays out (knn_sweep; not pipelined): (pred_all int32
         [kmax][nq], correct int64 [kmax] or None without query_labels)."""
-        tr, keep1 = _dataset(train_feat, train_labels)
-        te, keep2 = _dataset(test_feat)
-        if num_classes is None:
-            num_classes = int(keep1[1].max()) + 1 if keep1[1].size else 1
-        pred_all = np.zeros((max(kmax, 0), te.n), np.int32)
-        ql = None if query_labels is None else np.ascontiguousarray(query_labels, dtype=np.int32)
-        if ql is not None and ql.size < te.n:
-            raise KnnError(KNN_EINVAL, f"query_labels holds {ql.size} elements, needs {te.n}")
-        correct = None if ql is None else np.zeros(max(kmax, 0), np.int64)
-        if self.cache_train:
-            self._train_key = keep1
+        tr, te, num_classes, pred_all, ql, correct, keep = self._host_class_args(
+            train_feat, train_labels, test_feat, kmax, num_classes, query_labels)
         self._check(self.lib.knn_sweep(self.h, ctypes.byref(tr), ctypes.byref(te), kmax, num_classes,
-                                       -1 if self_base is None else self_base, _ptr(ql), _ptr(pred_all),
-                                       _ptr(correct)))
+                                       _self_base(self_base), _ptr(ql), _ptr(pred_all), _ptr(correct)))
         return pred_all, correct
 
     @staticmethod
@@ -588,26 +628,15 @@ class Context:
         without query_labels, scores float32 [nq][C] = each class's summed weight over the kmax
         neighbours, or None with scores=False); ``proba(scores)`` normalises them."""
         import torch
-        self._on_device(train)
-        self._note_train(train)
-        tr = _device_dataset(train, labels, d)
-        te = _device_dataset(test, None, d)
-        if pred_all is None:
-            pred_all = torch.empty((max(kmax, 0), te.n), dtype=torch.int32, device=test.device)
-        _check_tensor(pred_all, "pred_all", torch.int32, max(kmax, 0) * te.n)
+        tr, te = self._datasets_arg(train, labels, test, d)
+        pred_all = self._pred_all_arg(pred_all, kmax, te.n, torch.int32, test.device)
         _outputs(te.n, kmax, None, dist, idx)
         scores = self._scores_arg(scores, te.n, num_classes, test.device)
-        correct = None
-        if query_labels is not None:
-            _check_tensor(query_labels, "query_labels", torch.int32, te.n)
-            correct = torch.empty(max(kmax, 0), dtype=torch.int64, device=test.device)
+        correct, = self._accum(query_labels, "query_labels", torch.int32, te.n, kmax, torch.int64)
         self._check(self.lib.knn_sweep_weighted_device(
             self.h, ctypes.byref(tr), ctypes.byref(te), kmax, num_classes, _weight_kind(weights),
-            -1 if self_base is None else self_base,
-            None if query_labels is None else query_labels.data_ptr(), pred_all.data_ptr(),
-            None if correct is None else correct.data_ptr(), None if scores is None else scores.data_ptr(),
-            None if dist is None else dist.data_ptr(), None if idx is None else idx.data_ptr(),
-            self._stream(stream, test)))
+            _self_base(self_base), _opt_ptr(query_labels), pred_all.data_ptr(), _opt_ptr(correct), _opt_ptr(scores),
+            _opt_ptr(dist), _opt_ptr(idx), self._stream(stream, test)))
         return pred_all, correct, scores
 
     def loo_weighted_device(self, train, labels, kmax, num_classes, weights="distance", pred_all=None, scores=True,
@@ -622,18 +651,14 @@ class Context:
         """The weighted vote for one k (knn_predict_weighted_device): returns (pred int32 [nq],
         scores float32 [nq][C] or None).  dist / idx (optional) receive the [nq][k] lists."""
         import torch
-        self._on_device(train)
-        self._note_train(train)
-        tr = _device_dataset(train, labels, d)
-        te = _device_dataset(test, None, d)
+        tr, te = self._datasets_arg(train, labels, test, d)
         if pred is None:
             pred = torch.empty(te.n, dtype=torch.int32, device=test.device)
         _outputs(te.n, k, pred, dist, idx)
         scores = self._scores_arg(scores, te.n, num_classes, test.device)
         self._check(self.lib.knn_predict_weighted_device(
             self.h, ctypes.byref(tr), ctypes.byref(te), k, num_classes, _weight_kind(weights), pred.data_ptr(),
-            None if scores is None else scores.data_ptr(), None if dist is None else dist.data_ptr(),
-            None if idx is None else idx.data_ptr(), self._stream(stream, test)))
+            _opt_ptr(scores), _opt_ptr(dist), _opt_ptr(idx), self._stream(stream, test)))
         return pred, scores
 
     def vote_weighted_device(self, idx, dist, train_labels, num_classes, weights="distance", query_labels=None,
@@ -643,34 +668,15 @@ class Context:
         row are read (default: all).  Returns (pred_all [kmax][nq], correct or None, scores or
         None); kmax = kin, or kin - 1 with self_base."""
         import torch
-        self._on_device(idx)
-        if idx.dim() != 2:
-            raise KnnError(KNN_EINVAL, "idx must be a 2-D [nq][stride] tensor")
-        _check_tensor(idx, "idx", torch.int32)
-        if dist is not None:  # (the uniform kind reads no distances)
-            _check_tensor(dist, "dist", torch.float32)
-            if tuple(dist.shape) != tuple(idx.shape) or dist.stride() != idx.stride():
-                raise KnnError(KNN_EINVAL, "dist must have idx's shape and strides")
-            self._on_device(dist)
+        nq, stride, kin, kmax = self._lists_arg(idx, dist, kin, self_base)
         _check_tensor(train_labels, "train_labels", torch.int32)
-        nq, stride = idx.shape
-        kin = stride if kin is None else kin
-        kmax = kin - (0 if self_base is None else 1)
-        if pred_all is None:
-            pred_all = torch.empty((max(kmax, 0), nq), dtype=torch.int32, device=idx.device)
-        _check_tensor(pred_all, "pred_all", torch.int32, max(kmax, 0) * nq)
+        pred_all = self._pred_all_arg(pred_all, kmax, nq, torch.int32, idx.device)
         scores = self._scores_arg(scores, nq, num_classes, idx.device)
-        correct = None
-        if query_labels is not None:
-            _check_tensor(query_labels, "query_labels", torch.int32, nq)
-            correct = torch.empty(max(kmax, 0), dtype=torch.int64, device=idx.device)
+        correct, = self._accum(query_labels, "query_labels", torch.int32, nq, kmax, torch.int64)
         self._check(self.lib.knn_vote_weighted_device(
-            self.h, nq, kin, num_classes, idx.data_ptr(), None if dist is None else dist.data_ptr(), stride,
-            train_labels.data_ptr(),
-            _weight_kind(weights), -1 if self_base is None else self_base,
-            None if query_labels is None else query_labels.data_ptr(), pred_all.data_ptr(),
-            None if correct is None else correct.data_ptr(), None if scores is None else scores.data_ptr(),
-            self._stream(stream, idx)))
+            self.h, nq, kin, num_classes, idx.data_ptr(), _opt_ptr(dist), stride, train_labels.data_ptr(),
+            _weight_kind(weights), _self_base(self_base), _opt_ptr(query_labels), pred_all.data_ptr(),
+            _opt_ptr(correct), _opt_ptr(scores), self._stream(stream, idx)))
         return pred_all, correct, scores
 
     def sweep_weighted(self, train_feat, train_labels, test_feat, kmax, num_classes=None, weights="distance",
@@ -678,20 +684,11 @@ class Context:
         """Host arrays in, host arrays out (knn_sweep_weighted; not pipelined): (pred_all int32
         [kmax][nq], correct int64 [kmax] or None without query_labels, scores float32 [nq][C] or
         None with scores=False)."""
-        tr, keep1 = _dataset(train_feat, train_labels)
-        te, keep2 = _dataset(test_feat)
-        if num_classes is None:
-            num_classes = int(keep1[1].max()) + 1 if keep1[1].size else 1
-        pred_all = np.zeros((max(kmax, 0), te.n), np.int32)
-        ql = None if query_labels is None else np.ascontiguousarray(query_labels, dtype=np.int32)
-        if ql is not None and ql.size < te.n:
-            raise KnnError(KNN_EINVAL, f"query_labels holds {ql.size} elements, needs {te.n}")
-        correct = None if ql is None else np.zeros(max(kmax, 0), np.int64)
+        tr, te, num_classes, pred_all, ql, correct, keep = self._host_class_args(
+            train_feat, train_labels, test_feat, kmax, num_classes, query_labels)
         sc = np.zeros((te.n, max(num_classes, 0)), np.float32) if scores else None
-        if self.cache_train:
-            self._train_key = keep1
         self._check(self.lib.knn_sweep_weighted(self.h, ctypes.byref(tr), ctypes.byref(te), kmax, num_classes,
-                                                _weight_kind(weights), -1 if self_base is None else self_base,
+                                                _weight_kind(weights), _self_base(self_base),
                                                 _ptr(ql), _ptr(pred_all), _ptr(correct), _ptr(sc)))
         return pred_all, correct, sc
 
@@ -703,27 +700,15 @@ class Context:
         them); pred_all[k - 1] is regress_device's pred for k.  self_base, dist, idx as
         sweep_device."""
         import torch
-        self._on_device(train)
-        self._note_train(train)
-        tr = _device_dataset(train, None, d)
-        te = _device_dataset(test, None, d)
+        tr, te = self._datasets_arg(train, None, test, d)
         _check_tensor(targets, "targets", torch.float32, tr.n)
-        if pred_all is None:
-            pred_all = torch.empty((max(kmax, 0), te.n), dtype=torch.float32, device=test.device)
-        _check_tensor(pred_all, "pred_all", torch.float32, max(kmax, 0) * te.n)
+        pred_all = self._pred_all_arg(pred_all, kmax, te.n, torch.float32, test.device)
         _outputs(te.n, kmax, None, dist, idx)
-        sse = sae = None
-        if query_targets is not None:
-            _check_tensor(query_targets, "query_targets", torch.float32, te.n)
-            sse = torch.empty(max(kmax, 0), dtype=torch.float64, device=test.device)
-            sae = torch.empty(max(kmax, 0), dtype=torch.float64, device=test.device)
+        sse, sae = self._accum(query_targets, "query_targets", torch.float32, te.n, kmax, torch.float64, 2)
         self._check(self.lib.knn_regress_sweep_device(
             self.h, ctypes.byref(tr), ctypes.byref(te), targets.data_ptr(), kmax, _weight_kind(weights),
-            -1 if self_base is None else self_base,
-            None if query_targets is None else query_targets.data_ptr(), pred_all.data_ptr(),
-            None if sse is None else sse.data_ptr(), None if sae is None else sae.data_ptr(),
-            None if dist is None else dist.data_ptr(), None if idx is None else idx.data_ptr(),
-            self._stream(stream, test)))
+            _self_base(self_base), _opt_ptr(query_targets), pred_all.data_ptr(), _opt_ptr(sse), _opt_ptr(sae),
+            _opt_ptr(dist), _opt_ptr(idx), self._stream(stream, test)))
         return pred_all, sse, sae
 
     def regress_loo_device(self, train, targets, kmax, weights="uniform", pred_all=None, dist=None, idx=None,
@@ -738,10 +723,7 @@ class Context:
         """The regression for one k (knn_regress_device): returns pred float32 [nq].  dist / idx
         (optional) receive the [nq][k] lists."""
         import torch
-        self._on_device(train)
-        self._note_train(train)
-        tr = _device_dataset(train, None, d)
-        te = _device_dataset(test, None, d)
+        tr, te = self._datasets_arg(train, None, test, d)
         _check_tensor(targets, "targets", torch.float32, tr.n)
         if pred is None:
             pred = torch.empty(te.n, dtype=torch.float32, device=test.device)
@@ -749,8 +731,7 @@ class Context:
         _outputs(te.n, k, None, dist, idx)
         self._check(self.lib.knn_regress_device(
             self.h, ctypes.byref(tr), ctypes.byref(te), targets.data_ptr(), k, _weight_kind(weights),
-            pred.data_ptr(), None if dist is None else dist.data_ptr(), None if idx is None else idx.data_ptr(),
-            self._stream(stream, test)))
+            pred.data_ptr(), _opt_ptr(dist), _opt_ptr(idx), self._stream(stream, test)))
         return pred
 
     def regress_vote_device(self, idx, dist, train_targets, weights="uniform", query_targets=None, pred_all=None,
@@ -760,33 +741,14 @@ class Context:
         row are read (default: all).  train_targets is indexed by the lists' train rows.  Returns
         (pred_all [kmax][nq], sse, sae or None, None); kmax = kin, or kin - 1 with self_base."""
         import torch
-        self._on_device(idx)
-        if idx.dim() != 2:
-            raise KnnError(KNN_EINVAL, "idx must be a 2-D [nq][stride] tensor")
-        _check_tensor(idx, "idx", torch.int32)
-        if dist is not None:  # (the uniform kind reads no distances)
-            _check_tensor(dist, "dist", torch.float32)
-            if tuple(dist.shape) != tuple(idx.shape) or dist.stride() != idx.stride():
-                raise KnnError(KNN_EINVAL, "dist must have idx's shape and strides")
-            self._on_device(dist)
+        nq, stride, kin, kmax = self._lists_arg(idx, dist, kin, self_base)
         _check_tensor(train_targets, "train_targets", torch.float32)
-        nq, stride = idx.shape
-        kin = stride if kin is None else kin
-        kmax = kin - (0 if self_base is None else 1)
-        if pred_all is None:
-            pred_all = torch.empty((max(kmax, 0), nq), dtype=torch.float32, device=idx.device)
-        _check_tensor(pred_all, "pred_all", torch.float32, max(kmax, 0) * nq)
-        sse = sae = None
-        if query_targets is not None:
-            _check_tensor(query_targets, "query_targets", torch.float32, nq)
-            sse = torch.empty(max(kmax, 0), dtype=torch.float64, device=idx.device)
-            sae = torch.empty(max(kmax, 0), dtype=torch.float64, device=idx.device)
+        pred_all = self._pred_all_arg(pred_all, kmax, nq, torch.float32, idx.device)
+        sse, sae = self._accum(query_targets, "query_targets", torch.float32, nq, kmax, torch.float64, 2)
         self._check(self.lib.knn_regress_vote_device(
-            self.h, nq, kin, idx.data_ptr(), None if dist is None else dist.data_ptr(), stride,
-            train_targets.data_ptr(), _weight_kind(weights), -1 if self_base is None else self_base,
-            None if query_targets is None else query_targets.data_ptr(), pred_all.data_ptr(),
-            None if sse is None else sse.data_ptr(), None if sae is None else sae.data_ptr(),
-            self._stream(stream, idx)))
+            self.h, nq, kin, idx.data_ptr(), _opt_ptr(dist), stride, train_targets.data_ptr(),
+            _weight_kind(weights), _self_base(self_base), _opt_ptr(query_targets), pred_all.data_ptr(),
+            _opt_ptr(sse), _opt_ptr(sae), self._stream(stream, idx)))
         return pred_all, sse, sae
 
     def regress_sweep(self, train_feat, train_targets, test_feat, kmax, weights="uniform", query_targets=None,
@@ -803,7 +765,7 @@ class Context:
         if self.cache_train:
             self._train_key = keep1
         self._check(self.lib.knn_regress_sweep(self.h, ctypes.byref(tr), ctypes.byref(te), _ptr(tt), kmax,
-                                               _weight_kind(weights), -1 if self_base is None else self_base,
+                                               _weight_kind(weights), _self_base(self_base),
                                                _ptr(qt), _ptr(pred_all), _ptr(sse), _ptr(sae)))
         return pred_all, sse, sae
 
@@ -815,7 +777,7 @@ class Context:
         (kinds 1 and 3: bf16-exact values)."""
         dtype = _tensor_dtype(feat) if dtype is None else dtype
         self._check(self.lib.knn_generate(
-            self.h, feat.data_ptr(), None if labels is None else labels.data_ptr(), row0,
+            self.h, feat.data_ptr(), _opt_ptr(labels), row0,
             feat.shape[0], d, feat.shape[1], dtype, kind, seed, stream_id, num_classes,
             self._stream(stream, feat)))
         # written behind torch's back: every context caching a train tensor that shares bytes with
@@ -968,7 +930,7 @@ class Comm:
         _outputs(q1 - q0, k, pred, dist, idx)
         st = self.lib.knn_predict_train_sharded(
             self.ctx.h, self.h, ctypes.byref(tr), idx_base, ctypes.byref(te), k, num_classes, pred.data_ptr(),
-            None if dist is None else dist.data_ptr(), None if idx is None else idx.data_ptr(),
+            _opt_ptr(dist), _opt_ptr(idx),
             self.ctx._stream(stream, test))
         if st != KNN_OK:
             raise KnnError(st, self.lib.knn_last_error(self.ctx.h).decode())

@@ -102,13 +102,14 @@ struct knn_ctx {
     uint32_t finish_seq = 0;
     int32_t* ctrl_host_dev = nullptr;  // its device address (k_finish writes it)
     bool ctrl_clean = false;  // the status words are zero (the last call ended in k_finish)
-    // k-sweep (knn_sweep_device / knn_sweep): the top-kin lists of the pass, and the host entry
-    // point's device copies of its outputs and query labels; sized once and grown like the others
-    DBuf sw_dist, sw_idx, sw_pred, sw_ql, sw_correct, sw_scores;
+    // list consumers (lists_core / lists_host): the top-kin lists of the pass, and the host entry
+    // points' device copies of pred_all, the queries' side input (labels or targets), the per-k
+    // accumulators (correct | sse, sae) and the scores; sized once and grown like the others
+    DBuf sw_dist, sw_idx, sw_pred, sw_qside, sw_acc, sw_scores;
     // regression (knn_regress_*): the error partials [2][kmax][chunks], the all-zero label array
     // the vote-less pass runs with (the caller has no classes), and the host entry point's device
-    // copies of the train / query targets and of sse | sae
-    DBuf rg_part, rg_zero, rg_targets, rg_qt, rg_sums;
+    // copy of the train targets
+    DBuf rg_part, rg_zero, rg_targets;
     DBuf arrive;              // k_direct_rows' fused merge: per query group, segments finished
     bool arrive_clean = false;  // arrive is all zero (the last launch ran to completion)
     bool merge_kernel = false;  // study switch KNN_DIRECT_MERGE_KERNEL=1: k_direct_rows' segments via k_merge_vote
@@ -159,7 +160,8 @@ knn_status fail(knn_ctx* c, knn_status s, const char* fmt, ...) {
                         #expr, hipGetErrorString(e__), __FILE__, __LINE__);                    \
     } while (0)
 
-// HIP_OR_FAIL inside knn_predict's enqueue phase: drain and invalidate first (abort_call)
+// HIP_OR_FAIL inside a host-buffer call's enqueue phase (knn_predict, lists_host): drain and
+// invalidate first (abort_call)
 #define HIP_OR_ABORT(expr)                                                                     \
     do {                                                                                        \
         hipError_t e__ = (expr);                                                                \
@@ -930,8 +932,8 @@ void knn_destroy(knn_ctx* c) {
     (void)hipSetDevice(c->device);
     for (DBuf* b : {&c->tnorm, &c->tnp, &c->qnorm, &c->gthr, &c->cnt, &c->cand,
                     &c->fb_list, &c->ctrl, &c->scratch, &c->split_t, &c->split_q, &c->pad_t, &c->seg_rec, &c->arrive, &c->tmax, &c->tsmax, &c->qstat, &c->tblk, &c->tctrl, &c->cursor, &c->lshare, &c->h_train, &c->h_labels, &c->h_test, &c->h_pred,
-                    &c->h_dist, &c->h_idx, &c->sw_dist, &c->sw_idx, &c->sw_pred, &c->sw_ql, &c->sw_correct, &c->sw_scores,
-                    &c->rg_part, &c->rg_zero, &c->rg_targets, &c->rg_qt, &c->rg_sums})
+                    &c->h_dist, &c->h_idx, &c->sw_dist, &c->sw_idx, &c->sw_pred, &c->sw_qside, &c->sw_acc, &c->sw_scores,
+                    &c->rg_part, &c->rg_zero, &c->rg_targets})
         b->release();
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; i++) {
@@ -1101,12 +1103,27 @@ knn_status predict_core(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te
     return KNN_OK;
 }
 
+// the row stride of a host-buffer call's device copies: rows padded to 16 B
+int device_ld(int d, int dtype) {
+    const int per16 = 16 / elem_size(dtype);
+    return (d + per16 - 1) / per16 * per16;
+}
+
+// The device call's checks on the shapes a host-buffer call will see (batches of B queries, rows
+// ldd apart), before anything is enqueued: no early return may leave a copy to or from the
+// caller's buffers in flight.  (The entry has checked the caller's label pointer already.)
+knn_status validate_host_shapes(knn_ctx* c, const knn_dataset* tr, int64_t B, int ldd, int32_t k, int32_t C,
+                                const QueryOut& out, bool need_pred) {
+    const knn_dataset vtr{(const void*)(uintptr_t)256, (const int32_t*)(uintptr_t)256, tr->n, tr->d, ldd, tr->dtype};
+    const knn_dataset vq{(const void*)(uintptr_t)256, nullptr, B, tr->d, ldd, tr->dtype};
+    return validate_call(c, &vtr, &vq, k, C, out, false, need_pred);
+}
+
 // The train set of a host-buffer call on the device: reused across calls when the context
 // caches train uploads (KNN_OPT_CACHE_TRAIN) and the buffer, shape and generation match.
 knn_status train_device(knn_ctx* c, const knn_dataset* tr, hipStream_t st, knn_dataset* dtr) {
     const size_t es = (size_t)elem_size(tr->dtype);
-    const int per16 = (int)(16 / es);
-    const int ldd = (tr->d + per16 - 1) / per16 * per16;  // device rows padded to 16 B
+    const int ldd = device_ld(tr->d, tr->dtype);
     auto& tc = c->tcache;
     const bool hit = c->cache_train && tc.valid && tc.feat == tr->feat && tc.labels == tr->labels && tc.n == tr->n &&
                      tc.d == tr->d && tc.ld == tr->ld && tc.dtype == tr->dtype && tc.gen == c->generation;
@@ -1117,7 +1134,7 @@ knn_status train_device(knn_ctx* c, const knn_dataset* tr, hipStream_t st, knn_d
         HIP_OR_FAIL(c, c->h_labels.ensure(sizeof(int32_t) * tr->n));
         HIP_OR_FAIL(c, hipMemcpy2DAsync(c->h_train.p, es * ldd, tr->feat, es * tr->ld, es * tr->d, tr->n,
                                         hipMemcpyHostToDevice, st));
-        // (knn_regress_sweep has no classes: labels == NULL, and the pass runs with zeros)
+        // (lists_host for regression has no classes: labels == NULL, and the pass runs with zeros)
         if (tr->labels)
             HIP_OR_FAIL(c, hipMemcpyAsync(c->h_labels.p, tr->labels, sizeof(int32_t) * tr->n, hipMemcpyHostToDevice, st));
         else
@@ -1185,31 +1202,109 @@ knn_status knn_merge_vote_append(knn_ctx* c, int32_t nsrc, int64_t nq, int32_t k
     return finish_call(c, st);
 }
 
+// ---------------------------------------------------------------------------------
+// Consumers of the exact top-k lists: the k-sweep's vote (k_vote_sweep), the weighted vote
+// (k_vote_weighted) and regression (k_regress_sweep; knn_amd.h "Regression").  A consumer is a
+// ListConsumer, its texts and its *_enqueue function; the argument checks (list_check), the
+// consumer alone on the caller's lists (lists_vote), the pass loop over device datasets
+// (lists_core) and the batch loop over host arrays (lists_host) are shared.
+// ---------------------------------------------------------------------------------
 namespace {
 
-// what the sweep entry points share: the outputs asked for and the list length
-knn_status sweep_check(knn_ctx* c, int32_t kmax, int64_t self_base, const void* qlabels, const void* pred_all,
-                       const void* correct) {
-    if (kmax < 1) return fail(c, KNN_EINVAL, "sweep: kmax=%d must be >= 1", kmax);
-    if (!qlabels && !pred_all && !correct)
-        return fail(c, KNN_EINVAL, "sweep: query labels, pred_all and correct are all NULL");
-    if (correct && !qlabels) return fail(c, KNN_EINVAL, "sweep: correct needs the query labels");
+enum ConsumerKind { VOTE_SWEEP = 0, VOTE_WEIGHTED = 1, REGRESS = 2 };
+
+// What a call asks of its consumer.  Per query every element is 4 bytes wide (int32 labels and
+// predictions for the class votes, float targets and predictions for regression) and every
+// accumulator element 8 (int64 counts, double sums): the shared loops offset, stage and copy them
+// without knowing which.
+struct ListConsumer {
+    ConsumerKind kind;
+    int weights;           // knn_weight (VOTE_WEIGHTED, REGRESS)
+    int row0;              // the first prefix row written: pred_all then points at that row
+    const float* targets;  // REGRESS: the train targets
+    const void* qside;     // the queries' labels or, REGRESS, targets [nq]
+    void* pred_all;        // [kmax - row0] rows, pred_stride apart
+    int64_t pred_stride;
+    void* acc[2];          // per-k accumulators [kmax]: correct | sse, sae
+    float* scores;         // VOTE_WEIGHTED: per-class scores [nq][C]
+    float* dist_out;       // the lists the caller asked for, [nq][kmax]
+    int32_t* idx_out;
+};
+
+ListConsumer sweep_consumer(const int32_t* qlabels, int32_t* pred_all, int64_t pred_stride, int64_t* correct,
+                            float* dist_out, int32_t* idx_out) {
+    return {VOTE_SWEEP, 0, 0, nullptr, qlabels, pred_all, pred_stride, {correct, nullptr}, nullptr, dist_out, idx_out};
+}
+ListConsumer weighted_consumer(int weights, int row0, const int32_t* qlabels, int32_t* pred_all, int64_t pred_stride,
+                               int64_t* correct, float* scores, float* dist_out, int32_t* idx_out) {
+    return {VOTE_WEIGHTED, weights, row0, nullptr, qlabels, pred_all, pred_stride, {correct, nullptr}, scores,
+            dist_out, idx_out};
+}
+ListConsumer regress_consumer(int weights, int row0, const float* targets, const float* qtargets, float* pred_all,
+                              int64_t pred_stride, double* sse, double* sae, float* dist_out, int32_t* idx_out) {
+    return {REGRESS, weights, row0, targets, qtargets, pred_all, pred_stride, {sse, sae}, nullptr, dist_out, idx_out};
+}
+
+// the consumers' error texts, by kind.  bad_lists is lists_vote's printf format for (nq, kin,
+// stride, C); regression has no classes and prints no C.
+const struct {
+    const char *prefix, *none_asked, *needs_side, *bad_lists, *null_lists;
+} kConsumerText[] = {
+    {"sweep", "query labels, pred_all and correct are all NULL", "correct needs the query labels",
+     "vote sweep: bad nq=%lld kin=%d idx_stride=%lld C=%d", "vote sweep: d_idx / d_train_labels is NULL"},
+    {"weighted vote", "query labels, pred_all, correct and scores are all NULL", "correct needs the query labels",
+     "weighted vote: bad nq=%lld kin=%d stride=%lld C=%d", "weighted vote: d_idx / d_dist / d_train_labels is NULL"},
+    {"regression", "pred_all, sse and sae are all NULL", "sse / sae need the query targets",
+     "regression: bad nq=%lld kin=%d stride=%lld", "regression: d_idx / d_dist / d_train_targets is NULL"},
+};
+
+// what every entry point of a consumer checks: the kind of weights, the outputs asked for (the
+// query labels count as one: a class vote's caller may want the status alone; regression's query
+// targets do not) and the list length
+knn_status list_check(knn_ctx* c, const ListConsumer& lc, int32_t kmax, int64_t self_base) {
+    const char* p = kConsumerText[lc.kind].prefix;
+    if (lc.kind != VOTE_SWEEP) {
+        if (lc.weights != KNN_W_UNIFORM && lc.weights != KNN_W_INV_DIST && lc.weights != KNN_W_INV_SQDIST)
+            return fail(c, KNN_EINVAL, "%s: unknown weights=%d", p, lc.weights);
+        if (lc.weights == KNN_W_INV_SQDIST && c->metric != KNN_METRIC_SQEUCLIDEAN)
+            return fail(c, KNN_EINVAL, "%s: KNN_W_INV_SQDIST needs the squared Euclidean metric (metric=%d)", p,
+                        c->metric);
+    }
+    if (kmax < 1) return fail(c, KNN_EINVAL, "%s: kmax=%d must be >= 1", p, kmax);
+    if (!(lc.kind != REGRESS && lc.qside) && !lc.pred_all && !lc.acc[0] && !lc.acc[1] && !lc.scores)
+        return fail(c, KNN_EINVAL, "%s: %s", p, kConsumerText[lc.kind].none_asked);
+    if ((lc.acc[0] || lc.acc[1]) && !lc.qside) return fail(c, KNN_EINVAL, "%s: %s", p, kConsumerText[lc.kind].needs_side);
     if (self_base >= 0 && kmax + 1 > 1024)
-        return fail(c, KNN_EINVAL, "sweep: kmax=%d + the self row exceeds the supported maximum 1024", kmax);
+        return fail(c, KNN_EINVAL, "%s: kmax=%d + the self row exceeds the supported maximum 1024", p, kmax);
     return KNN_OK;
 }
 
+// The kernels' weight kind.  A non-Euclidean metric's distance is no square: KNN_W_INV_DIST is
+// 1.0f / D there, the kernels' inverse-of-the-value kind (list_check refused KNN_W_INV_SQDIST).
+int kernel_weights(const knn_ctx* c, int weights) {
+    return (c->metric != KNN_METRIC_SQEUCLIDEAN && weights == KNN_W_INV_DIST) ? KNN_VOTE_W_INV_SQDIST : weights;
+}
+
+// the lists a consumer runs on, in device memory: the first kin entries of rows stride apart;
+// check_dist: they are the caller's, not a pass's (a NaN or negative distance is an error)
+struct Lists {
+    const int32_t* idx;
+    const float* dist;
+    int64_t nq, stride;
+    int kin;
+    bool check_dist;
+};
+
 // k_vote_sweep on lists in device memory, enqueued on st (no synchronisation)
-knn_status vote_sweep_enqueue(knn_ctx* c, int64_t nq, int kin, int C, const int32_t* idx, int64_t idx_stride,
-                              const int32_t* labels, int64_t self_base, const int32_t* qlabels, int32_t* pred_all,
-                              int64_t pred_stride, int64_t* correct, const float* dist_in, float* dist_out,
-                              int32_t* idx_out, hipStream_t st) {
+knn_status vote_sweep_enqueue(knn_ctx* c, const ListConsumer& lc, const Lists& L, int C, const int32_t* labels,
+                              int64_t self_base, hipStream_t st) {
     VoteSweepArgs v{};
-    v.idx = idx; v.idx_stride = idx_stride; v.labels = labels;
-    v.nq = nq; v.kin = kin; v.kmax = self_base >= 0 ? kin - 1 : kin; v.C = C; v.self_base = self_base;
-    v.qlabels = qlabels; v.pred_all = pred_all; v.pred_stride = pred_stride;
-    v.correct = reinterpret_cast<unsigned long long*>(correct);
-    v.dist_in = dist_in; v.dist_out = dist_in ? dist_out : nullptr; v.idx_out = idx_out;
+    v.idx = L.idx; v.idx_stride = L.stride; v.labels = labels;
+    v.nq = L.nq; v.kin = L.kin; v.kmax = self_base >= 0 ? L.kin - 1 : L.kin; v.C = C; v.self_base = self_base;
+    v.qlabels = static_cast<const int32_t*>(lc.qside);
+    v.pred_all = static_cast<int32_t*>(lc.pred_all); v.pred_stride = lc.pred_stride;
+    v.correct = static_cast<unsigned long long*>(lc.acc[0]);
+    v.dist_in = L.dist; v.dist_out = L.dist ? lc.dist_out : nullptr; v.idx_out = lc.idx_out;
     v.status = c->ctrl.as<int32_t>();
     stage_begin(c, st, "vote_sweep");
     HIP_OR_FAIL(c, knn_launch_vote_sweep(v, st));
@@ -1217,88 +1312,155 @@ knn_status vote_sweep_enqueue(knn_ctx* c, int64_t nq, int kin, int C, const int3
     return KNN_OK;
 }
 
-// the weighted vote behind a pass (sweep_core): the kind, the first prefix row written (pred_all
-// then points at that row) and the per-class scores [nq][C] (optional)
-struct WeightedVote {
-    int weights;
-    int row0;
-    float* scores;
-};
-
 // k_vote_weighted on lists in device memory, enqueued on st (no synchronisation); scores is
 // zeroed here, ahead of the kernel on the same stream
-knn_status vote_weighted_enqueue(knn_ctx* c, int64_t nq, int kin, int C, const int32_t* idx, const float* dist,
-                                 int64_t stride, const int32_t* labels, const WeightedVote& wv, int64_t self_base,
-                                 const int32_t* qlabels, int32_t* pred_all, int64_t pred_stride, int64_t* correct,
-                                 float* dist_out, int32_t* idx_out, bool check_dist, hipStream_t st) {
+knn_status vote_weighted_enqueue(knn_ctx* c, const ListConsumer& lc, const Lists& L, int C, const int32_t* labels,
+                                 int64_t self_base, hipStream_t st) {
     VoteWeightedArgs v{};
-    v.idx = idx; v.dist = dist; v.stride = stride; v.labels = labels;
-    v.nq = nq; v.kin = kin; v.kmax = self_base >= 0 ? kin - 1 : kin; v.C = C;
-    // a non-Euclidean metric's distance is no square: KNN_W_INV_DIST is 1.0f / D there, the
-    // kernel's inverse-of-the-value kind (weighted_check refused KNN_W_INV_SQDIST)
-    v.weights = (c->metric != KNN_METRIC_SQEUCLIDEAN && wv.weights == KNN_W_INV_DIST) ? KNN_VOTE_W_INV_SQDIST
-                                                                                      : wv.weights;
+    v.idx = L.idx; v.dist = L.dist; v.stride = L.stride; v.labels = labels;
+    v.nq = L.nq; v.kin = L.kin; v.kmax = self_base >= 0 ? L.kin - 1 : L.kin; v.C = C;
+    v.weights = kernel_weights(c, lc.weights);
     v.self_base = self_base;
-    v.qlabels = qlabels; v.pred_all = pred_all; v.pred_stride = pred_stride; v.row0 = wv.row0;
-    v.correct = reinterpret_cast<unsigned long long*>(correct);
-    v.scores = wv.scores; v.dist_out = dist ? dist_out : nullptr; v.idx_out = idx_out;
-    v.check_dist = check_dist ? 1 : 0;
+    v.qlabels = static_cast<const int32_t*>(lc.qside);
+    v.pred_all = static_cast<int32_t*>(lc.pred_all); v.pred_stride = lc.pred_stride; v.row0 = lc.row0;
+    v.correct = static_cast<unsigned long long*>(lc.acc[0]);
+    v.scores = lc.scores; v.dist_out = L.dist ? lc.dist_out : nullptr; v.idx_out = lc.idx_out;
+    v.check_dist = L.check_dist ? 1 : 0;
     v.status = c->ctrl.as<int32_t>();
     stage_begin(c, st, "vote_weighted");
-    if (wv.scores && nq > 0) HIP_OR_FAIL(c, hipMemsetAsync(wv.scores, 0, sizeof(float) * (size_t)nq * (size_t)C, st));
+    if (lc.scores && L.nq > 0) HIP_OR_FAIL(c, hipMemsetAsync(lc.scores, 0, sizeof(float) * (size_t)L.nq * (size_t)C, st));
     HIP_OR_FAIL(c, knn_launch_vote_weighted(v, st));
     stage_end(c, st);
     return KNN_OK;
 }
 
-// The sweep over device datasets: one top-kin pass with no vote (QueryOut.pred == NULL) into the
-// context's list workspace, k_vote_sweep behind it on the same stream, one finish_call.  (The
-// GEMM path runs more than c->ws_queries queries in passes, like predict_core; each pass ends
-// in its own finish_call and adds into d_correct.)  d_pred_all rows are pred_stride apart.
-// wv != NULL: the pass keeps its distances whether or not the caller asked for them, and
-// k_vote_weighted votes instead (knn_sweep_weighted_device / knn_predict_weighted_device).
-knn_status sweep_core(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
-                      int64_t self_base, const int32_t* d_qlabels, int32_t* d_pred_all, int64_t pred_stride,
-                      int64_t* d_correct, float* d_dist, int32_t* d_idx, hipStream_t st,
-                      const WeightedVote* wv = nullptr) {
+// k_regress_sweep (+ k_regress_reduce, which adds into sse / sae) on lists in device memory,
+// enqueued on st (no synchronisation)
+knn_status regress_enqueue(knn_ctx* c, const ListConsumer& lc, const Lists& L, int64_t self_base, hipStream_t st) {
+    RegressArgs v{};
+    v.idx = L.idx; v.dist = L.dist; v.stride = L.stride; v.targets = lc.targets;
+    v.nq = L.nq; v.kin = L.kin; v.kmax = self_base >= 0 ? L.kin - 1 : L.kin;
+    v.weights = kernel_weights(c, lc.weights);
+    v.self_base = self_base;
+    v.qtargets = static_cast<const float*>(lc.qside);
+    v.pred_all = static_cast<float*>(lc.pred_all); v.pred_stride = lc.pred_stride; v.row0 = lc.row0;
+    v.dist_out = L.dist ? lc.dist_out : nullptr; v.idx_out = lc.idx_out;
+    v.check_dist = L.check_dist ? 1 : 0;
+    v.status = c->ctrl.as<int32_t>();
+    double *sse = static_cast<double*>(lc.acc[0]), *sae = static_cast<double*>(lc.acc[1]);
+    if ((sse || sae) && L.nq > 0) {
+        HIP_OR_FAIL(c, c->rg_part.ensure(sizeof(double) * 2 * (size_t)v.kmax * (size_t)knn_regress_chunks(L.nq)));
+        v.part = c->rg_part.as<double>();
+    }
+    stage_begin(c, st, "regress");
+    HIP_OR_FAIL(c, knn_launch_regress(v, st));
+    if (v.part) HIP_OR_FAIL(c, knn_launch_regress_reduce(v.part, L.nq, v.kmax, lc.row0, sse, sae, st));
+    stage_end(c, st);
+    return KNN_OK;
+}
+
+knn_status consumer_enqueue(knn_ctx* c, const ListConsumer& lc, const Lists& L, int C, const int32_t* labels,
+                            int64_t self_base, hipStream_t st) {
+    switch (lc.kind) {
+        case VOTE_SWEEP: return vote_sweep_enqueue(c, lc, L, C, labels, self_base, st);
+        case VOTE_WEIGHTED: return vote_weighted_enqueue(c, lc, L, C, labels, self_base, st);
+        default: return regress_enqueue(c, lc, L, self_base, st);
+    }
+}
+
+hipError_t zero_accumulators(const ListConsumer& lc, int32_t kmax, hipStream_t st) {
+    for (void* a : lc.acc)
+        if (a)
+            if (hipError_t e = hipMemsetAsync(a, 0, 8 * (size_t)kmax, st)) return e;
+    return hipSuccess;
+}
+
+// knn_vote_sweep_device, knn_vote_weighted_device and knn_regress_vote_device: the consumer alone
+// on the caller's lists.  inputs: every array the kind reads is there.
+knn_status lists_vote(knn_ctx* c, const ListConsumer& lc, const Lists& L, int32_t C, const int32_t* labels,
+                      int64_t self_base, bool inputs, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    c->stages.clear();
+    const int32_t kmax = self_base >= 0 ? L.kin - 1 : L.kin;
+    if (L.nq < 0 || L.kin < 1 || L.kin > 1024 || L.stride < L.kin || C < 1 || C > 16384)
+        return fail(c, KNN_EINVAL, kConsumerText[lc.kind].bad_lists, (long long)L.nq, L.kin, (long long)L.stride, C);
     knn_status s;
+    if ((s = list_check(c, lc, kmax, self_base)) != KNN_OK) return s;
+    if (L.nq > 0 && !inputs) return fail(c, KNN_EINVAL, "%s", kConsumerText[lc.kind].null_lists);
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    HIP_OR_FAIL(c, zero_accumulators(lc, kmax, st));
+    if ((s = consumer_enqueue(c, lc, L, C, labels, self_base, st)) != KNN_OK) return s;
+    return finish_call(c, st);
+}
+
+// The pass loop of every consumer over device datasets: one top-kin pass with no vote
+// (QueryOut.pred == NULL) into the context's list workspace, the consumer behind it on the same
+// stream, one finish_call.  The GEMM path runs more than c->ws_queries queries in passes, like
+// predict_core; each pass ends in its own finish_call and adds into the accumulators, which are
+// zeroed here first unless the caller has (lists_host, batch after batch).  Regression has no
+// classes: its callers pass C = 1, and the pass runs on a context-owned all-zero label array.
+// Its GEMM passes are cut at multiples of the reduce's span, so that sse / sae are the bits of a
+// single pass.
+knn_status lists_core(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
+                      int64_t self_base, const ListConsumer& lc, bool zero_acc, hipStream_t st) {
+    knn_status s;
+    const bool regress = lc.kind == REGRESS;
     const int kin = kmax + (self_base >= 0 ? 1 : 0);
+    knn_dataset trv;  // regression's train view
+    if (regress) {
+        if (!tr) return fail(c, KNN_EINVAL, "train dataset is NULL");
+        trv = *tr;
+        trv.labels = static_cast<const int32_t*>(tr->feat);  // (for the checks; the zero array replaces it below)
+        tr = &trv;
+    }
     QueryOut out{nullptr, nullptr, nullptr, nullptr, kin, 0};
     if ((s = validate_call(c, tr, te, kin, C, out, false, false)) != KNN_OK) return s;
     if (self_base >= 0 && self_base + te->n > tr->n)
-        return fail(c, KNN_EINVAL, "sweep: self rows [%lld, %lld) outside the %lld train rows", (long long)self_base,
-                    (long long)(self_base + te->n), (long long)tr->n);
+        return fail(c, KNN_EINVAL, "%s: self rows [%lld, %lld) outside the %lld train rows",
+                    regress ? "regression" : "sweep", (long long)self_base, (long long)(self_base + te->n),
+                    (long long)tr->n);
+    if (regress && te->n > 0 && !lc.targets) return fail(c, KNN_EINVAL, "regression: the train targets are NULL");
     HIP_OR_FAIL(c, hipSetDevice(c->device));
-    if (d_correct) HIP_OR_FAIL(c, hipMemsetAsync(d_correct, 0, sizeof(int64_t) * (size_t)kmax, st));
+    if (zero_acc) HIP_OR_FAIL(c, zero_accumulators(lc, kmax, st));
     if (te->n == 0) {
         HIP_OR_FAIL(c, hipStreamSynchronize(st));
         return KNN_OK;
     }
+    if (regress) {
+        const size_t need = sizeof(int32_t) * (size_t)std::max<int64_t>(tr->n, 1);
+        if (need > c->rg_zero.bytes || !c->rg_zero.p) {
+            HIP_OR_FAIL(c, c->rg_zero.ensure(need));
+            HIP_OR_FAIL(c, hipMemsetAsync(c->rg_zero.p, 0, need, st));
+        }
+        trv.labels = c->rg_zero.as<int32_t>();
+    }
     const int algo = choose_algo(c, tr->n, te->n, tr->d, kin, tr->dtype);
     const bool gemm = is_gemm(algo);
-    const int64_t pass = gemm ? std::max<int64_t>(1, c->ws_queries) : te->n;
+    const int64_t grain = regress ? (int64_t)KNN_REGRESS_CHUNK * KNN_REGRESS_SPAN : 1;
+    int64_t pass = gemm ? std::max<int64_t>(1, c->ws_queries) : te->n;
+    if (gemm && pass >= grain) pass -= pass % grain;
     const int64_t rows = std::min(pass, te->n);
+    // (the weighted kinds read the distances whether or not the caller asked for them)
+    const bool keep_dist = lc.kind != VOTE_SWEEP || lc.dist_out;
     HIP_OR_FAIL(c, c->sw_idx.ensure(sizeof(int32_t) * (size_t)rows * kin));
-    if (d_dist || wv) HIP_OR_FAIL(c, c->sw_dist.ensure(sizeof(float) * (size_t)rows * kin));
+    if (keep_dist) HIP_OR_FAIL(c, c->sw_dist.ensure(sizeof(float) * (size_t)rows * kin));
     out.idx = c->sw_idx.as<int32_t>();
-    out.dist = (d_dist || wv) ? c->sw_dist.as<float>() : nullptr;
+    out.dist = keep_dist ? c->sw_dist.as<float>() : nullptr;
     for (int64_t q0 = 0; q0 < te->n; q0 += pass) {
         const int64_t n = std::min(pass, te->n - q0);
         const knn_dataset tq = offset_rows(*te, q0, n);
         if ((s = predict_enqueue(c, tr, &tq, kin, C, out, st, algo, nullptr)) == KNN_OK) {
-            if (wv) {
-                const WeightedVote w{wv->weights, wv->row0, wv->scores ? wv->scores + q0 * C : nullptr};
-                s = vote_weighted_enqueue(c, n, kin, C, out.idx, out.dist, kin, tr->labels, w,
-                                          self_base >= 0 ? self_base + q0 : -1, d_qlabels ? d_qlabels + q0 : nullptr,
-                                          d_pred_all ? d_pred_all + q0 : nullptr, pred_stride, d_correct,
-                                          d_dist ? d_dist + q0 * kmax : nullptr, d_idx ? d_idx + q0 * kmax : nullptr,
-                                          false, st);
-            } else {
-                s = vote_sweep_enqueue(c, n, kin, C, out.idx, kin, tr->labels, self_base >= 0 ? self_base + q0 : -1,
-                                       d_qlabels ? d_qlabels + q0 : nullptr, d_pred_all ? d_pred_all + q0 : nullptr,
-                                       pred_stride, d_correct, out.dist, d_dist ? d_dist + q0 * kmax : nullptr,
-                                       d_idx ? d_idx + q0 * kmax : nullptr, st);
-            }
+            ListConsumer pc = lc;  // the consumer's view of the queries from q0 on
+            if (pc.qside) pc.qside = static_cast<const char*>(pc.qside) + 4 * q0;
+            if (pc.pred_all) pc.pred_all = static_cast<char*>(pc.pred_all) + 4 * q0;
+            if (pc.scores) pc.scores += q0 * C;
+            if (pc.dist_out) pc.dist_out += q0 * kmax;
+            if (pc.idx_out) pc.idx_out += q0 * kmax;
+            s = consumer_enqueue(c, pc, Lists{out.idx, out.dist, n, kin, kin, false}, C, tr->labels,
+                                 self_base >= 0 ? self_base + q0 : -1, st);
         }
         if (s != KNN_OK || (s = finish_call(c, st)) != KNN_OK) {
             if (s != KNN_EINVAL && s != KNN_ERANGE) c->tprep.valid = c->tpad.valid = false;  // a HIP failure: the operands may be partial
@@ -1306,6 +1468,116 @@ knn_status sweep_core(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, 
         }
         pass_stats(c, c->ctrl_host, gemm);
     }
+    return KNN_OK;
+}
+
+// knn_sweep_device, knn_sweep_weighted_device, knn_predict_weighted_device, knn_regress_sweep_device
+// and knn_regress_device: the checks, then the pass loop on the caller's stream
+knn_status lists_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
+                        int64_t self_base, const ListConsumer& lc, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    knn_status s;
+    if ((s = list_check(c, lc, kmax, self_base)) != KNN_OK) return s;
+    reset_stats(c);
+    return lists_core(c, tr, te, kmax, C, self_base, lc, true, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+// knn_sweep, knn_sweep_weighted and knn_regress_sweep: lc holds the caller's HOST arrays.  One
+// batch after another (not pipelined): each is uploaded with its side input, run through
+// lists_core, and its pred_all rows and scores are copied back.  The accumulators stay on the
+// device, added into batch after batch, and come back once at the end.
+knn_status lists_host(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
+                      int64_t self_base, const ListConsumer& lc) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    knn_status s;
+    const bool regress = lc.kind == REGRESS;
+    if ((s = check_dataset(c, tr, "train", !regress)) != KNN_OK) return s;
+    if ((s = check_dataset(c, te, "test", false)) != KNN_OK) return s;
+    if ((s = list_check(c, lc, kmax, self_base)) != KNN_OK) return s;
+    if (tr->d != te->d) return fail(c, KNN_EINVAL, "feature count mismatch: train d=%d test d=%d", tr->d, te->d);
+    if (tr->dtype != te->dtype) return fail(c, KNN_EINVAL, "train and test dtypes differ");
+    const int64_t nq = te->n;
+    const int kin = kmax + (self_base >= 0 ? 1 : 0);
+    if (kin > tr->n) return fail(c, KNN_EINVAL, "k=%d outside [1, n_train=%lld]", kin, (long long)tr->n);
+    if (self_base >= 0 && self_base + nq > tr->n)
+        return fail(c, KNN_EINVAL, "%s: self rows [%lld, %lld) outside the %lld train rows",
+                    regress ? "regression" : "sweep", (long long)self_base, (long long)(self_base + nq),
+                    (long long)tr->n);
+    if (regress && tr->n > 0 && !lc.targets) return fail(c, KNN_EINVAL, "regression: the train targets are NULL");
+    reset_stats(c);
+    for (void* a : lc.acc)
+        if (a) std::memset(a, 0, 8 * (size_t)kmax);
+    if (nq == 0) return KNN_OK;
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int d = tr->d;
+    const size_t es = (size_t)elem_size(tr->dtype);
+    const int ldd = device_ld(d, tr->dtype);
+    int64_t B = std::min<int64_t>(nq, c->batch_rows);
+    if (regress) {
+        // batches are cut at multiples of the reduce's span: the sums then are the bits
+        // knn_regress_sweep_device gives for all queries
+        const int64_t span = (int64_t)KNN_REGRESS_CHUNK * KNN_REGRESS_SPAN;
+        B = std::min<int64_t>(nq, std::max<int64_t>(span, c->batch_rows - c->batch_rows % span));
+    } else if (lc.scores && C >= 1) {
+        B = std::min<int64_t>(B, std::max<int64_t>(1, ((int64_t)64 << 20) / C));  // a batch's scores stay under 256 MiB
+    }
+    if ((s = validate_host_shapes(c, tr, B, ldd, kin, C, QueryOut{nullptr, nullptr, nullptr, nullptr, kin, 0}, false)) !=
+        KNN_OK)
+        return s;
+    // every error from here on drains the stream (no copy from or to the caller's buffers
+    // outlives the call) and drops the train cache entry (its upload may not have run)
+    auto abort_call = [&](knn_status e) {
+        (void)hipStreamSynchronize(st);
+        c->tcache.valid = false;
+        c->tprep.valid = c->tpad.valid = false;
+        return e;
+    };
+    knn_dataset trn = *tr, dtr;
+    if (regress) trn.labels = nullptr;  // no classes: train_device uploads zeros
+    if ((s = train_device(c, &trn, st, &dtr)) != KNN_OK) return abort_call(s);
+    ListConsumer dc = lc;  // the consumer on the device copies of one batch
+    if (regress) {
+        HIP_OR_ABORT(c->rg_targets.ensure(sizeof(float) * (size_t)tr->n));
+        HIP_OR_ABORT(hipMemcpyAsync(c->rg_targets.p, lc.targets, sizeof(float) * (size_t)tr->n, hipMemcpyHostToDevice, st));
+        dc.targets = c->rg_targets.as<float>();
+    }
+    HIP_OR_ABORT(c->q_slot[0].ensure(es * (size_t)ldd * B));
+    if (lc.pred_all) HIP_OR_ABORT(c->sw_pred.ensure(4 * (size_t)kmax * B));
+    if (lc.qside) HIP_OR_ABORT(c->sw_qside.ensure(4 * (size_t)B));
+    if (lc.scores) HIP_OR_ABORT(c->sw_scores.ensure(sizeof(float) * (size_t)B * (size_t)C));
+    if (lc.acc[0] || lc.acc[1]) {
+        HIP_OR_ABORT(c->sw_acc.ensure(8 * 2 * (size_t)kmax));
+        HIP_OR_ABORT(hipMemsetAsync(c->sw_acc.p, 0, 8 * 2 * (size_t)kmax, st));
+    }
+    dc.pred_all = lc.pred_all ? c->sw_pred.p : nullptr;
+    dc.qside = lc.qside ? c->sw_qside.p : nullptr;
+    dc.scores = lc.scores ? c->sw_scores.as<float>() : nullptr;
+    for (int i = 0; i < 2; i++) dc.acc[i] = lc.acc[i] ? c->sw_acc.as<char>() + 8 * (size_t)kmax * i : nullptr;
+    for (int64_t q0 = 0; q0 < nq; q0 += B) {
+        const int64_t n = std::min(B, nq - q0);
+        const unsigned char* src = (const unsigned char*)te->feat + es * (size_t)q0 * (size_t)te->ld;
+        HIP_OR_ABORT(hipMemcpy2DAsync(c->q_slot[0].p, es * ldd, src, es * te->ld, es * d, n, hipMemcpyHostToDevice, st));
+        if (lc.qside)
+            HIP_OR_ABORT(hipMemcpyAsync(c->sw_qside.p, static_cast<const char*>(lc.qside) + 4 * q0, 4 * (size_t)n,
+                                        hipMemcpyHostToDevice, st));
+        c->stats[7] += (int64_t)(es * d * n);
+        const knn_dataset dq{c->q_slot[0].p, nullptr, n, d, ldd, te->dtype};
+        dc.pred_stride = n;
+        if ((s = lists_core(c, &dtr, &dq, kmax, C, self_base >= 0 ? self_base + q0 : -1, dc, false, st)) != KNN_OK)
+            return abort_call(s);
+        // (synchronous copies on the null stream: ordered after the context's blocking stream)
+        if (lc.pred_all)
+            HIP_OR_ABORT(hipMemcpy2D(static_cast<char*>(lc.pred_all) + 4 * q0, 4 * (size_t)nq, c->sw_pred.p, 4 * (size_t)n,
+                                     4 * (size_t)n, kmax, hipMemcpyDeviceToHost));
+        if (lc.scores)
+            HIP_OR_ABORT(hipMemcpy(lc.scores + (size_t)q0 * (size_t)C, c->sw_scores.p, sizeof(float) * (size_t)n * (size_t)C,
+                                   hipMemcpyDeviceToHost));
+    }
+    for (int i = 0; i < 2; i++)
+        if (lc.acc[i]) HIP_OR_ABORT(hipMemcpy(lc.acc[i], dc.acc[i], 8 * (size_t)kmax, hipMemcpyDeviceToHost));
     return KNN_OK;
 }
 
@@ -1317,480 +1589,100 @@ knn_status knn_vote_sweep_device(knn_ctx* c, int64_t nq, int32_t kin, int32_t C,
                                  int64_t idx_stride, const int32_t* d_train_labels, int64_t self_base,
                                  const int32_t* d_query_labels, int32_t* d_pred_all, int64_t* d_correct,
                                  void* hip_stream) {
-    if (!c) return KNN_EINVAL;
-    c->err.clear();
-    c->stages.clear();
-    const int32_t kmax = self_base >= 0 ? kin - 1 : kin;
-    if (nq < 0 || kin < 1 || kin > 1024 || idx_stride < kin || C < 1 || C > 16384)
-        return fail(c, KNN_EINVAL, "vote sweep: bad nq=%lld kin=%d idx_stride=%lld C=%d", (long long)nq, kin,
-                    (long long)idx_stride, C);
-    knn_status s;
-    if ((s = sweep_check(c, kmax, self_base, d_query_labels, d_pred_all, d_correct)) != KNN_OK) return s;
-    if (nq > 0 && (!d_idx || !d_train_labels)) return fail(c, KNN_EINVAL, "vote sweep: d_idx / d_train_labels is NULL");
-    HIP_OR_FAIL(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    HIP_OR_FAIL(c, reset_ctrl(c, st));
-    if (d_correct) HIP_OR_FAIL(c, hipMemsetAsync(d_correct, 0, sizeof(int64_t) * (size_t)kmax, st));
-    if ((s = vote_sweep_enqueue(c, nq, kin, C, d_idx, idx_stride, d_train_labels, self_base, d_query_labels,
-                                d_pred_all, nq, d_correct, nullptr, nullptr, nullptr, st)) != KNN_OK)
-        return s;
-    return finish_call(c, st);
+    return lists_vote(c, sweep_consumer(d_query_labels, d_pred_all, nq, d_correct, nullptr, nullptr),
+                      Lists{d_idx, nullptr, nq, idx_stride, kin, true}, C, d_train_labels, self_base,
+                      d_idx && d_train_labels, hip_stream);
 }
 
 knn_status knn_sweep_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
                             int64_t self_base, const int32_t* d_query_labels, int32_t* d_pred_all,
                             int64_t* d_correct, float* d_topk_dist, int32_t* d_topk_idx, void* hip_stream) {
-    if (!c) return KNN_EINVAL;
-    c->err.clear();
-    knn_status s;
-    if ((s = sweep_check(c, kmax, self_base, d_query_labels, d_pred_all, d_correct)) != KNN_OK) return s;
-    reset_stats(c);
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    return sweep_core(c, tr, te, kmax, C, self_base, d_query_labels, d_pred_all, te ? te->n : 0, d_correct,
-                      d_topk_dist, d_topk_idx, st);
+    return lists_device(c, tr, te, kmax, C, self_base,
+                        sweep_consumer(d_query_labels, d_pred_all, te ? te->n : 0, d_correct, d_topk_dist, d_topk_idx),
+                        hip_stream);
 }
-
-}  // extern "C"
-
-namespace {
-
-// what the weighted entry points share: the kind, the outputs asked for and the list length
-knn_status weighted_check(knn_ctx* c, int32_t kmax, int32_t weights, int64_t self_base, const void* qlabels,
-                          const void* pred_all, const void* correct, const void* scores) {
-    if (weights != KNN_W_UNIFORM && weights != KNN_W_INV_DIST && weights != KNN_W_INV_SQDIST)
-        return fail(c, KNN_EINVAL, "weighted vote: unknown weights=%d", weights);
-    if (weights == KNN_W_INV_SQDIST && c->metric != KNN_METRIC_SQEUCLIDEAN)
-        return fail(c, KNN_EINVAL, "weighted vote: KNN_W_INV_SQDIST needs the squared Euclidean metric (metric=%d)",
-                    c->metric);
-    if (kmax < 1) return fail(c, KNN_EINVAL, "weighted vote: kmax=%d must be >= 1", kmax);
-    if (!qlabels && !pred_all && !correct && !scores)
-        return fail(c, KNN_EINVAL, "weighted vote: query labels, pred_all, correct and scores are all NULL");
-    if (correct && !qlabels) return fail(c, KNN_EINVAL, "weighted vote: correct needs the query labels");
-    if (self_base >= 0 && kmax + 1 > 1024)
-        return fail(c, KNN_EINVAL, "weighted vote: kmax=%d + the self row exceeds the supported maximum 1024", kmax);
-    return KNN_OK;
-}
-
-// knn_sweep and knn_sweep_weighted (wv != NULL: out_scores [nq][C] optional)
-knn_status sweep_host(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
-                      int64_t self_base, const int32_t* query_labels, int32_t* out_pred_all, int64_t* out_correct,
-                      const WeightedVote* wv, float* out_scores) {
-    knn_status s;
-    if ((s = check_dataset(c, tr, "train", true)) != KNN_OK) return s;
-    if ((s = check_dataset(c, te, "test", false)) != KNN_OK) return s;
-    if (wv)
-        s = weighted_check(c, kmax, wv->weights, self_base, query_labels, out_pred_all, out_correct, out_scores);
-    else
-        s = sweep_check(c, kmax, self_base, query_labels, out_pred_all, out_correct);
-    if (s != KNN_OK) return s;
-    if (tr->d != te->d) return fail(c, KNN_EINVAL, "feature count mismatch: train d=%d test d=%d", tr->d, te->d);
-    if (tr->dtype != te->dtype) return fail(c, KNN_EINVAL, "train and test dtypes differ");
-    const int64_t nq = te->n;
-    const int kin = kmax + (self_base >= 0 ? 1 : 0);
-    if (kin > tr->n) return fail(c, KNN_EINVAL, "k=%d outside [1, n_train=%lld]", kin, (long long)tr->n);
-    if (self_base >= 0 && self_base + nq > tr->n)
-        return fail(c, KNN_EINVAL, "sweep: self rows [%lld, %lld) outside the %lld train rows", (long long)self_base,
-                    (long long)(self_base + nq), (long long)tr->n);
-    reset_stats(c);
-    if (out_correct) std::memset(out_correct, 0, sizeof(int64_t) * (size_t)kmax);
-    if (nq == 0) return KNN_OK;
-    HIP_OR_FAIL(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const int d = tr->d;
-    const size_t es = (size_t)elem_size(tr->dtype);
-    const int ldd = (int)((d + (int)(16 / es) - 1) / (int)(16 / es) * (int)(16 / es));  // device rows padded to 16 B
-    int64_t B = std::min<int64_t>(nq, c->batch_rows);
-    // (the device copy of a batch's scores stays under 256 MiB)
-    if (out_scores && C >= 1) B = std::min<int64_t>(B, std::max<int64_t>(1, ((int64_t)64 << 20) / C));
-    {
-        // the device call's checks on the shapes it will see, before anything is enqueued
-        const knn_dataset vtr{(const void*)(uintptr_t)256, tr->labels, tr->n, d, ldd, tr->dtype};
-        const knn_dataset vq{(const void*)(uintptr_t)256, nullptr, B, d, ldd, te->dtype};
-        const QueryOut vo{nullptr, nullptr, nullptr, nullptr, kin, 0};
-        if ((s = validate_call(c, &vtr, &vq, kin, C, vo, false, false)) != KNN_OK) return s;
-    }
-    // every error from here on drains the stream (no copy from or to the caller's buffers
-    // outlives the call) and drops the train cache entry (its upload may not have run)
-    auto abort_call = [&](knn_status e) {
-        (void)hipStreamSynchronize(st);
-        c->tcache.valid = false;
-        c->tprep.valid = c->tpad.valid = false;
-        return e;
-    };
-    knn_dataset dtr;
-    if ((s = train_device(c, tr, st, &dtr)) != KNN_OK) return abort_call(s);
-    HIP_OR_ABORT(c->q_slot[0].ensure(es * (size_t)ldd * B));
-    if (out_pred_all) HIP_OR_ABORT(c->sw_pred.ensure(sizeof(int32_t) * (size_t)kmax * B));
-    if (query_labels) HIP_OR_ABORT(c->sw_ql.ensure(sizeof(int32_t) * (size_t)B));
-    if (out_correct) HIP_OR_ABORT(c->sw_correct.ensure(sizeof(int64_t) * (size_t)kmax));
-    if (out_scores) HIP_OR_ABORT(c->sw_scores.ensure(sizeof(float) * (size_t)B * (size_t)C));
-    const WeightedVote wvd{wv ? wv->weights : 0, 0, out_scores ? c->sw_scores.as<float>() : nullptr};
-    std::vector<int64_t> part(out_correct ? kmax : 0);
-    // one batch after another, each uploaded, swept and downloaded before the next starts
-    for (int64_t q0 = 0; q0 < nq; q0 += B) {
-        const int64_t n = std::min(B, nq - q0);
-        const unsigned char* src = (const unsigned char*)te->feat + es * (size_t)q0 * (size_t)te->ld;
-        HIP_OR_ABORT(hipMemcpy2DAsync(c->q_slot[0].p, es * ldd, src, es * te->ld, es * d, n, hipMemcpyHostToDevice, st));
-        if (query_labels)
-            HIP_OR_ABORT(hipMemcpyAsync(c->sw_ql.p, query_labels + q0, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
-        c->stats[7] += (int64_t)(es * d * n);
-        const knn_dataset dq{c->q_slot[0].p, nullptr, n, d, ldd, te->dtype};
-        s = sweep_core(c, &dtr, &dq, kmax, C, self_base >= 0 ? self_base + q0 : -1,
-                       query_labels ? c->sw_ql.as<int32_t>() : nullptr, out_pred_all ? c->sw_pred.as<int32_t>() : nullptr,
-                       n, out_correct ? c->sw_correct.as<int64_t>() : nullptr, nullptr, nullptr, st, wv ? &wvd : nullptr);
-        if (s != KNN_OK) return abort_call(s);
-        // (synchronous copies on the null stream: ordered after the context's blocking stream)
-        if (out_pred_all)
-            HIP_OR_ABORT(hipMemcpy2D(out_pred_all + q0, sizeof(int32_t) * (size_t)nq, c->sw_pred.p, sizeof(int32_t) * (size_t)n,
-                                     sizeof(int32_t) * (size_t)n, kmax, hipMemcpyDeviceToHost));
-        if (out_correct) {
-            HIP_OR_ABORT(hipMemcpy(part.data(), c->sw_correct.p, sizeof(int64_t) * (size_t)kmax, hipMemcpyDeviceToHost));
-            for (int i = 0; i < kmax; i++) out_correct[i] += part[i];
-        }
-        if (out_scores)
-            HIP_OR_ABORT(hipMemcpy(out_scores + (size_t)q0 * (size_t)C, c->sw_scores.p, sizeof(float) * (size_t)n * (size_t)C,
-                                   hipMemcpyDeviceToHost));
-    }
-    return KNN_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 knn_status knn_sweep(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
                      int64_t self_base, const int32_t* query_labels, int32_t* out_pred_all, int64_t* out_correct) {
-    if (!c) return KNN_EINVAL;
-    c->err.clear();
-    return sweep_host(c, tr, te, kmax, C, self_base, query_labels, out_pred_all, out_correct, nullptr, nullptr);
-}
-
-knn_status knn_sweep_weighted(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
-                              int32_t weights, int64_t self_base, const int32_t* query_labels, int32_t* out_pred_all,
-                              int64_t* out_correct, float* out_scores) {
-    if (!c) return KNN_EINVAL;
-    c->err.clear();
-    const WeightedVote wv{weights, 0, nullptr};
-    return sweep_host(c, tr, te, kmax, C, self_base, query_labels, out_pred_all, out_correct, &wv, out_scores);
+    return lists_host(c, tr, te, kmax, C, self_base,
+                      sweep_consumer(query_labels, out_pred_all, 0, out_correct, nullptr, nullptr));
 }
 
 knn_status knn_vote_weighted_device(knn_ctx* c, int64_t nq, int32_t kin, int32_t C, const int32_t* d_idx,
                                     const float* d_dist, int64_t stride, const int32_t* d_train_labels,
                                     int32_t weights, int64_t self_base, const int32_t* d_query_labels,
                                     int32_t* d_pred_all, int64_t* d_correct, float* d_scores, void* hip_stream) {
-    if (!c) return KNN_EINVAL;
-    c->err.clear();
-    c->stages.clear();
-    const int32_t kmax = self_base >= 0 ? kin - 1 : kin;
-    if (nq < 0 || kin < 1 || kin > 1024 || stride < kin || C < 1 || C > 16384)
-        return fail(c, KNN_EINVAL, "weighted vote: bad nq=%lld kin=%d stride=%lld C=%d", (long long)nq, kin,
-                    (long long)stride, C);
-    knn_status s;
-    if ((s = weighted_check(c, kmax, weights, self_base, d_query_labels, d_pred_all, d_correct, d_scores)) != KNN_OK)
-        return s;
-    if (nq > 0 && (!d_idx || !d_train_labels || (!d_dist && weights != KNN_W_UNIFORM)))
-        return fail(c, KNN_EINVAL, "weighted vote: d_idx / d_dist / d_train_labels is NULL");
-    HIP_OR_FAIL(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    HIP_OR_FAIL(c, reset_ctrl(c, st));
-    if (d_correct) HIP_OR_FAIL(c, hipMemsetAsync(d_correct, 0, sizeof(int64_t) * (size_t)kmax, st));
-    const WeightedVote wv{weights, 0, d_scores};
-    if ((s = vote_weighted_enqueue(c, nq, kin, C, d_idx, d_dist, stride, d_train_labels, wv, self_base,
-                                   d_query_labels, d_pred_all, nq, d_correct, nullptr, nullptr, true, st)) != KNN_OK)
-        return s;
-    return finish_call(c, st);
+    return lists_vote(c,
+                      weighted_consumer(weights, 0, d_query_labels, d_pred_all, nq, d_correct, d_scores, nullptr, nullptr),
+                      Lists{d_idx, d_dist, nq, stride, kin, true}, C, d_train_labels, self_base,
+                      d_idx && d_train_labels && (d_dist || weights == KNN_W_UNIFORM), hip_stream);
 }
 
 knn_status knn_sweep_weighted_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax,
                                      int32_t C, int32_t weights, int64_t self_base, const int32_t* d_query_labels,
                                      int32_t* d_pred_all, int64_t* d_correct, float* d_scores, float* d_topk_dist,
                                      int32_t* d_topk_idx, void* hip_stream) {
-    if (!c) return KNN_EINVAL;
-    c->err.clear();
-    knn_status s;
-    if ((s = weighted_check(c, kmax, weights, self_base, d_query_labels, d_pred_all, d_correct, d_scores)) != KNN_OK)
-        return s;
-    reset_stats(c);
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    const WeightedVote wv{weights, 0, d_scores};
-    return sweep_core(c, tr, te, kmax, C, self_base, d_query_labels, d_pred_all, te ? te->n : 0, d_correct,
-                      d_topk_dist, d_topk_idx, st, &wv);
+    return lists_device(c, tr, te, kmax, C, self_base,
+                        weighted_consumer(weights, 0, d_query_labels, d_pred_all, te ? te->n : 0, d_correct, d_scores,
+                                          d_topk_dist, d_topk_idx),
+                        hip_stream);
 }
 
 knn_status knn_predict_weighted_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t k,
                                        int32_t C, int32_t weights, int32_t* d_pred, float* d_scores,
                                        float* d_topk_dist, int32_t* d_topk_idx, void* hip_stream) {
-    if (!c) return KNN_EINVAL;
-    c->err.clear();
-    knn_status s;
-    if ((s = weighted_check(c, k, weights, -1, nullptr, d_pred, nullptr, d_scores)) != KNN_OK) return s;
-    reset_stats(c);
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     // only row k - 1 of the prefix votes is staged and stored: d_pred is that row
-    const WeightedVote wv{weights, k - 1, d_scores};
-    return sweep_core(c, tr, te, k, C, -1, nullptr, d_pred, te ? te->n : 0, nullptr, d_topk_dist, d_topk_idx, st, &wv);
+    return lists_device(c, tr, te, k, C, -1,
+                        weighted_consumer(weights, k - 1, nullptr, d_pred, te ? te->n : 0, nullptr, d_scores, d_topk_dist,
+                                          d_topk_idx),
+                        hip_stream);
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------
-// Regression (knn_amd.h "Regression"): k_regress_sweep on the lists of the same top-kin pass
-// ---------------------------------------------------------------------------------
-namespace {
-
-// what the regression entry points share: the kind, the outputs asked for and the list length
-knn_status regress_check(knn_ctx* c, int32_t kmax, int32_t weights, int64_t self_base, const void* qtargets,
-                         const void* pred_all, const void* sse, const void* sae) {
-    if (weights != KNN_W_UNIFORM && weights != KNN_W_INV_DIST && weights != KNN_W_INV_SQDIST)
-        return fail(c, KNN_EINVAL, "regression: unknown weights=%d", weights);
-    if (weights == KNN_W_INV_SQDIST && c->metric != KNN_METRIC_SQEUCLIDEAN)
-        return fail(c, KNN_EINVAL, "regression: KNN_W_INV_SQDIST needs the squared Euclidean metric (metric=%d)",
-                    c->metric);
-    if (kmax < 1) return fail(c, KNN_EINVAL, "regression: kmax=%d must be >= 1", kmax);
-    if (!pred_all && !sse && !sae) return fail(c, KNN_EINVAL, "regression: pred_all, sse and sae are all NULL");
-    if ((sse || sae) && !qtargets) return fail(c, KNN_EINVAL, "regression: sse / sae need the query targets");
-    if (self_base >= 0 && kmax + 1 > 1024)
-        return fail(c, KNN_EINVAL, "regression: kmax=%d + the self row exceeds the supported maximum 1024", kmax);
-    return KNN_OK;
+knn_status knn_sweep_weighted(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t kmax, int32_t C,
+                              int32_t weights, int64_t self_base, const int32_t* query_labels, int32_t* out_pred_all,
+                              int64_t* out_correct, float* out_scores) {
+    return lists_host(c, tr, te, kmax, C, self_base,
+                      weighted_consumer(weights, 0, query_labels, out_pred_all, 0, out_correct, out_scores, nullptr,
+                                        nullptr));
 }
-
-// k_regress_sweep (+ k_regress_reduce, which adds into sse / sae) on lists in device memory,
-// enqueued on st (no synchronisation)
-knn_status regress_enqueue(knn_ctx* c, int64_t nq, int kin, const int32_t* idx, const float* dist, int64_t stride,
-                           const float* targets, int weights, int row0, int64_t self_base, const float* qtargets,
-                           float* pred_all, int64_t pred_stride, double* sse, double* sae, float* dist_out,
-                           int32_t* idx_out, bool check_dist, hipStream_t st) {
-    RegressArgs v{};
-    v.idx = idx; v.dist = dist; v.stride = stride; v.targets = targets;
-    v.nq = nq; v.kin = kin; v.kmax = self_base >= 0 ? kin - 1 : kin;
-    // (the metric's mapping of the kind: vote_weighted_enqueue)
-    v.weights = (c->metric != KNN_METRIC_SQEUCLIDEAN && weights == KNN_W_INV_DIST) ? KNN_VOTE_W_INV_SQDIST : weights;
-    v.self_base = self_base;
-    v.qtargets = qtargets; v.pred_all = pred_all; v.pred_stride = pred_stride; v.row0 = row0;
-    v.dist_out = dist ? dist_out : nullptr; v.idx_out = idx_out;
-    v.check_dist = check_dist ? 1 : 0;
-    v.status = c->ctrl.as<int32_t>();
-    if ((sse || sae) && nq > 0) {
-        HIP_OR_FAIL(c, c->rg_part.ensure(sizeof(double) * 2 * (size_t)v.kmax * (size_t)knn_regress_chunks(nq)));
-        v.part = c->rg_part.as<double>();
-    }
-    stage_begin(c, st, "regress");
-    HIP_OR_FAIL(c, knn_launch_regress(v, st));
-    if (v.part) HIP_OR_FAIL(c, knn_launch_regress_reduce(v.part, nq, v.kmax, row0, sse, sae, st));
-    stage_end(c, st);
-    return KNN_OK;
-}
-
-// the train view the vote-less pass runs with: the caller's features, and -- regression has no
-// classes -- a context-owned all-zero label array with C = 1
-knn_status regress_train(knn_ctx* c, const knn_dataset* tr, hipStream_t st, knn_dataset* out) {
-    *out = *tr;
-    const size_t need = sizeof(int32_t) * (size_t)std::max<int64_t>(tr->n, 1);
-    if (need > c->rg_zero.bytes || !c->rg_zero.p) {
-        HIP_OR_FAIL(c, c->rg_zero.ensure(need));
-        HIP_OR_FAIL(c, hipMemsetAsync(c->rg_zero.p, 0, need, st));
-    }
-    out->labels = c->rg_zero.as<int32_t>();
-    return KNN_OK;
-}
-
-// sweep_core's sibling: one top-kin pass with no vote into the context's list workspace,
-// k_regress_sweep behind it on the same stream, one finish_call per pass.  The GEMM path's passes
-// are cut at multiples of the reduce's span, so that sse / sae -- zeroed here when zero_sums,
-// then added into pass after pass on the stream -- are the bits of a single pass.
-knn_status regress_core(knn_ctx* c, const knn_dataset* tr0, const knn_dataset* te, const float* d_targets,
-                        int32_t kmax, int32_t weights, int row0, int64_t self_base, const float* d_qtargets,
-                        float* d_pred_all, int64_t pred_stride, double* d_sse, double* d_sae, bool zero_sums,
-                        float* d_dist, int32_t* d_idx, hipStream_t st) {
-    knn_status s;
-    if (!tr0) return fail(c, KNN_EINVAL, "train dataset is NULL");
-    const int kin = kmax + (self_base >= 0 ? 1 : 0);
-    const knn_dataset probe{tr0->feat, reinterpret_cast<const int32_t*>(tr0->feat), tr0->n, tr0->d, tr0->ld, tr0->dtype};
-    QueryOut out{nullptr, nullptr, nullptr, nullptr, kin, 0};
-    if ((s = validate_call(c, &probe, te, kin, 1, out, false, false)) != KNN_OK) return s;
-    if (self_base >= 0 && self_base + te->n > tr0->n)
-        return fail(c, KNN_EINVAL, "regression: self rows [%lld, %lld) outside the %lld train rows",
-                    (long long)self_base, (long long)(self_base + te->n), (long long)tr0->n);
-    if (te->n > 0 && !d_targets) return fail(c, KNN_EINVAL, "regression: the train targets are NULL");
-    HIP_OR_FAIL(c, hipSetDevice(c->device));
-    if (zero_sums) {
-        if (d_sse) HIP_OR_FAIL(c, hipMemsetAsync(d_sse, 0, sizeof(double) * (size_t)kmax, st));
-        if (d_sae) HIP_OR_FAIL(c, hipMemsetAsync(d_sae, 0, sizeof(double) * (size_t)kmax, st));
-    }
-    if (te->n == 0) {
-        HIP_OR_FAIL(c, hipStreamSynchronize(st));
-        return KNN_OK;
-    }
-    knn_dataset trz;
-    if ((s = regress_train(c, tr0, st, &trz)) != KNN_OK) return s;
-    const knn_dataset* tr = &trz;
-    const int algo = choose_algo(c, tr->n, te->n, tr->d, kin, tr->dtype);
-    const bool gemm = is_gemm(algo);
-    const int64_t span = (int64_t)KNN_REGRESS_CHUNK * KNN_REGRESS_SPAN;
-    int64_t pass = gemm ? std::max<int64_t>(1, c->ws_queries) : te->n;
-    if (gemm && pass >= span) pass -= pass % span;
-    const int64_t rows = std::min(pass, te->n);
-    HIP_OR_FAIL(c, c->sw_idx.ensure(sizeof(int32_t) * (size_t)rows * kin));
-    HIP_OR_FAIL(c, c->sw_dist.ensure(sizeof(float) * (size_t)rows * kin));
-    out.idx = c->sw_idx.as<int32_t>();
-    out.dist = c->sw_dist.as<float>();
-    for (int64_t q0 = 0; q0 < te->n; q0 += pass) {
-        const int64_t n = std::min(pass, te->n - q0);
-        const knn_dataset tq = offset_rows(*te, q0, n);
-        if ((s = predict_enqueue(c, tr, &tq, kin, 1, out, st, algo, nullptr)) == KNN_OK)
-            s = regress_enqueue(c, n, kin, out.idx, out.dist, kin, d_targets, weights, row0,
-                                self_base >= 0 ? self_base + q0 : -1, d_qtargets ? d_qtargets + q0 : nullptr,
-                                d_pred_all ? d_pred_all + q0 : nullptr, pred_stride, d_sse, d_sae,
-                                d_dist ? d_dist + q0 * kmax : nullptr, d_idx ? d_idx + q0 * kmax : nullptr, false, st);
-        if (s != KNN_OK || (s = finish_call(c, st)) != KNN_OK) {
-            if (s != KNN_EINVAL && s != KNN_ERANGE) c->tprep.valid = c->tpad.valid = false;  // a HIP failure: the operands may be partial
-            return s;
-        }
-        pass_stats(c, c->ctrl_host, gemm);
-    }
-    return KNN_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 knn_status knn_regress_vote_device(knn_ctx* c, int64_t nq, int32_t kin, const int32_t* d_idx, const float* d_dist,
                                    int64_t stride, const float* d_train_targets, int32_t weights, int64_t self_base,
                                    const float* d_query_targets, float* d_pred_all, double* d_sse, double* d_sae,
                                    void* hip_stream) {
-    if (!c) return KNN_EINVAL;
-    c->err.clear();
-    c->stages.clear();
-    const int32_t kmax = self_base >= 0 ? kin - 1 : kin;
-    if (nq < 0 || kin < 1 || kin > 1024 || stride < kin)
-        return fail(c, KNN_EINVAL, "regression: bad nq=%lld kin=%d stride=%lld", (long long)nq, kin, (long long)stride);
-    knn_status s;
-    if ((s = regress_check(c, kmax, weights, self_base, d_query_targets, d_pred_all, d_sse, d_sae)) != KNN_OK) return s;
-    if (nq > 0 && (!d_idx || !d_train_targets || (!d_dist && weights != KNN_W_UNIFORM)))
-        return fail(c, KNN_EINVAL, "regression: d_idx / d_dist / d_train_targets is NULL");
-    HIP_OR_FAIL(c, hipSetDevice(c->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    HIP_OR_FAIL(c, reset_ctrl(c, st));
-    if (d_sse) HIP_OR_FAIL(c, hipMemsetAsync(d_sse, 0, sizeof(double) * (size_t)kmax, st));
-    if (d_sae) HIP_OR_FAIL(c, hipMemsetAsync(d_sae, 0, sizeof(double) * (size_t)kmax, st));
-    if ((s = regress_enqueue(c, nq, kin, d_idx, d_dist, stride, d_train_targets, weights, 0, self_base, d_query_targets,
-                             d_pred_all, nq, d_sse, d_sae, nullptr, nullptr, true, st)) != KNN_OK)
-        return s;
-    return finish_call(c, st);
+    return lists_vote(c,
+                      regress_consumer(weights, 0, d_train_targets, d_query_targets, d_pred_all, nq, d_sse, d_sae, nullptr,
+                                       nullptr),
+                      Lists{d_idx, d_dist, nq, stride, kin, true}, 1, nullptr, self_base,
+                      d_idx && d_train_targets && (d_dist || weights == KNN_W_UNIFORM), hip_stream);
 }
 
 knn_status knn_regress_sweep_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te,
                                     const float* d_train_targets, int32_t kmax, int32_t weights, int64_t self_base,
                                     const float* d_query_targets, float* d_pred_all, double* d_sse, double* d_sae,
                                     float* d_topk_dist, int32_t* d_topk_idx, void* hip_stream) {
-    if (!c) return KNN_EINVAL;
-    c->err.clear();
-    knn_status s;
-    if ((s = regress_check(c, kmax, weights, self_base, d_query_targets, d_pred_all, d_sse, d_sae)) != KNN_OK) return s;
-    reset_stats(c);
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    return regress_core(c, tr, te, d_train_targets, kmax, weights, 0, self_base, d_query_targets, d_pred_all,
-                        te ? te->n : 0, d_sse, d_sae, true, d_topk_dist, d_topk_idx, st);
+    return lists_device(c, tr, te, kmax, 1, self_base,
+                        regress_consumer(weights, 0, d_train_targets, d_query_targets, d_pred_all, te ? te->n : 0, d_sse,
+                                         d_sae, d_topk_dist, d_topk_idx),
+                        hip_stream);
 }
 
 knn_status knn_regress_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, const float* d_train_targets,
                               int32_t k, int32_t weights, float* d_pred, float* d_topk_dist, int32_t* d_topk_idx,
                               void* hip_stream) {
-    if (!c) return KNN_EINVAL;
-    c->err.clear();
-    knn_status s;
-    if ((s = regress_check(c, k, weights, -1, nullptr, d_pred, nullptr, nullptr)) != KNN_OK) return s;
-    reset_stats(c);
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     // only row k - 1 of the prefix predictions is staged and stored: d_pred is that row
-    return regress_core(c, tr, te, d_train_targets, k, weights, k - 1, -1, nullptr, d_pred, te ? te->n : 0, nullptr,
-                        nullptr, false, d_topk_dist, d_topk_idx, st);
+    return lists_device(c, tr, te, k, 1, -1,
+                        regress_consumer(weights, k - 1, d_train_targets, nullptr, d_pred, te ? te->n : 0, nullptr, nullptr,
+                                         d_topk_dist, d_topk_idx),
+                        hip_stream);
 }
 
 knn_status knn_regress_sweep(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, const float* train_targets,
                              int32_t kmax, int32_t weights, int64_t self_base, const float* query_targets,
                              float* out_pred_all, double* out_sse, double* out_sae) {
-    if (!c) return KNN_EINVAL;
-    c->err.clear();
-    knn_status s;
-    if ((s = check_dataset(c, tr, "train", false)) != KNN_OK) return s;
-    if ((s = check_dataset(c, te, "test", false)) != KNN_OK) return s;
-    if ((s = regress_check(c, kmax, weights, self_base, query_targets, out_pred_all, out_sse, out_sae)) != KNN_OK)
-        return s;
-    if (tr->d != te->d) return fail(c, KNN_EINVAL, "feature count mismatch: train d=%d test d=%d", tr->d, te->d);
-    if (tr->dtype != te->dtype) return fail(c, KNN_EINVAL, "train and test dtypes differ");
-    const int64_t nq = te->n;
-    const int kin = kmax + (self_base >= 0 ? 1 : 0);
-    if (kin > tr->n) return fail(c, KNN_EINVAL, "k=%d outside [1, n_train=%lld]", kin, (long long)tr->n);
-    if (self_base >= 0 && self_base + nq > tr->n)
-        return fail(c, KNN_EINVAL, "regression: self rows [%lld, %lld) outside the %lld train rows",
-                    (long long)self_base, (long long)(self_base + nq), (long long)tr->n);
-    if (tr->n > 0 && !train_targets) return fail(c, KNN_EINVAL, "regression: the train targets are NULL");
-    reset_stats(c);
-    if (out_sse) std::memset(out_sse, 0, sizeof(double) * (size_t)kmax);
-    if (out_sae) std::memset(out_sae, 0, sizeof(double) * (size_t)kmax);
-    if (nq == 0) return KNN_OK;
-    HIP_OR_FAIL(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const int d = tr->d;
-    const size_t es = (size_t)elem_size(tr->dtype);
-    const int ldd = (int)((d + (int)(16 / es) - 1) / (int)(16 / es) * (int)(16 / es));  // device rows padded to 16 B
-    // batches are cut at multiples of the reduce's span: the sums, which stay on the device and are
-    // added into batch after batch, then are the bits knn_regress_sweep_device gives for all queries
-    const int64_t span = (int64_t)KNN_REGRESS_CHUNK * KNN_REGRESS_SPAN;
-    const int64_t B = std::min<int64_t>(nq, std::max<int64_t>(span, c->batch_rows - c->batch_rows % span));
-    {
-        // the device call's checks on the shapes it will see, before anything is enqueued
-        const knn_dataset vtr{(const void*)(uintptr_t)256, (const int32_t*)(uintptr_t)256, tr->n, d, ldd, tr->dtype};
-        const knn_dataset vq{(const void*)(uintptr_t)256, nullptr, B, d, ldd, te->dtype};
-        const QueryOut vo{nullptr, nullptr, nullptr, nullptr, kin, 0};
-        if ((s = validate_call(c, &vtr, &vq, kin, 1, vo, false, false)) != KNN_OK) return s;
-    }
-    // every error from here on drains the stream (no copy from or to the caller's buffers
-    // outlives the call) and drops the train cache entry (its upload may not have run)
-    auto abort_call = [&](knn_status e) {
-        (void)hipStreamSynchronize(st);
-        c->tcache.valid = false;
-        c->tprep.valid = c->tpad.valid = false;
-        return e;
-    };
-    const knn_dataset trn{tr->feat, nullptr, tr->n, tr->d, tr->ld, tr->dtype};  // no classes here
-    knn_dataset dtr;
-    if ((s = train_device(c, &trn, st, &dtr)) != KNN_OK) return abort_call(s);
-    HIP_OR_ABORT(c->rg_targets.ensure(sizeof(float) * (size_t)tr->n));
-    HIP_OR_ABORT(hipMemcpyAsync(c->rg_targets.p, train_targets, sizeof(float) * (size_t)tr->n, hipMemcpyHostToDevice, st));
-    HIP_OR_ABORT(c->q_slot[0].ensure(es * (size_t)ldd * B));
-    if (out_pred_all) HIP_OR_ABORT(c->sw_pred.ensure(sizeof(float) * (size_t)kmax * B));
-    if (query_targets) HIP_OR_ABORT(c->rg_qt.ensure(sizeof(float) * (size_t)B));
-    double *d_sse = nullptr, *d_sae = nullptr;
-    if (out_sse || out_sae) {
-        HIP_OR_ABORT(c->rg_sums.ensure(sizeof(double) * 2 * (size_t)kmax));
-        HIP_OR_ABORT(hipMemsetAsync(c->rg_sums.p, 0, sizeof(double) * 2 * (size_t)kmax, st));
-        if (out_sse) d_sse = c->rg_sums.as<double>();
-        if (out_sae) d_sae = c->rg_sums.as<double>() + kmax;
-    }
-    // one batch after another, each uploaded, swept and downloaded before the next starts
-    for (int64_t q0 = 0; q0 < nq; q0 += B) {
-        const int64_t n = std::min(B, nq - q0);
-        const unsigned char* src = (const unsigned char*)te->feat + es * (size_t)q0 * (size_t)te->ld;
-        HIP_OR_ABORT(hipMemcpy2DAsync(c->q_slot[0].p, es * ldd, src, es * te->ld, es * d, n, hipMemcpyHostToDevice, st));
-        if (query_targets)
-            HIP_OR_ABORT(hipMemcpyAsync(c->rg_qt.p, query_targets + q0, sizeof(float) * n, hipMemcpyHostToDevice, st));
-        c->stats[7] += (int64_t)(es * d * n);
-        const knn_dataset dq{c->q_slot[0].p, nullptr, n, d, ldd, te->dtype};
-        s = regress_core(c, &dtr, &dq, c->rg_targets.as<float>(), kmax, weights, 0, self_base >= 0 ? self_base + q0 : -1,
-                         query_targets ? c->rg_qt.as<float>() : nullptr, out_pred_all ? c->sw_pred.as<float>() : nullptr,
-                         n, d_sse, d_sae, false, nullptr, nullptr, st);
-        if (s != KNN_OK) return abort_call(s);
-        // (a synchronous copy on the null stream: ordered after the context's blocking stream)
-        if (out_pred_all)
-            HIP_OR_ABORT(hipMemcpy2D(out_pred_all + q0, sizeof(float) * (size_t)nq, c->sw_pred.p, sizeof(float) * (size_t)n,
-                                     sizeof(float) * (size_t)n, kmax, hipMemcpyDeviceToHost));
-    }
-    if (out_sse) HIP_OR_ABORT(hipMemcpy(out_sse, d_sse, sizeof(double) * (size_t)kmax, hipMemcpyDeviceToHost));
-    if (out_sae) HIP_OR_ABORT(hipMemcpy(out_sae, d_sae, sizeof(double) * (size_t)kmax, hipMemcpyDeviceToHost));
-    return KNN_OK;
+    return lists_host(c, tr, te, kmax, 1, self_base,
+                      regress_consumer(weights, 0, train_targets, query_targets, out_pred_all, 0, out_sse, out_sae, nullptr,
+                                       nullptr));
 }
 
 }  // extern "C"
@@ -1819,7 +1711,7 @@ knn_status knn_predict(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te,
     hipStream_t st = c->stream, cs = c->cstream;
     const int d = tr->d;
     const size_t es = (size_t)elem_size(tr->dtype);
-    const int ldd = (int)((d + (int)(16 / es) - 1) / (int)(16 / es) * (int)(16 / es));  // device rows padded to 16 B
+    const int ldd = device_ld(d, tr->dtype);
     const int algo = choose_algo(c, tr->n, nq, d, k, tr->dtype);
     const bool gemm = is_gemm(algo);
     // queries stream through two device slots: batch b+1 uploads (copy stream) while batch b
@@ -1827,14 +1719,9 @@ knn_status knn_predict(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te,
     int64_t B = std::min<int64_t>(nq, c->batch_rows);
     if (gemm) B = std::min<int64_t>(B, c->ws_queries);
     const int64_t nb = (nq + B - 1) / B;
-    {
-        // the device call's checks on the shapes it will see, before anything is enqueued: no
-        // early return may leave a copy to or from the caller's buffers in flight
-        const knn_dataset vtr{(const void*)(uintptr_t)256, tr->labels, tr->n, d, ldd, tr->dtype};
-        const knn_dataset vq{(const void*)(uintptr_t)256, nullptr, B, d, ldd, te->dtype};
-        const QueryOut vo{out_pred, out_dist, out_idx, nullptr, k, 0};
-        if ((s = validate_call(c, &vtr, &vq, k, C, vo, false)) != KNN_OK) return s;
-    }
+    if ((s = validate_host_shapes(c, tr, B, ldd, k, C, QueryOut{out_pred, out_dist, out_idx, nullptr, k, 0}, true)) !=
+        KNN_OK)
+        return s;
     // from here on every error drains both streams (no DMA outlives the call) and drops the
     // train cache entry (its upload may not have run)
     auto abort_call = [&](knn_status e) {

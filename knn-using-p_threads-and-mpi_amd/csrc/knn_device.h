@@ -1,5 +1,5 @@
 // knn_device.h -- device helpers shared by the kernel translation units of libknn_amd
-// (knn_kernels.hip, knn_metric.hip, knn_fused.hip, knn_fused16.hip, knn_vote_weighted.hip): keys and
+// (knn_kernels.hip, knn_metric.hip, knn_fused.hip, knn_fused16.hip, knn_vote_weighted.hip, knn_regress.hip): keys and
 // wave bitonic networks, the vote and outputs of a finished wave list, the lane-shift insert, bf16 helpers, ordered-float bits, LDS-DMA issue and the GEMM filter tile
 // geometry.
 #pragma once
@@ -462,4 +462,34 @@ __device__ __forceinline__ float vote_weight(int kind, bool zero_mode, float d) 
     if (kind == KNN_VOTE_W_UNIFORM) return 1.0f;
     if (zero_mode) return d == 0.0f ? 1.0f : 0.0f;
     return kind == KNN_VOTE_W_INV_DIST ? 1.0f / sqrtf(d) : 1.0f / d;
+}
+
+// What the list kernels k_vote_weighted and k_regress_sweep share; no arithmetic.  (k_vote_sweep
+// keeps its own copy of the self-removal: through list_skip its 1024-entry form allocated one
+// more spilled scalar register.)
+// Self-removal: the place of the entry left out of query q's list row[0 .. kin) -- the first
+// equal to self_base + q, the last when none is, kin (none) without self_base.  Elements at or
+// behind it read one place further on.  One wave per list, element e = 64 r + lane.
+template <int R>
+__device__ __forceinline__ int list_skip(const int32_t* __restrict__ row, int kin, int64_t self_base, int64_t q,
+                                         int lane) {
+    int skip = kin;
+    if (self_base >= 0) {
+        const int64_t self = self_base + q;
+        skip = kin - 1;
+#pragma unroll
+        for (int r = R - 1; r >= 0; r--) {
+            const int e = 64 * r + lane;
+            const u64 m = __ballot(e < kin && (int64_t)row[e] == self);
+            if (m) skip = 64 * r + __ffsll(m) - 1;
+        }
+    }
+    return skip;
+}
+// the zero rule of the weighted kinds looks at the first entry that is left: present, at d == 0
+__device__ __forceinline__ bool list_zero_mode(int weights, const int32_t* __restrict__ row,
+                                               const float* __restrict__ drow, int skip) {
+    if (weights == KNN_VOTE_W_UNIFORM) return false;
+    const int first = skip == 0 ? 1 : 0;
+    return row[first] >= 0 && drow[first] == 0.0f;
 }

@@ -18,8 +18,9 @@
 
 // ---------------------------------------------------------------------------------
 // k_regress_sweep<R>: k_vote_weighted's skeleton -- one wave per query, element e = 64 r + lane
-// in register r, the same self-skip, zero rule, first_missing, check_dist and idx_out /
-// dist_out copy, the [k][query] tile staged in LDS (row stride qb + 1) and stored coalesced --
+// in register r, the same self-skip and zero rule (list_skip, list_zero_mode: knn_device.h),
+// first_missing, check_dist and idx_out / dist_out copy, the [k][query] tile staged in LDS (row
+// stride qb + 1) and stored coalesced --
 // with the per-class rounds replaced by ONE chain per query:
 //   N_k = N_{k-1} + (double)w_j (double)y_j,  D_k = D_{k-1} + (double)w_j,  j = k - 1 ascending.
 //  * The list is walked in order; the entry's lane hands (w, y) to the wave (v_readlane: the
@@ -59,24 +60,8 @@ __global__ __launch_bounds__(256) void k_regress_sweep(RegressArgs a) {
             const int64_t q = q0 + j;
             const int32_t* __restrict__ row = a.idx + q * a.stride;
             const float* __restrict__ drow = a.dist ? a.dist + q * a.stride : nullptr;
-            // the place of the skipped entry (kin: none)
-            int skip = a.kin;
-            if (a.self_base >= 0) {
-                const int64_t self = a.self_base + q;
-                skip = a.kin - 1;
-#pragma unroll
-                for (int r = R - 1; r >= 0; r--) {
-                    const int e = 64 * r + lane;
-                    const u64 m = __ballot(e < a.kin && (int64_t)row[e] == self);
-                    if (m) skip = 64 * r + __ffsll(m) - 1;
-                }
-            }
-            // the zero rule looks at the first entry that is left
-            bool zero_mode = false;
-            if (a.weights != KNN_VOTE_W_UNIFORM) {
-                const int first = skip == 0 ? 1 : 0;
-                zero_mode = row[first] >= 0 && drow[first] == 0.0f;
-            }
+            const int skip = list_skip<R>(row, a.kin, a.self_base, q, lane);
+            const bool zero_mode = list_zero_mode(a.weights, row, drow, skip);
             float w[R], y[R];
             int first_missing = a.kmax;
 #pragma unroll

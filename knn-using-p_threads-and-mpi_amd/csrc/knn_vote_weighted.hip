@@ -17,7 +17,7 @@
 
 // ---------------------------------------------------------------------------------
 // k_vote_weighted<R>: k_vote_sweep's skeleton -- one wave per query, element e = 64 r + lane
-// in register r, labels read as labels[idx], the same self-skip, the [k][query] tile staged
+// in register r, labels read as labels[idx], the same self-skip (list_skip), the [k][query] tile staged
 // in LDS (row stride qb + 1) and stored coalesced, correct[k - 1] counted per thread -- with
 // the popcount of a label's occurrences replaced by the score the rules define:
 //   S_c(k) = the fp32 sum of w_j over j < k with label_j == c, added in ascending j.
@@ -65,24 +65,8 @@ __global__ __launch_bounds__(256) void k_vote_weighted(VoteWeightedArgs a) {
             const int64_t q = q0 + j;
             const int32_t* __restrict__ row = a.idx + q * a.stride;
             const float* __restrict__ drow = a.dist ? a.dist + q * a.stride : nullptr;
-            // the place of the skipped entry (kin: none)
-            int skip = a.kin;
-            if (a.self_base >= 0) {
-                const int64_t self = a.self_base + q;
-                skip = a.kin - 1;
-#pragma unroll
-                for (int r = R - 1; r >= 0; r--) {
-                    const int e = 64 * r + lane;
-                    const u64 m = __ballot(e < a.kin && (int64_t)row[e] == self);
-                    if (m) skip = 64 * r + __ffsll(m) - 1;
-                }
-            }
-            // the zero rule looks at the first entry that is left
-            bool zero_mode = false;
-            if (a.weights != KNN_VOTE_W_UNIFORM) {
-                const int first = skip == 0 ? 1 : 0;
-                zero_mode = row[first] >= 0 && drow[first] == 0.0f;
-            }
+            const int skip = list_skip<R>(row, a.kin, a.self_base, q, lane);
+            const bool zero_mode = list_zero_mode(a.weights, row, drow, skip);
             int lab[R];
             float w[R];
             int first_missing = a.kmax;

@@ -281,6 +281,39 @@ def test_host_sweep_over_several_batches(knn, ctx, grid):
     assert np.array_equal(ch, (ph == ql[None, :]).sum(axis=1))
 
 
+def batch_case(self_base):
+    """2,000 train rows x 20 on an integer grid (ties), 7 classes, and 1,500 queries: two full
+    host batches of 700 and a ragged one.  With self_base the queries are train rows
+    [self_base, self_base + 1500) and score against their own labels."""
+    rng = np.random.default_rng(31)
+    tr = rng.integers(-3, 4, size=(2000, 20)).astype(np.float32)
+    lab = rng.integers(0, 7, size=2000).astype(np.int32)
+    if self_base is None:
+        return tr, lab, rng.integers(-3, 4, size=(1500, 20)).astype(np.float32), \
+            rng.integers(0, 7, size=1500).astype(np.int32)
+    return tr, lab, tr[self_base:self_base + 1500].copy(), lab[self_base:self_base + 1500].copy()
+
+
+@pytest.mark.parametrize("self_base", [None, 300])
+def test_host_sweep_batches_of_700(knn, monkeypatch, self_base):
+    """Context.sweep in host batches of 700 (KNN_BATCH_ROWS; 700 + 700 + 100 queries) equals
+    sweep_device on the same data in one call: pred_all and the correct counts summed over the
+    batches, with and without the self rows."""
+    C, kmax = 7, 9
+    tr, lab, te, ql = batch_case(self_base)
+    monkeypatch.setenv("KNN_BATCH_ROWS", "700")
+    c = knn.Context(0, algo="direct")
+    try:
+        ph, ch = c.sweep(tr, lab, te, kmax, C, query_labels=ql, self_base=self_base)
+        pd, cd = c.sweep_device(_dev(tr), _dev(lab), _dev(te), kmax, C, query_labels=_dev(ql), self_base=self_base)
+        assert c.stats()["h2d_query_bytes"] == 0     # (the device call moves nothing)
+    finally:
+        c.close()
+    assert ph.shape == (kmax, 1500) and np.array_equal(ph, pd.cpu().numpy())
+    assert np.array_equal(ch, cd.cpu().numpy()) and np.array_equal(ch, (ph == ql[None, :]).sum(axis=1))
+    assert (ph[1:] != ph[:-1]).any(axis=0).mean() >= 0.25   # the predictions move with k
+
+
 # ---------------------------------------------------------------------------------------
 # status
 # ---------------------------------------------------------------------------------------

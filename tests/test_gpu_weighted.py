@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import DATA, PKG_DIR, golden_manifest, golden_pred, pred_sha
-from test_gpu_sweep import D, KMAXS, NQ, NQS, NT, _dev, _grid_labels, _loo_set, _pad4
+from test_gpu_sweep import D, KMAXS, NQ, NQS, NT, _dev, _grid_labels, _loo_set, _pad4, batch_case
 from test_weighted_cpu import (INV_DIST, INV_SQDIST, KINDS, UNIFORM, bits, list_weights, remove_self,
                                weighted_reference)
 
@@ -341,6 +341,29 @@ def test_host_sweep_weighted_over_several_batches(knn, ctx, sets):
     p = knn.proba(sd)
     assert np.allclose(p.cpu().numpy(), knn.proba(sh), rtol=1e-6, atol=0)   # (a helper: the row sums' order is torch's)
     assert np.allclose(p.sum(dim=1).cpu().numpy(), 1.0, rtol=0, atol=1e-6)
+
+
+@pytest.mark.parametrize("self_base", [None, 300])
+@pytest.mark.parametrize("weights", KINDS)
+def test_host_sweep_weighted_batches_of_700(knn, monkeypatch, weights, self_base):
+    """Context.sweep_weighted in host batches of 700 (KNN_BATCH_ROWS; test_gpu_sweep's batch_case)
+    equals sweep_weighted_device on the same data in one call: pred_all, the correct counts summed
+    over the batches and every batch's rows of the scores, in every bit."""
+    C, kmax = 7, 9
+    tr, lab, te, ql = batch_case(self_base)
+    monkeypatch.setenv("KNN_BATCH_ROWS", "700")
+    c = knn.Context(0, algo="direct")
+    try:
+        ph, ch, sh = c.sweep_weighted(tr, lab, te, kmax, C, weights, query_labels=ql, self_base=self_base,
+                                      scores=True)
+        pd, cd, sd = c.sweep_weighted_device(_dev(tr), _dev(lab), _dev(te), kmax, C, weights,
+                                             query_labels=_dev(ql), self_base=self_base, scores=True)
+    finally:
+        c.close()
+    assert ph.shape == (kmax, 1500) and np.array_equal(ph, pd.cpu().numpy())
+    assert np.array_equal(ch, cd.cpu().numpy()) and np.array_equal(ch, (ph == ql[None, :]).sum(axis=1))
+    assert sh.shape == (1500, C) and np.array_equal(bits(sh), bits(sd.cpu().numpy()))
+    assert (sh > 0).any(axis=1).all()
 
 
 # ---------------------------------------------------------------------------------------
