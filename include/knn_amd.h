@@ -61,8 +61,15 @@ typedef enum {
                                runs it first and re-runs a call as KNN_ALGO_GEMM_SPLIT when
                                more than 1/16 of its queries overflow their candidate lists.
                                bf16 data: as KNN_ALGO_GEMM */
-    KNN_ALGO_DIRECT_SCAN = 5 /* direct form, one block per query (k_exact_scan, the GEMM path's
+    KNN_ALGO_DIRECT_SCAN = 5, /* direct form, one block per query (k_exact_scan, the GEMM path's
                                 per-query fallback) */
+    KNN_ALGO_GEMM_I8 = 6   /* as KNN_ALGO_GEMM_BF16, with the fp32 rows quantised to int8 for the
+                              filter only (one symmetric scale per train set, max|t| / 127, used for
+                              the queries too; v_mfma_i32_32x32x32_i8, half the MFMA work per
+                              feature; the certificate carries the measured rounding) + the same
+                              exact fp32 rescore.  Runs at d = 128, k <= 32 on a train set with a
+                              finite non-zero range; anywhere else the call runs the bf16 operands
+                              of KNN_ALGO_GEMM_BF16.  knn_last_stats()[11] says which ran. */
 } knn_algo;
 
 /* knn_opts.flags */
@@ -486,8 +493,10 @@ int32_t knn_stage_times(const knn_ctx* ctx, const char** names, float* ms, int32
  * filter's train-side operands came from the KNN_OPT_CACHE_TRAIN cache (no train norm or
  * tile-block pass ran), [9] the fused filter's MFMA shape (32: v_mfma_f32_32x32x16_bf16,
  * 16: v_mfma_f32_16x16x32_bf16, 0: no fused filter ran), [10] the fused filter's queries per
- * wave (32 or 64, knn_fused_plan's rule; 0: no fused filter ran).  Returns the number
- * written (<= 11). */
+ * wave (32 or 64, knn_fused_plan's rule; 0: no fused filter ran), [11] the element the filter
+ * multiplied: 1 int8 (KNN_ALGO_GEMM_I8's form; [3] stays 3, fp32 rows rounded once to a narrow
+ * MFMA operand), 0 the data's own type or bf16.  Returns the number written (<= 12); a caller
+ * that asks for 11 gets the first 11 as before. */
 int32_t knn_last_stats(const knn_ctx* ctx, int64_t* out, int32_t n);
 
 /*
@@ -526,6 +535,10 @@ knn_status knn_confusion_matrix_device(knn_ctx* ctx, const int32_t* d_pred, cons
  * sum_k a[i][k] b[j][k] as the MFMA accumulates it (device float [32][32]). */
 knn_status knn_mfma_probe_bf16(knn_ctx* ctx, const uint16_t* d_a, const uint16_t* d_b, int32_t K,
                                float* d_out, void* hip_stream);
+/* The same for the int8 operand class: v_mfma_i32_32x32x32_i8 over K/32 k-steps on a, b =
+ * [32][K] int8 (K % 32 == 0), d_out int32 [32][32]; every sum must be the integer dot product. */
+knn_status knn_mfma_probe_i8(knn_ctx* ctx, const int8_t* d_a, const int8_t* d_b, int32_t K,
+                             int32_t* d_out, void* hip_stream);
 
 /* ARFF loader (replaces ArffParser::parse, libarff/arff_parser.cpp:23, for the
  * read path): NUMERIC attributes parsed with libarff's istringstream>>float rules.

@@ -49,12 +49,15 @@ STATUS_NAMES = {0: "KNN_OK", 1: "KNN_EINVAL", 2: "KNN_ENOMEM", 3: "KNN_EHIP", 4:
                 5: "KNN_ENODEV", 6: "KNN_EIO", 7: "KNN_ERCCL"}
 KNN_COMM_ID_BYTES = 128
 KNN_F32, KNN_BF16 = 0, 1
-ALGOS = {"auto": 0, "direct": 1, "gemm": 2, "gemm_split": 3, "gemm_bf16": 4, "direct_scan": 5}
+ALGOS = {"auto": 0, "direct": 1, "gemm": 2, "gemm_split": 3, "gemm_bf16": 4, "direct_scan": 5, "gemm_i8": 6}
 # knn_weight: the vote's weight kinds ("distance" is sklearn's weights="distance")
 WEIGHTS = {"uniform": 0, "distance": 1, "sqdist": 2}
 # knn_metric: the distance a context computes ("euclidean" is the reference's squared Euclidean)
 METRICS = {"euclidean": 0, "manhattan": 1, "chebyshev": 2}
 FILTER_OPERANDS = {-1: None, 0: "f32", 1: "bf16", 2: "bf16x3 split", 3: "bf16 rounded"}
+# knn_last_stats()[11]: the element the filter multiplied.  Under "bf16 rounded" (fp32 rows rounded
+# once to a narrow MFMA operand, one product per fp32 product) it is "i8" when the int8 form ran
+FILTER_ELEMENTS = {0: "bf16", 1: "i8"}
 
 
 class KnnError(RuntimeError):
@@ -138,6 +141,8 @@ def load_library(path=LIB_PATH):
         "knn_generate": (I32, [P, P, P, I64, I64, I32, I32, I32, I32, ctypes.c_uint64,
                                ctypes.c_uint32, I32, P]),
         "knn_mfma_probe_bf16": (I32, [P, P, P, I32, P, P]),
+        "knn_mfma_probe_i8": (I32, [P, P, P, I32, P, P]),
+        "knn_debug_set_i8_coarsen": (I32, [P, F]),
         "knn_set_generation": (I32, [P, ctypes.c_uint64]),
         "knn_set_metric": (I32, [P, I32]),
         "knn_get_metric": (I32, [P]),
@@ -814,6 +819,22 @@ class Context:
                                                  self._stream(stream, a)))
         return out
 
+    def mfma_probe_i8(self, a, b, stream=None):
+        """The int8 filter's MFMA chain on device operands a, b: [32][K] torch.int8 (K % 32 == 0)
+        -> int32 [32][32] = a @ b.T as v_mfma_i32_32x32x32_i8 sums it."""
+        import torch
+        if a.shape != b.shape or a.dim() != 2 or a.shape[0] != 32 or a.dtype != torch.int8 or b.dtype != torch.int8:
+            raise KnnError(KNN_EINVAL, "a, b must be [32][K] int8")
+        a, b = a.contiguous(), b.contiguous()
+        out = torch.empty((32, 32), dtype=torch.int32, device=a.device)
+        self._check(self.lib.knn_mfma_probe_i8(self.h, a.data_ptr(), b.data_ptr(), a.shape[1], out.data_ptr(),
+                                               self._stream(stream, a)))
+        return out
+
+    def _set_i8_coarsen(self, mul):
+        """Test hook: the int8 filter's quantisation step times mul (1 <= mul <= 8) from now on."""
+        self._check(self.lib.knn_debug_set_i8_coarsen(self.h, float(mul)))
+
     def set_generation(self, generation):
         """Invalidate cached train uploads and train-side filter operands (knn_set_generation)."""
         self._check(self.lib.knn_set_generation(self.h, generation))
@@ -842,13 +863,14 @@ class Context:
         return out
 
     def stats(self):
-        v = (ctypes.c_int64 * 11)()
-        self.lib.knn_last_stats(self.h, v, 11)
+        v = (ctypes.c_int64 * 12)()
+        self.lib.knn_last_stats(self.h, v, 12)
         return {"candidates": v[0], "fallback_queries": v[1], "train_segments": v[2],
                 "filter_operands": FILTER_OPERANDS.get(v[3], v[3]), "rerun_split": bool(v[4]),
                 "fused_norm": bool(v[5]), "h2d_train_bytes": v[6], "h2d_query_bytes": v[7],
                 "train_operands_cached": bool(v[8]), "filter_mfma": v[9],
-                "queries_per_wave": v[10]}
+                "queries_per_wave": v[10],
+                "filter_element": FILTER_ELEMENTS.get(v[11], v[11]) if v[3] in (1, 2, 3) else None}
 
 
 def comm_unique_id():

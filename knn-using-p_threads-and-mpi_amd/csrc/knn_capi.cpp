@@ -80,8 +80,19 @@ struct knn_ctx {
     // train-side operands of the fused filter (tnorm, tnp, tmax, tblk, tctrl) kept across calls
     // under KNN_OPT_CACHE_TRAIN, keyed by the train view, the tile height and the generation;
     // epoch = the upload count of knn_predict's own train buffer (its pointer does not change)
-    struct { const void* feat; int64_t n; int d, ld, dtype, bn; uint64_t gen, epoch; bool valid; }
-        tprep{nullptr, 0, 0, 0, 0, 0, 0, 0, false};
+    // (i8: the blocks hold the int8 operand class)
+    struct { const void* feat; int64_t n; int d, ld, dtype, bn; uint64_t gen, epoch; bool valid; int i8; }
+        tprep{nullptr, 0, 0, 0, 0, 0, 0, 0, false, 0};
+    // the int8 operand class's view of a train set (KNN_ALGO_GEMM_I8), kept with tprep's key: the
+    // scale s = max|t| / 127 (read back once per train set: the one host round trip of the
+    // class, on the call that builds the operands), whether the class may run on it (finite,
+    // non-zero range), and whether a call ended with more than 1/64 of its queries on the exact
+    // fallback (demoted: AUTO then keeps to the bf16 operands for this train set)
+    struct { const void* feat; int64_t n; int d, ld; uint64_t gen, epoch; bool valid; float s; bool ok, demoted; }
+        i8c{nullptr, 0, 0, 0, 0, 0, false, 0.0f, false, false};
+    DBuf i8max;              // the max-abs word of k_absmax
+    float i8_coarsen = 1.0f; // test hook (knn_debug_set_i8_coarsen): the int8 step times a factor in [1, 8]
+    int64_t i8_pass_nq = 0;  // queries of the last int8 pass (the demotion rule)
     uint64_t train_epoch = 0;
     // the same for the non-fused GEMM paths' train copy padded to the 64-row grid (pad_t)
     struct { const void* feat; int64_t n; int d, ld, dtype; uint64_t gen, epoch; bool valid; }
@@ -131,9 +142,11 @@ struct knn_ctx {
     bool stage_open = false;  // the last stage_begin recorded an event (profile = 3 skips some)
     std::vector<float> stage_ms;
     std::vector<const char*> stage_names;
-    int64_t stats[11] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
+    int64_t stats[12] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
                                                       // operand type, rerun, fused, train / query H2D
-                                                      // bytes, train-side filter operands from the cache
+                                                      // bytes, train-side filter operands from the cache,
+                                                      // MFMA form, queries per wave, [11] the filter's
+                                                      // operand element (0: the data's / bf16, 1: int8)
     int subs = 2;                           // candidate sub-slices per segment of the last GEMM pass
     int64_t rerun_stats[3] = {0, -1, 0};    // segments, operand type, fused of AUTO's gated split re-run
     int num_cus = 256;
@@ -215,18 +228,32 @@ knn_status check_dataset(knn_ctx* c, const knn_dataset* x, const char* what, boo
     return KNN_OK;
 }
 
+// AUTO and the int8 operand class (DESIGN.md "int8 filter operands"): whether AUTO takes it where
+// it can run, and the largest ratio E8 / Ebf of the train set's row residuals under the int8 and
+// the bf16 rounding at which it still does (the guard against a scale set by outliers).  Measured
+// on A's rows by coarsening the int8 step (profiles/r08_studies): against gemm_bf16's 19.0 ms per
+// step, ratio 2.5 (the rule's own step) runs 14.2, 3.1 (x1.25) 14.8, 3.7 (x1.5) 15.6, 4.3 (x1.75)
+// 16.2 -- still 15 % under -- and 5.0 (x2) 17.6 at best, 19.4 in the median: under 10 %.  R is the
+// largest measured ratio that keeps the 10 %.
+static constexpr bool KNN_AUTO_I8 = true;
+static constexpr float KNN_I8_AUTO_R = 4.3f;
+
 // filter operand type of a GEMM-path call: fp32 data runs split (ELEM_SPLIT, bf16 hi/lo
 // rows of 4d bytes) under KNN_ALGO_GEMM_SPLIT, rounded (ELEM_ROUND, bf16 rows of 2d bytes)
-// under KNN_ALGO_GEMM_BF16, else the data's own type
+// under KNN_ALGO_GEMM_BF16, else the data's own type.  KNN_ALGO_GEMM_I8 is the rounded class too
+// (fp32 rows rounded once to a narrow MFMA operand): run_gemm rounds to int8 where the int8 form
+// can run and to bf16 where it cannot, and reports which in stats[11]
 int filter_elem(int algo, int dtype) {
     if (dtype != KNN_F32) return dtype;
-    return algo == KNN_ALGO_GEMM_SPLIT ? ELEM_SPLIT : algo == KNN_ALGO_GEMM_BF16 ? ELEM_ROUND : dtype;
+    return algo == KNN_ALGO_GEMM_SPLIT ? ELEM_SPLIT
+         : (algo == KNN_ALGO_GEMM_BF16 || algo == KNN_ALGO_GEMM_I8) ? ELEM_ROUND : dtype;
 }
 int filter_row_bytes(int felem, int d) {
     return felem == ELEM_SPLIT ? 4 * d : felem == ELEM_ROUND ? 2 * d : d * elem_size(felem);
 }
 bool is_gemm(int algo) {
-    return algo == KNN_ALGO_GEMM || algo == KNN_ALGO_GEMM_SPLIT || algo == KNN_ALGO_GEMM_BF16;
+    return algo == KNN_ALGO_GEMM || algo == KNN_ALGO_GEMM_SPLIT || algo == KNN_ALGO_GEMM_BF16 ||
+           algo == KNN_ALGO_GEMM_I8;
 }
 
 int choose_algo(const knn_ctx* c, int64_t nt, int64_t nq, int d, int k, int dtype) {
@@ -254,7 +281,12 @@ int choose_algo(const knn_ctx* c, int64_t nt, int64_t nq, int d, int k, int dtyp
     // Other widths keep the 10^9-pair rule.
     const double pairs = (double)nt * (double)nq;
     if (d >= 32 && nt >= 8192 && (pairs >= 1e9 || (knn_fused_supported(d) && nt >= 16384))) {
-        if (gemm_ok(KNN_ALGO_GEMM_BF16)) return KNN_ALGO_GEMM_BF16;
+        // fp32 rows at d = 128, k <= 32 with no forced study shape: the int8 operand class (half
+        // the MFMA work per feature), which run_gemm takes when the train set's range allows it
+        // (finite, E8 <= R Ebf, not demoted) and otherwise runs as the bf16 operands
+        if (gemm_ok(KNN_ALGO_GEMM_BF16))
+            return KNN_AUTO_I8 && dtype == KNN_F32 && d == 128 && k <= 32 && !c->fforce.m16 && c->fforce.nbuf == 0
+                       ? KNN_ALGO_GEMM_I8 : KNN_ALGO_GEMM_BF16;
         if (gemm_ok(KNN_ALGO_GEMM_SPLIT)) return KNN_ALGO_GEMM_SPLIT;
         if (gemm_ok(KNN_ALGO_GEMM)) return KNN_ALGO_GEMM;
     }
@@ -548,7 +580,9 @@ int choose_splits(const knn_ctx* c, int64_t n_qtiles, int64_t nt, int dtype, int
     return best;
 }
 
-// The GEMM pipeline of one filter operand type, enqueued on st with no host round trip:
+// The GEMM pipeline of one filter operand type, enqueued on st with no host round trip (one
+// exception: a call that builds the int8 operand class's train operands reads the train set's
+// scale back first -- a stream synchronisation, once per cached train set or per forced call):
 // norms -> operand rows -> filter -> rescore (queries whose candidate list overflowed, or
 // every query when a norm is too large for the certificate, go to the fallback list).
 // gate (optional): every stage runs only when *gate != 0 (AUTO's re-run, decided on the
@@ -592,7 +626,82 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     // bf16 MFMA operands (rounded fp32 rows or bf16 data) run the fused-norm filter
     // the fused filter's plan, computed once: it sizes the tile blocks (bn_f), the occupancy,
     // the schedule and the launch of this pass
-    const FilterPlan fplan = knn_fused_supported(d) ? knn_fused_plan(d, k, nq, c->num_cus, c->fforce, max_splits(nt, k, 64 * KNN_RESCORE_CAPW)) : FilterPlan{};
+    // The int8 operand class (KNN_ALGO_GEMM_I8, fp32 data): taken when its plan exists (d = 128,
+    // k <= 32, no forced study shape) and the train set's range allows it; else this call runs
+    // the bf16 operands below unchanged.  own_train / may_cache: as for tprep below.
+    // AUTO takes the class only for a train set whose operands this context keeps (may_cache):
+    // the scale, the guard's statistics and the demotion mark live with that cache.  Without it
+    // every call would pay the scale's host round trip and the statistics passes again, and a
+    // train set the guard misjudges could never be demoted -- so such calls run the bf16
+    // operands exactly as before.  A forced context (KNN_ALGO_GEMM_I8) is not restricted.
+    float i8s = 0.0f;
+    FilterPlan iplan{};
+    if (algo == KNN_ALGO_GEMM_I8 && dtype == KNN_F32 && !gate && knn_fused_supported(d) &&
+        (c->algo != KNN_ALGO_AUTO || (c->cache_train && (tr->feat == c->h_train.p || c->cache_train_device)))) {
+        const bool own = tr->feat == c->h_train.p;
+        const bool mayc = c->cache_train && (own || c->cache_train_device);
+        const uint64_t ep = own ? c->train_epoch : 0;
+        auto& ic = c->i8c;
+        const bool hit = mayc && ic.valid && ic.feat == tr->feat && ic.n == nt && ic.d == d && ic.ld == tr->ld &&
+                         ic.gen == c->generation && ic.epoch == ep;
+        // (a cached train set the class does not take costs a call nothing more than this test)
+        if (!(hit && (!ic.ok || (ic.demoted && c->algo == KNN_ALGO_AUTO)))) {
+            iplan = knn_fused_plan(d, k, nq, c->num_cus, c->fforce, max_splits(nt, k, 64 * KNN_RESCORE_CAPW), true);
+            if (iplan.nw > 0 && !knn_fused_has_kernel(d, iplan)) iplan = FilterPlan{};
+        }
+    }
+    if (iplan.nw > 0) {
+        const bool own = tr->feat == c->h_train.p;
+        const bool mayc = c->cache_train && (own || c->cache_train_device);
+        const uint64_t ep = own ? c->train_epoch : 0;
+        auto& ic = c->i8c;
+        const bool hit = mayc && ic.valid && ic.feat == tr->feat && ic.n == nt && ic.d == d && ic.ld == tr->ld &&
+                         ic.gen == c->generation && ic.epoch == ep;
+        if (!hit) {
+            uint32_t bits = 0;
+            HIP_OR_FAIL(c, c->i8max.ensure(sizeof(uint32_t)));
+            HIP_OR_FAIL(c, hipMemsetAsync(c->i8max.p, 0, sizeof(uint32_t), st));
+            stage_begin(c, st, "i8_scale");
+            HIP_OR_FAIL(c, knn_launch_absmax((const float*)tr->feat, nt, tr->ld, d, c->i8max.as<uint32_t>(), st));
+            stage_end(c, st);
+            HIP_OR_FAIL(c, hipMemcpyAsync(&bits, c->i8max.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_OR_FAIL(c, hipStreamSynchronize(st));
+            float mx;
+            std::memcpy(&mx, &bits, sizeof(float));
+            // finite and > 0, and s2 = 2 s^2 far from the ends of the exponent range (norms at
+            // or above 2^125 leave the GEMM form anyway).  max tn / s2 <= d 127^2 / 2 < 2^30 then
+            // holds for every train set: one scale bounds every element by 127 s.
+            const float s = mx / 127.0f * c->i8_coarsen;
+            bool ok = bits < 0x7f800000u && s >= 0x1p-40f && s <= 0x1p40f;
+            // AUTO's guard against a scale set by outliers: E8 <= R Ebf, the train set's largest row
+            // residual |t - rt| under the int8 and under the bf16 rounding (two statistics passes
+            // of k_row_norms, on the call that builds the operands only; they leave the cached
+            // bf16 operands' statistics stale, so those are rebuilt below).  A forced context and
+            // the test hook's coarser steps skip it.
+            if (ok && c->algo == KNN_ALGO_AUTO && c->i8_coarsen == 1.0f) {
+                HIP_OR_FAIL(c, c->tmax.ensure(sizeof(float4) * ((nt + 63) / 64 + 1)));
+                HIP_OR_FAIL(c, c->tsmax.ensure(sizeof(float4)));
+                HIP_OR_FAIL(c, c->tctrl.ensure(4 * sizeof(int32_t)));
+                c->tprep.valid = false;
+                float4 e[2];
+                for (int pass = 0; pass < 2; pass++) {
+                    HIP_OR_FAIL(c, knn_launch_row_norms(tr->feat, dtype, nt, tr->ld, d, c->tnorm.as<float>(),
+                                                        c->tctrl.as<int32_t>(), nullptr, nullptr, 0.0f, st,
+                                                        c->tmax.as<float4>(), nullptr, nullptr, 1.0f, pass ? s : 0.0f));
+                    HIP_OR_FAIL(c, knn_launch_tile_stat_max(c->tmax.as<float4>(), (nt + 63) / 64, c->tsmax.as<float4>(), st));
+                    HIP_OR_FAIL(c, hipMemcpyAsync(&e[pass], c->tsmax.p, sizeof(float4), hipMemcpyDeviceToHost, st));
+                }
+                HIP_OR_FAIL(c, hipStreamSynchronize(st));
+                ok = e[1].y <= KNN_I8_AUTO_R * e[0].y;  // (false for NaN)
+            }
+            ic = {tr->feat, nt, d, tr->ld, c->generation, ep, mayc, s, ok, false};
+        }
+        // (AUTO leaves a demoted train set to the bf16 operands; a forced context keeps int8)
+        if (ic.ok && !(ic.demoted && c->algo == KNN_ALGO_AUTO)) i8s = ic.s;
+    }
+    const bool i8 = i8s > 0.0f;
+    const FilterPlan fplan = i8 ? iplan
+                           : knn_fused_supported(d) ? knn_fused_plan(d, k, nq, c->num_cus, c->fforce, max_splits(nt, k, 64 * KNN_RESCORE_CAPW)) : FilterPlan{};
     const bool fused = (felem == ELEM_ROUND || felem == ELEM_BF16) && knn_fused_supported(d) && fplan.nw > 0;
     float coef, eta;
     if (fused) {
@@ -615,7 +724,7 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     const bool may_cache = c->cache_train && (own_train || c->cache_train_device);
     auto& tp = c->tprep;
     const bool prep_hit = fused_tn && !gate && may_cache && tp.valid && tp.feat == tr->feat && tp.n == nt &&
-                          tp.d == d && tp.ld == tr->ld && tp.dtype == dtype && tp.bn == bn_f &&
+                          tp.d == d && tp.ld == tr->ld && tp.dtype == dtype && tp.bn == bn_f && tp.i8 == (i8 ? 1 : 0) &&
                           tp.gen == c->generation && tp.epoch == (own_train ? c->train_epoch : 0);
     if (fused_tn && !gate) {
         HIP_OR_FAIL(c, c->tctrl.ensure(4 * sizeof(int32_t)));
@@ -628,7 +737,8 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
             HIP_OR_FAIL(c, hipMemsetAsync(c->tctrl.p, 0, 4 * sizeof(int32_t), st));
             HIP_OR_FAIL(c, knn_launch_row_norms(tr->feat, dtype, nt, tr->ld, d, c->tnorm.as<float>(),
                                                 c->tctrl.as<int32_t>(), c->tctrl.as<uint32_t>() + 2,
-                                                c->tnp.as<float>(), 1.0f - coef, st, c->tmax.as<float4>(), nullptr));
+                                                c->tnp.as<float>(), 1.0f - coef, st, c->tmax.as<float4>(), nullptr,
+                                                nullptr, 1.0f, i8s));
             HIP_OR_FAIL(c, knn_launch_tile_stat_max(c->tmax.as<float4>(), (nt + 63) / 64, c->tsmax.as<float4>(), st));
         }
         HIP_OR_FAIL(c, hipMemcpyAsync(c->ctrl.p, c->tctrl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
@@ -640,10 +750,11 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
         if (fused && !gate)
             HIP_OR_FAIL(c, knn_launch_tile_stat_max(c->tmax.as<float4>(), (nt + 63) / 64, c->tsmax.as<float4>(), st));
     }
-    // (the fused filter's query operand is rn(-2 q): its rounding is bounded for rn(-2 q) / -2)
+    // (the fused filter's query operand is rn(-2 q): its rounding is bounded for rn(-2 q) / -2;
+    // the int8 class quantises q itself with the train set's scale -- the -2 is in s2)
     HIP_OR_FAIL(c, knn_launch_row_norms(te->feat, dtype, nq, te->ld, d, c->qnorm.as<float>(),
                                         c->ctrl.as<int32_t>(), nullptr, nullptr, 0.0f, st, nullptr, gate,
-                                        fused ? c->qstat.as<float2>() : nullptr, -2.0f));
+                                        fused ? c->qstat.as<float2>() : nullptr, -2.0f, i8s));
     stage_end(c, st);
     // (a norm >= 2^125 sets GEMM_UNSAFE in the status word: the filter then skips and the
     // rescore sends every query to the exact fallback scan -- decided on the device)
@@ -664,22 +775,31 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
         // The gated split re-run never takes this branch (the fused filter is the first pass).
         const int64_t ntf = ntp + 256;  // (256 pad rows: a piece's scan may run up to 224 rows past
                                         //  its own -- seven 32-row tiles of an octet, k_gemm_fused)
-        const size_t tb = (size_t)bn_f * 2 * d + 4 * bn_f + 16;
+        // (int8 class: rows of d bytes, the header's bn words the integer norm terms, k_i8_rows)
+        const size_t tb = (size_t)bn_f * (i8 ? 1 : 2) * d + 4 * bn_f + 16;
         HIP_OR_FAIL(c, c->split_q.ensure(sizeof(uint16_t) * (size_t)d * nq));
         stage_begin(c, st, "aug");
         if (!prep_hit) {
             HIP_OR_FAIL(c, c->tblk.ensure(tb * (size_t)(ntf / bn_f)));
-            HIP_OR_FAIL(c, knn_launch_tn_rows(tr->feat, dtype, ntf, nt, tr->ld, d, c->tnorm.as<float>(), 1.0f,
-                                              c->tblk.p, c->tmax.as<float4>(), bn_f, st, nullptr));
+            if (i8)
+                HIP_OR_FAIL(c, knn_launch_i8_rows((const float*)tr->feat, ntf, nt, tr->ld, d, c->tnorm.as<float>(), i8s,
+                                                  c->tblk.p, c->tmax.as<float4>(), bn_f, st));
+            else
+                HIP_OR_FAIL(c, knn_launch_tn_rows(tr->feat, dtype, ntf, nt, tr->ld, d, c->tnorm.as<float>(), 1.0f,
+                                                  c->tblk.p, c->tmax.as<float4>(), bn_f, st, nullptr));
         }
-        HIP_OR_FAIL(c, knn_launch_tn_rows(te->feat, dtype, nq, nq, te->ld, d, nullptr, -2.0f, c->split_q.p, nullptr,
-                                          0, st, nullptr));
+        if (i8)
+            HIP_OR_FAIL(c, knn_launch_i8_rows((const float*)te->feat, nq, nq, te->ld, d, nullptr, i8s, c->split_q.p,
+                                              nullptr, 0, st));
+        else
+            HIP_OR_FAIL(c, knn_launch_tn_rows(te->feat, dtype, nq, nq, te->ld, d, nullptr, -2.0f, c->split_q.p, nullptr,
+                                              0, st, nullptr));
         stage_end(c, st);
         ftrain = c->tblk.p; ftest = c->split_q.p;
         fld_t = fld_q = d;
         c->stats[8] = prep_hit ? 1 : 0;
         if (may_cache)
-            tp = {tr->feat, nt, d, tr->ld, dtype, bn_f, c->generation, own_train ? c->train_epoch : 0, true};
+            tp = {tr->feat, nt, d, tr->ld, dtype, bn_f, c->generation, own_train ? c->train_epoch : 0, true, i8 ? 1 : 0};
     } else if (fused) {
         // (study build KNN_STUDY_AUG64, d = 64) augmented bf16 rows: train [rn(t) | tn split],
         // queries [-2 rn(q) | 1 1 1]
@@ -770,6 +890,7 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     g.cnt = c->cnt.as<int32_t>(); g.cand = c->cand.as<CandRec>(); g.cap = cap; g.cap_seg = cap / nseg;
     g.qstat = fused ? c->qstat.as<float2>() : nullptr;
     g.tsmax = fused ? c->tsmax.as<float4>() : nullptr;
+    g.i8_s2 = i8 ? knn_i8_s2_of(i8s) : 0.0f;
     // per-XCD scan cursors for the multi-segment schedule (B: filter traffic beyond L2 664 ->
     // 494 GB per launch, time unchanged; with one segment or the balanced schedule they saved
     // nothing: r03s).  KNN_NO_SCAN_CURSOR=1 turns them off (a diagnostic; same results).
@@ -844,6 +965,8 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
         c->stats[5] = fused;
         c->stats[9] = fused ? (plan.m16 ? 16 : 32) : 0;
         c->stats[10] = fused ? 32 * plan.qg : 0;
+        c->stats[11] = i8 ? 1 : 0;
+        if (i8) c->i8_pass_nq = nq;
         c->subs = subs;
     } else {
         c->rerun_stats[0] = nseg;
@@ -990,7 +1113,8 @@ knn_status validate_call(knn_ctx* c, const knn_dataset* tr, const knn_dataset* t
     return KNN_OK;
 }
 
-// One pass of the pipeline over a query set, enqueued on st with no host synchronisation;
+// One pass of the pipeline over a query set, enqueued on st with no host synchronisation (but for
+// the int8 operand class's scale read-back on the call that builds its train operands, run_gemm);
 // the status word is copied to ctrl_copy (pinned host, optional) at the end.
 knn_status predict_enqueue(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t k, int32_t C,
                            const QueryOut& out, hipStream_t st, int algo, int32_t* ctrl_copy) {
@@ -1035,12 +1159,18 @@ knn_status predict_enqueue(knn_ctx* c, const knn_dataset* tr, const knn_dataset*
 // stats of a finished pass (status word in ctrl)
 void pass_stats(knn_ctx* c, const int32_t* ctrl, bool gemm) {
     c->stats[1] += ctrl[1];
+    // an int8 pass that sent more than 1/64 of its queries to the exact fallback: the scale
+    // misjudged these rows (results are exact either way)
+    // (or so many that AUTO re-ran the call with the split operands, which zeroes the count)
+    if (gemm && c->stats[11] == 1 && c->i8c.valid && (ctrl[3] || (int64_t)ctrl[1] > c->i8_pass_nq / 64))
+        c->i8c.demoted = true;
     if (gemm && ctrl[3]) {
         // the split re-run ran: its segments / operand type describe the results
         c->stats[4] = 1;
         c->stats[2] = c->rerun_stats[0];
         c->stats[3] = c->rerun_stats[1];
         c->stats[5] = c->rerun_stats[2];
+        c->stats[11] = 0;
     }
 }
 
@@ -1062,7 +1192,7 @@ knn_dataset offset_rows(const knn_dataset& x, int64_t r0, int64_t n) {
 
 void reset_stats(knn_ctx* c) {
     c->stages.clear();
-    for (int i = 0; i < 11; i++) c->stats[i] = 0;
+    for (int i = 0; i < 12; i++) c->stats[i] = 0;
     c->stats[3] = -1;
 }
 
@@ -1861,7 +1991,7 @@ int32_t knn_stage_times(const knn_ctx* c, const char** names, float* ms, int32_t
 
 int32_t knn_last_stats(const knn_ctx* c, int64_t* out, int32_t n) {
     if (!c || !out) return 0;
-    int32_t m = std::min(n, 11);
+    int32_t m = std::min(n, 12);
     for (int32_t i = 0; i < m; i++) out[i] = c->stats[i];
     return m;
 }
@@ -1893,6 +2023,27 @@ knn_status knn_mfma_probe_bf16(knn_ctx* c, const uint16_t* d_a, const uint16_t* 
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     HIP_OR_FAIL(c, knn_launch_mfma_probe(d_a, d_b, K, d_out, st));
     HIP_OR_FAIL(c, hipStreamSynchronize(st));
+    return KNN_OK;
+}
+
+knn_status knn_mfma_probe_i8(knn_ctx* c, const int8_t* d_a, const int8_t* d_b, int32_t K, int32_t* d_out,
+                             void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    if (K <= 0 || K % 32 || !d_a || !d_b || !d_out) return fail(c, KNN_EINVAL, "mfma probe: K must be a positive multiple of 32");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIP_OR_FAIL(c, knn_launch_mfma_probe_i8(d_a, d_b, K, d_out, st));
+    HIP_OR_FAIL(c, hipStreamSynchronize(st));
+    return KNN_OK;
+}
+
+// test hook (not in knn_amd.h): the int8 operand class's step times mul (a factor in [1, 8]) on
+// this context from now on; the cached scale and operands are dropped
+knn_status knn_debug_set_i8_coarsen(knn_ctx* c, float mul) {
+    if (!c || !(mul >= 1.0f && mul <= 8.0f)) return KNN_EINVAL;
+    c->i8_coarsen = mul;
+    c->i8c.valid = c->tprep.valid = false;
     return KNN_OK;
 }
 

@@ -198,6 +198,50 @@ __device__ __forceinline__ float4 load4(const bf16_t* p) {
                        __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
 }
 
+// ---------------------------------------------------------------------------------
+// The int8 filter operand class (fp32 data, KNN_ALGO_GEMM_I8; DESIGN.md "int8 filter operands").
+// One symmetric scale per train set, s = max|t| / 127; a row element x becomes the integer
+//   n = clamp(rne(x / s), -127, 127)      (-128 is never produced; NaN -> -127)
+// and stands for the real number s n in the certificate.  Queries use the train set's s (a
+// query outside the train range saturates; its residual is measured like any other).  With
+// s2 = fl(2 s s) the filter's value is y* = tn - s2 (nq . nt), an exact integer sum times s2.
+// Every kernel that quantises, and the host tests, go through these functions.
+// ---------------------------------------------------------------------------------
+__host__ __device__ inline int knn_i8_quant(float x, float s) {
+    float r = rintf(x / s);
+    if (!(r >= -127.0f)) r = -127.0f;
+    if (r > 127.0f) r = 127.0f;
+    return (int)r;
+}
+__host__ __device__ inline float knn_i8_s2(float s) { return 2.0f * s * s; }
+// the integer the accumulator of a row starts from (negated): about tn / s2, in [0, 2^30]
+__host__ __device__ inline int32_t knn_i8_norm_q(float tn, float s2) {
+    float r = floorf(tn / s2);
+    if (!(r >= 0.0f)) r = 0.0f;
+    if (r > 0x1p30f) r = 0x1p30f;
+    return (int32_t)r;
+}
+// an upper bound of |tn - s2 n| (binary64: the product errs by <= 2^-53 s2 n, covered by the
+// tn term; the conversion and the factor round up)
+__host__ __device__ inline float knn_i8_norm_res(float tn, float s2, int32_t n) {
+    double e = (double)tn - (double)s2 * (double)n;
+    e = e < 0.0 ? -e : e;
+    return (float)e * (1.0f + 0x1p-20f) + (tn < 0.0f ? -tn : tn) * 0x1p-40f + 0x1p-126f;
+}
+// The integer fast test.  ti = knn_i8_fast_thr(tf, s2) is an integer <= -tf / s2 (real
+// arithmetic, s2 > 0), so for every integer a: -s2 a <= tf  =>  a >= -tf / s2 >= ti -- the
+// test a >= ti passes a superset of the float test.  The division rounds once (relative
+// 2^-24); 2^-20 |x| + 1 below x covers it and the floor.  tf = -inf (no valid query): INT32_MAX,
+// which no accumulator reaches; tf = +inf or NaN: INT32_MIN, everything passes.
+__host__ __device__ inline int32_t knn_i8_fast_thr(float tf, float s2) {
+    float x = -tf / s2;
+    if (x >= 0x1p31f) return 0x7fffffff;
+    if (!(x > -0x1p31f)) return (int32_t)0x80000000u;
+    x = floorf(fmaf(x < 0.0f ? x : -x, 0x1p-20f, x) - 1.0f);
+    if (!(x > -0x1p31f)) return (int32_t)0x80000000u;
+    return (int32_t)x;
+}
+
 // ordered uint <-> float (monotone for all non-NaN floats)
 __device__ __forceinline__ uint32_t f2o(float f) {
     uint32_t b = __float_as_uint(f);

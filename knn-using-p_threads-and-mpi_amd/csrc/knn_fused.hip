@@ -17,7 +17,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "knn_device.h"
@@ -198,7 +200,92 @@ hipError_t knn_launch_tn_rows(const void* x, int elem, int64_t n, int64_t n_vali
 }
 
 // ---------------------------------------------------------------------------------
-// k_tile_stat_max: out = {max tn, max |t - rt|, max |rt|, 0} over the n 64-row tile statistics
+// k_i8_rows: operand rows of the int8 operand class (fp32 x, the train set's scale s).
+//   queries (norms == NULL): [n][d] int8 = knn_i8_quant(x, s)
+//   train: blocks of bn rows, [bn][d] int8 | bn int32 -knn_i8_norm_q(tn, s2) (the accumulators'
+//   start) | the enclosing 64-row tile's statistics (k_row_norms with i8s = s) -- the same image
+//   shape as k_tn_rows at half the row bytes.  Rows n_valid .. n-1: zero features and -2^30, below
+//   every valid row's term (run_gemm admits a train set only when max tn / s2 < 2^30), and their
+//   indices are past row_end.  n % bn == 0.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_i8_rows(const float* __restrict__ x, int64_t n, int64_t n_valid, int ld, int d,
+                                                 const float* __restrict__ norms, float s,
+                                                 unsigned char* __restrict__ out, const float4* __restrict__ tstat,
+                                                 int bn) {
+    const int per_row = d >> 2;
+    auto quad = [&](int64_t r, int c) -> uint32_t {
+        if (r >= n_valid) return 0u;
+        const float4 v = load4(x + r * ld + c);
+        return ((uint32_t)knn_i8_quant(v.x, s) & 0xffu) | (((uint32_t)knn_i8_quant(v.y, s) & 0xffu) << 8) |
+               (((uint32_t)knn_i8_quant(v.z, s) & 0xffu) << 16) | (((uint32_t)knn_i8_quant(v.w, s) & 0xffu) << 24);
+    };
+    if (!norms) {
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n * per_row; i += (int64_t)gridDim.x * 256) {
+            const int64_t r = i / per_row;
+            const int c = (int)(i - r * per_row) * 4;
+            *reinterpret_cast<uint32_t*>(out + r * d + c) = quad(r, c);
+        }
+        return;
+    }
+    const float s2 = knn_i8_s2(s);
+    const int64_t per_tile = (int64_t)bn * per_row + bn + 1;
+    const int64_t tb = (int64_t)bn * d + 4 * bn + 16;
+    const int64_t nvt = (n_valid + 63) >> 6;  // 64-row tiles with statistics
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (n / bn) * per_tile; i += (int64_t)gridDim.x * 256) {
+        const int64_t T = i / per_tile;
+        const int64_t l = i - T * per_tile;
+        const int64_t r0 = T * bn;
+        unsigned char* blk = out + T * tb;
+        if (l < (int64_t)bn * per_row) {
+            const int rr = (int)(l / per_row);
+            const int c = (int)(l - (int64_t)rr * per_row) * 4;
+            *reinterpret_cast<uint32_t*>(blk + (int64_t)rr * d + c) = quad(r0 + rr, c);
+        } else if (l < (int64_t)bn * per_row + bn) {
+            const int rr = (int)(l - (int64_t)bn * per_row);
+            const int64_t r = r0 + rr;
+            *reinterpret_cast<int32_t*>(blk + (int64_t)bn * d + 4 * rr) = r < n_valid ? -knn_i8_norm_q(norms[r], s2) : -(1 << 30);
+        } else {
+            const int64_t t64 = r0 >> 6;
+            *reinterpret_cast<float4*>(blk + (int64_t)bn * d + 4 * bn) =
+                t64 < nvt ? tstat[t64] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    }
+}
+
+hipError_t knn_launch_i8_rows(const float* x, int64_t n, int64_t n_valid, int ld, int d, const float* norms, float s,
+                              void* out, const float4* tstat, int bn, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (d % 16 || ld % 4 || !(s > 0.0f) || (norms && (bn <= 0 || n % bn))) return hipErrorInvalidValue;
+    const int64_t total = norms ? (n / bn) * ((int64_t)bn * (d / 4) + bn + 1) : n * (d / 4);
+    hipLaunchKernelGGL(k_i8_rows, dim3(elementwise_grid(total)), dim3(256), 0, st, x, n, n_valid, ld, d, norms, s,
+                       (unsigned char*)out, tstat, bn);
+    KNN_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+float knn_i8_s2_of(float s) { return knn_i8_s2(s); }
+
+// host views of the int8 operand rule (knn_device.h), for tests/test_i8_quant_cpu.py.  No GPU call.
+extern "C" int knn_i8_debug_quant(const float* x, long long n, float s, signed char* out) {
+    for (long long i = 0; i < n; i++) out[i] = (signed char)knn_i8_quant(x[i], s);
+    return 0;
+}
+// out[3 i] = {knn_i8_norm_q(tn, s2), the bits of knn_i8_norm_res(tn, s2, that), knn_i8_fast_thr(tf, s2)}
+extern "C" int knn_i8_debug_fast(const float* tn, const float* tf, const float* s2, long long n, int* out) {
+    for (long long i = 0; i < n; i++) {
+        const int32_t nr = knn_i8_norm_q(tn[i], s2[i]);
+        const float res = knn_i8_norm_res(tn[i], s2[i], nr);
+        uint32_t bits;
+        memcpy(&bits, &res, 4);
+        out[3 * i] = nr;
+        out[3 * i + 1] = (int)bits;
+        out[3 * i + 2] = knn_i8_fast_thr(tf[i], s2[i]);
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------
+// k_tile_stat_max: out = {max tn, max |t - rt|, max |rt|, max |tn - s2 n| (int8 operands)} over the n 64-row tile statistics
 // (k_row_norms' tstat): the fused filter's fast-test tile term (a.tsmax).  One block.
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_tile_stat_max(const float4* __restrict__ t, int64_t n, float4* __restrict__ out) {
@@ -206,17 +293,18 @@ __global__ __launch_bounds__(256) void k_tile_stat_max(const float4* __restrict_
     float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // (the statistics are >= 0)
     for (int64_t i = threadIdx.x; i < n; i += 256) {
         const float4 v = t[i];
-        m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z);
+        m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         m.x = fmaxf(m.x, __shfl_xor(m.x, o)); m.y = fmaxf(m.y, __shfl_xor(m.y, o)); m.z = fmaxf(m.z, __shfl_xor(m.z, o));
+        m.w = fmaxf(m.w, __shfl_xor(m.w, o));
     }
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
         float4 r = part[0];
-        for (int w = 1; w < 4; w++) { r.x = fmaxf(r.x, part[w].x); r.y = fmaxf(r.y, part[w].y); r.z = fmaxf(r.z, part[w].z); }
+        for (int w = 1; w < 4; w++) { r.x = fmaxf(r.x, part[w].x); r.y = fmaxf(r.y, part[w].y); r.z = fmaxf(r.z, part[w].z); r.w = fmaxf(r.w, part[w].w); }
         *out = r;
     }
 }
@@ -283,10 +371,44 @@ __device__ __forceinline__ void fused_pace(int32_t* p, int steps) {
     }
 }
 
-template <int RB, int NBUF, int NW, int QG, int RG, int KR>
+// The 16 compares of a lane's accumulator values against one operand, each folded into a mask by
+// an add-with-carry (the lane scans of fused_piece's slow path; CMP: the element's compare)
+#define KNN_FUSED_SCAN16(CMP)                                                                   \
+    CMP " vcc, %17, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                            \
+    CMP " vcc, %16, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                            \
+    CMP " vcc, %15, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                            \
+    CMP " vcc, %14, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                            \
+    CMP " vcc, %13, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                            \
+    CMP " vcc, %12, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                            \
+    CMP " vcc, %11, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                            \
+    CMP " vcc, %10, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                            \
+    CMP " vcc, %9, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                             \
+    CMP " vcc, %8, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                             \
+    CMP " vcc, %7, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                             \
+    CMP " vcc, %6, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                             \
+    CMP " vcc, %5, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                             \
+    CMP " vcc, %4, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                             \
+    CMP " vcc, %3, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"                             \
+    CMP " vcc, %2, %1\n\tv_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
+#define KNN_FUSED_SCAN16_Y(Y) "v"(Y[0]), "v"(Y[1]), "v"(Y[2]), "v"(Y[3]), "v"(Y[4]), "v"(Y[5]), "v"(Y[6]), "v"(Y[7]), \
+    "v"(Y[8]), "v"(Y[9]), "v"(Y[10]), "v"(Y[11]), "v"(Y[12]), "v"(Y[13]), "v"(Y[14]), "v"(Y[15])
+
+// I8: the int8 operand class (DESIGN.md "int8 filter operands"): rows of RB = d int8 bytes on
+// v_mfma_i32_32x32x32_i8 (K = 32 per k-step, the same 16 bytes per lane and k-step), the tile
+// header's BN words int32 -n_r (n_r ~ tn / s2), integer accumulators
+//   a = nq . nt - n_r,    y* = tn - s2 nq . nt = (tn - s2 n_r) - s2 a,   |tn - s2 n_r| <= nu,
+// the fast test max_r a_r >= ti (ti: knn_i8_fast_thr of the same tf, which carries nu) and the
+// slow path's G = qn - s2 float(a) with nu in the band.  Three sites differ from the bf16 form:
+// the MFMA, the accumulators' start, the fast test and its scans' compares.
+template <int RB, int NBUF, int NW, int QG, int RG, int KR, bool I8>
 __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int qt, const int seg,
                                             const int64_t row_begin, const int64_t row_end,
                                             const int64_t rot_units, int& steps) {
+    typedef typename std::conditional<I8, int, float>::type AccT;  // an accumulator value
+    typedef AccT accx16 __attribute__((ext_vector_type(16)));
+    typedef typename std::conditional<I8, int4, float4>::type accx4;  // one header read of four accumulator starts
+    typedef int intx4 __attribute__((ext_vector_type(4)));
+    constexpr int EB = I8 ? 1 : 2;  // bytes per operand element
     // TN (RB = 2d, the product): train tiles carry their rows' norms in a header, and each
     // accumulator starts from them (the MFMA's C operand) -- no augmented k-step.  Otherwise
     // (RB = 2d + 32, the KNN_STUDY_AUG64 build at d = 64) the norm rides in 16 augmented columns
@@ -320,6 +442,8 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     constexpr bool RL = KR > 0;                   // thresholds from per-lane register lists (else LDS heaps)
     // (QG = 2 on 64-row tiles, four accumulators, was tried at d = 64: 1.5 KB of scratch spills)
     static_assert(QG == 1 || (QG == 2 && RG == 1 && RL), "64-query waves: 32-row tiles, register lists");
+    static_assert(!I8 || (RL && KR <= 32 && TN && PAIR && KNN_FUSED_TF_GLOBAL && !KNN_STUDY_NO_NORM),
+                  "int8 operands: the register-list shapes, header norms, the global tile term");
     constexpr int LL = KR == 104 ? 52 : KR == 8 ? 8 : 16;  // register list length (one per lane half)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* tiles = smem;                                     // [NBUF][TILE]
@@ -334,7 +458,8 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     const int k = a.k;
     const float INF = __uint_as_float(0x7f800000u);
     const float coef = a.coef, eta = a.eta;
-    const int64_t ldb = (int64_t)a.ld_t * 2;  // augmented train row pitch, bytes
+    const int64_t ldb = (int64_t)a.ld_t * EB;  // train row pitch, bytes
+    [[maybe_unused]] const float s2 = a.i8_s2;  // (I8)
     const unsigned char* trainb = reinterpret_cast<const unsigned char*>(a.train);
 
     if constexpr (!RL) {
@@ -358,7 +483,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         q[g] = (int64_t)qt * BM + jl[g];
         qvalid[g] = q[g] < a.nq;
         const unsigned char* qrow = reinterpret_cast<const unsigned char*>(a.test) +
-                                    (qvalid[g] ? q[g] : 0) * (int64_t)a.ld_q * 2;
+                                    (qvalid[g] ? q[g] : 0) * (int64_t)a.ld_q * EB;
 #pragma unroll
         for (int s = 0; s < NS; s++)
             qf[g][s] = qvalid[g] ? *reinterpret_cast<const uint4*>(qrow + 32 * s + 16 * h)
@@ -397,15 +522,20 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // band.  KNN_FUSED_TF_GLOBAL=0: the per-tile term (round 5).
     constexpr bool TFG = KNN_FUSED_TF_GLOBAL && PAIR && TN;
     float tk[QG], tfc[QG];  // (TFG) the tile term and the fast-test threshold, per query group
+    [[maybe_unused]] int tic[QG];  // (I8) the integer fast-test threshold of tfc
     if constexpr (TFG) {
         const float4 smax = *a.tsmax;
 #pragma unroll
-        for (int g = 0; g < QG; g++) tk[g] = fmaf(coef + 0x1p-18f, smax.x, fmaf(qe2[g], smax.y, eq2[g] * smax.z));
+        for (int g = 0; g < QG; g++) {
+            tk[g] = fmaf(coef + 0x1p-18f, smax.x, fmaf(qe2[g], smax.y, eq2[g] * smax.z));
+            if constexpr (I8) tk[g] += smax.w * (1.0f + 0x1p-20f);  // nu: the integer norm terms' residual
+        }
     }
     float tfb[QG];     // tf without the tile term
     auto make_tfb = [&](int g) __attribute__((always_inline)) {
         tfb[g] = qvalid[g] ? ((thr[g] - qn[g]) + fmaf(coef, qn[g], eta)) + 0x1p-18f * (fabsf(thr[g]) + qn[g]) : -INF;
         if constexpr (TFG) tfc[g] = tfb[g] + tk[g];
+        if constexpr (I8) tic[g] = knn_i8_fast_thr(tfc[g], s2);
     };
 #pragma unroll
     for (int g = 0; g < QG; g++) make_tfb(g);
@@ -431,6 +561,11 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         TQ r;
 #pragma unroll
         for (int g = 0; g < QG; g++) r.v[g] = make_float2(tx, fmaf(qe2[g], ty, eq2[g] * tz));
+        if constexpr (I8) {  // the tile's nu joins the band
+            const float nu = *reinterpret_cast<const float*>(tiles + buf * TILE + HDR + 4 * BN + 12) * (1.0f + 0x1p-20f);
+#pragma unroll
+            for (int g = 0; g < QG; g++) r.v[g].y += nu;
+        }
         return r;
     };
 
@@ -516,10 +651,10 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // ---- one tile's MFMAs into X; in between, the fast test of the previous tile (Y): a v_min3
     // chain per accumulator; returns bit 16c (x 0xffff) when some lane of accumulator c holds a
     // passing value (the slow path builds the value set, pass_set)
-    [[maybe_unused]] floatx16 cnorm;  // (KNN_ABLATE_NO_NORM only)
+    [[maybe_unused]] accx16 cnorm;  // (KNN_ABLATE_NO_NORM only)
     if constexpr (KNN_STUDY_NO_NORM) {
 #pragma unroll
-        for (int r = 0; r < 16; r++) cnorm[r] = (float)a.d * (1.0f / 3.0f);
+        for (int r = 0; r < 16; r++) cnorm[r] = (AccT)((float)a.d * (1.0f / 3.0f));
     }
     constexpr int PF = FUSED_PF / NACC;  // k-steps of A fragments read ahead
     uint4 pa[PF], pb[PF];                // PAIR: the odd step's first fragments, read early
@@ -533,8 +668,8 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
             if (RG == 2) pb[s] = *reinterpret_cast<const uint4*>(a1p + fused_frag_off(0, 0, s, STRIDE));
         }
     };
-    auto step = [&](floatx16 (&X)[NACC], floatx16 (&Y)[NACC], int buf, bool dma_on, const DmaTile& dd,
-                    const float (&tf)[QG], bool pre, float (&mn_out)[NACC]) -> uint32_t {
+    auto step = [&](accx16 (&X)[NACC], accx16 (&Y)[NACC], int buf, bool dma_on, const DmaTile& dd,
+                    const AccT (&tf)[QG], bool pre, AccT (&mn_out)[NACC]) -> uint32_t {
         const unsigned char* tile = tiles + buf * TILE;
         const unsigned char* a0p = tile + fused_frag_off(j, h, 0, STRIDE);
         const unsigned char* a1p = tile + fused_frag_off((RG == 2 ? 32 : 0) + j, h, 0, STRIDE);
@@ -548,7 +683,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
             for (int rg = 0; rg < RG; rg++) {
 #pragma unroll
                 for (int g4 = 0; g4 < 4; g4++) {
-                    const float4 v = *reinterpret_cast<const float4*>(tile + fused_norm_off(HDR, h, rg, g4));
+                    const accx4 v = *reinterpret_cast<const accx4*>(tile + fused_norm_off(HDR, h, rg, g4));
                     X[rg][4 * g4] = v.x;
                     X[rg][4 * g4 + 1] = v.y;
                     X[rg][4 * g4 + 2] = v.z;
@@ -562,11 +697,15 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
             for (int rg = 0; rg < RG; rg++) X[rg] = cnorm;
         } else {
 #pragma unroll
-            for (int rg = 0; rg < RG; rg++) X[rg] = floatx16{};
+            for (int rg = 0; rg < RG; rg++) X[rg] = accx16{};
         }
-        float mn[NACC];
+        // (I8: the running maximum -- the test is max_r a_r >= ti)
+        AccT mn[NACC];
 #pragma unroll
-        for (int c = 0; c < NACC; c++) mn[c] = INF;
+        for (int c = 0; c < NACC; c++) {
+            if constexpr (I8) mn[c] = (int)0x80000000u;
+            else mn[c] = INF;
+        }
         uint4 xa[NS], xb[NS];
 #pragma unroll
         for (int s = 0; s < PF && s < NS; s++) {
@@ -589,12 +728,21 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
             for (int cc = 0; cc < NACC; cc++) {
                 const int c = s == 0 ? NACC - 1 - cc : cc;  // (k-step 0: query group 0 last)
                 const int rg = c % RG, g = c / RG;
-                const bf16x8 A = __builtin_bit_cast(bf16x8, (RG == 2 && rg) ? xb[s] : xa[s]);
-                X[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, __builtin_bit_cast(bf16x8, qf[g][s]),
-                                                               s == 0 ? X[rg] : X[c], 0, 0, 0);
+                if constexpr (I8) {
+                    const intx4 A = __builtin_bit_cast(intx4, (RG == 2 && rg) ? xb[s] : xa[s]);
+                    X[c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A, __builtin_bit_cast(intx4, qf[g][s]),
+                                                                 s == 0 ? X[rg] : X[c], 0, 0, 0);
+                } else {
+                    const bf16x8 A = __builtin_bit_cast(bf16x8, (RG == 2 && rg) ? xb[s] : xa[s]);
+                    X[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, __builtin_bit_cast(bf16x8, qf[g][s]),
+                                                                   s == 0 ? X[rg] : X[c], 0, 0, 0);
+                }
                 if (!KNN_STUDY_NO_EPI) {
 #pragma unroll
-                    for (int v = s * VPS; v < (s + 1) * VPS && v < 16; v++) mn[c] = fminf(mn[c], Y[c][v]);
+                    for (int v = s * VPS; v < (s + 1) * VPS && v < 16; v++) {
+                        if constexpr (I8) mn[c] = max(mn[c], Y[c][v]);
+                        else mn[c] = fminf(mn[c], Y[c][v]);
+                    }
                     // computed here, beside this k-step's MFMAs: without the opaque use the
                     // compiler sinks the whole v_min3 chain into the last k-step, where it
                     // runs exposed after the final MFMA
@@ -607,7 +755,8 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         // (pass_set) -- usually one of the two
         uint32_t u = 0u;
 #pragma unroll
-        for (int c = 0; c < NACC; c++) u |= __ballot(mn[c] <= tf[c / RG]) != 0ull ? (0xffffu << (16 * c)) : 0u;
+        for (int c = 0; c < NACC; c++)
+            u |= __ballot(I8 ? mn[c] >= tf[c / RG] : mn[c] <= tf[c / RG]) != 0ull ? (0xffffu << (16 * c)) : 0u;
 #pragma unroll
         for (int c = 0; c < NACC; c++) mn_out[c] = mn[c];
         return u;
@@ -675,8 +824,12 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // certified bounds L <= D <= U of value y of query group g against tile stats tq: Delta =
     // coef (qn + tmax) + eta + rho -- the tile's maximum norm tmax >= the row's norm, a slightly
     // wider band (still L <= D <= U) for no per-value norm read
-    auto bounds = [&](int g, float y, float2 tq, float& L, float& U) __attribute__((always_inline)) {
-        const float G = qn[g] + y;
+    // (I8: y is the integer a, G = qn - s2 float(a); the conversion, the fma's rounding and s2's own
+    // are inside coef, and the tile's nu is in tq.y)
+    auto bounds = [&](int g, auto y, float2 tq, float& L, float& U) __attribute__((always_inline)) {
+        float G;
+        if constexpr (I8) G = fmaf(-s2, (float)y, qn[g]);
+        else G = qn[g] + y;
         const float dl = fmaf(coef, qn[g] + tq.x, eta) + tq.y;
         L = G - dl;
         U = G + dl;
@@ -686,14 +839,14 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // so the walk below is a runtime loop with one copy of its body -- a static walk over
     // the 16 NACC values replicates accept() per value, and the code no longer fits the
     // instruction cache (measured 10x slower on B)
-    auto yval = [&](floatx16 (&Y)[NACC], int v) __attribute__((always_inline)) -> float {
+    auto yval = [&](accx16 (&Y)[NACC], int v) __attribute__((always_inline)) -> float {
         if constexpr (NACC == 1) return Y[0][v & 15];
         else return (v >> 4) ? Y[1][v & 15] : Y[0][v & 15];
     };
     // (heap shapes) the values of Y some lane passes (bit 16c + r), for the accumulators set in
     // acc: per group of 4 values (rows 8g .. 8g+3 of the lane half) one ballot of their minimum,
     // then one v_cmp + ballot per value of the passing groups only
-    auto pass_set = [&](floatx16 (&Y)[NACC], float tf, uint32_t acc) __attribute__((always_inline)) -> uint32_t {
+    auto pass_set = [&](accx16 (&Y)[NACC], float tf, uint32_t acc) __attribute__((always_inline)) -> uint32_t {
         uint32_t u = 0u;
 #pragma unroll
         for (int c = 0; c < NACC; c++)
@@ -712,7 +865,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     };
     // immediate slow path (4-wave heap shapes): the passing values of tile tp, visited by
     // index; the two lanes of a query take turns (one heap writer at a time)
-    auto slow = [&](floatx16 (&Y)[NACC], int tp, float tf, float2 tq, uint32_t u) {
+    auto slow = [&](accx16 (&Y)[NACC], int tp, float tf, float2 tq, uint32_t u) {
         const int64_t tbase = tile_row(tp);
         u = pass_set(Y, tf, u);
         while (u) {
@@ -782,12 +935,12 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // unless the threshold is still loose).  Any processing order keeps every true neighbour:
     // a row is kept iff L <= the threshold at its turn, and the threshold is always the k-th
     // smallest U of kept rows.
-    auto lane_rounds = [&](floatx16 (&Y)[NACC], const float (&tf)[QG], const float (&mnY)[NACC], uint32_t u,
+    auto lane_rounds = [&](accx16 (&Y)[NACC], const AccT (&tf)[QG], const AccT (&mnY)[NACC], uint32_t u,
                            auto&& fn) __attribute__((always_inline)) {
 #pragma unroll
         for (int c = 0; c < NACC; c++) {
             if (!((u >> (16 * c)) & 1u)) continue;  // (wave-uniform) no lane passes in c
-            const float tfc = tf[c / RG];
+            const AccT tfc = tf[c / RG];
             // round 1, one scan of the lane's 16 values from r = 15 down to 0: the passing set as
             // a 16-bit mask m = 2m + (y_r <= tf) (v_addc_co_u32 with the compare's VCC as
             // carry-in) and the value of the LOWEST passing index (v_cndmask on the same VCC) --
@@ -800,7 +953,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
             // 4-8 % slower: r03q; the count from the compares' wave masks by scalar ops, 2.7 %
             // slower on B: r03s.)
             uint32_t m = 0u;
-            float yv = INF;
+            AccT yv = I8 ? (AccT)0 : (AccT)INF;
             int idx;
             auto pick = [](uint32_t mm) __attribute__((always_inline)) { return __ffs((int)mm) - 1; };  // lowest set bit
             if constexpr (KR <= 32) {
@@ -810,79 +963,13 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
                 // second mask of the positions equal to the minimum picks its index.  Same box (r05p):
                 // A filter 20.07 -> 19.85 ms, B 466.7 -> 463.3; C1 (k = 100: more lanes pass twice,
                 // each paying the second mask) 1677 -> 1687, so KR = 104 keeps the value scan
-                asm volatile("v_cmp_le_f32_e32 vcc, %17, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %16, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %15, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %14, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %13, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %12, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %11, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %10, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %9, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %8, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %7, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %6, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %5, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %4, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %3, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_le_f32_e32 vcc, %2, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             : "+v"(m)
-                             : "v"(tfc), "v"(Y[c][0]), "v"(Y[c][1]), "v"(Y[c][2]), "v"(Y[c][3]), "v"(Y[c][4]), "v"(Y[c][5]), "v"(Y[c][6]), "v"(Y[c][7]), "v"(Y[c][8]), "v"(Y[c][9]), "v"(Y[c][10]), "v"(Y[c][11]), "v"(Y[c][12]), "v"(Y[c][13]), "v"(Y[c][14]), "v"(Y[c][15])
-                             : "vcc");
+                if constexpr (I8) asm volatile(KNN_FUSED_SCAN16("v_cmp_ge_i32_e32") : "+v"(m) : "v"(tfc), KNN_FUSED_SCAN16_Y(Y[c]) : "vcc");
+                else asm volatile(KNN_FUSED_SCAN16("v_cmp_le_f32_e32") : "+v"(m) : "v"(tfc), KNN_FUSED_SCAN16_Y(Y[c]) : "vcc");
                 yv = mnY[c];
                 if (__ballot((m & (m - 1u)) != 0u)) {
                     uint32_t e = 0u;
-                    asm volatile("v_cmp_eq_f32_e32 vcc, %17, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %16, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %15, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %14, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %13, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %12, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %11, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %10, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %9, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %8, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %7, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %6, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %5, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %4, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %3, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                             "v_cmp_eq_f32_e32 vcc, %2, %1\n\t"
-                             "v_addc_co_u32_e32 %0, vcc, %0, %0, vcc\n\t"
-                                 : "+v"(e)
-                                 : "v"(yv), "v"(Y[c][0]), "v"(Y[c][1]), "v"(Y[c][2]), "v"(Y[c][3]), "v"(Y[c][4]), "v"(Y[c][5]), "v"(Y[c][6]), "v"(Y[c][7]), "v"(Y[c][8]), "v"(Y[c][9]), "v"(Y[c][10]), "v"(Y[c][11]), "v"(Y[c][12]), "v"(Y[c][13]), "v"(Y[c][14]), "v"(Y[c][15])
-                                 : "vcc");
+                    if constexpr (I8) asm volatile(KNN_FUSED_SCAN16("v_cmp_eq_i32_e32") : "+v"(e) : "v"(yv), KNN_FUSED_SCAN16_Y(Y[c]) : "vcc");
+                    else asm volatile(KNN_FUSED_SCAN16("v_cmp_eq_f32_e32") : "+v"(e) : "v"(yv), KNN_FUSED_SCAN16_Y(Y[c]) : "vcc");
                     idx = pick(m & e);
                 } else {
                     idx = pick(m);
@@ -948,7 +1035,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
                 for (int round = 1; round < 16; round++) {
                     if (!__ballot(m != 0u)) break;
                     idx = pick(m);
-                    yv = INF;
+                    yv = I8 ? (AccT)0 : (AccT)INF;
                     // the value at idx: compare + select per value in one asm block (the
                     // compiler's form pads each pair with a hazard s_nop)
                     asm volatile("v_cmp_eq_u32_e32 vcc, 0, %1\n\t"
@@ -1007,13 +1094,13 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
             }
         }
     };
-    auto slow_rl = [&](floatx16 (&Y)[NACC], int tp, const float (&tf)[QG], const TQ& tq, const float (&mnY)[NACC],
+    auto slow_rl = [&](accx16 (&Y)[NACC], int tp, const AccT (&tf)[QG], const TQ& tq, const AccT (&mnY)[NACC],
                        uint32_t u) {
         if constexpr (RL) {
             const int64_t tbase = tile_row(tp);
             // (the band's half-width hoisted per tile and 32-bit row compares measured no faster:
             // r05q)
-            auto visit = [&](int c, int idx, float yv) __attribute__((always_inline)) {
+            auto visit = [&](int c, int idx, AccT yv) __attribute__((always_inline)) {
                 const int g = c / RG;
                 const int row = 32 * (c % RG) + (idx & 3) + 8 * (idx >> 2) + 4 * h;
                 const int64_t t = tbase + row;
@@ -1055,7 +1142,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     };
     // (the heap shapes visit the passing positions wave-wide: per value only a queue append,
     // so the lane-parallel scan would cost more than it saves -- C1 259.8 vs 273.3 ms, r03p)
-    auto record = [&](floatx16 (&Y)[NACC], int tp, float tf, float2 tq, uint32_t u) {
+    auto record = [&](accx16 (&Y)[NACC], int tp, float tf, float2 tq, uint32_t u) {
         const int64_t tbase = tile_row(tp);
         u = pass_set(Y, tf, u);
         while (u) {
@@ -1083,9 +1170,9 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         }
     };
 
-    floatx16 accA[NACC], accB[NACC];
+    accx16 accA[NACC], accB[NACC];
 #pragma unroll
-    for (int c = 0; c < NACC; c++) accA[c] = accB[c] = floatx16{};
+    for (int c = 0; c < NACC; c++) accA[c] = accB[c] = accx16{};
     __syncthreads();  // LDS init is complete before any DMA lands; blk_rot is written
     rot = __builtin_amdgcn_readfirstlane(*blk_rot);
 #pragma unroll
@@ -1176,7 +1263,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         }
     };
     // one tile of the scan; posc: the tile's place in its barrier group (it % GRP), static
-    auto iter = [&](auto posc, floatx16 (&X)[NACC], floatx16 (&Y)[NACC], int it) {
+    auto iter = [&](auto posc, accx16 (&X)[NACC], accx16 (&Y)[NACC], int it) {
         constexpr int POS = decltype(posc)::value;
         if constexpr (RL && QG == 1 && KR <= 32 && KNN_FUSED_LIST_SHARE) {
             if (a.lshare && list_share_now(it)) exchange_lists();
@@ -1243,10 +1330,13 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         }
         const bool dma_on = !FRONT && !KNN_STUDY_NO_DMA && it + AHEAD < ntiles;
         const DmaTile dd = dma_desc((it + AHEAD) % NBUF, it + AHEAD);
-        float tf[QG];
+        AccT tf[QG];
 #pragma unroll
-        for (int g = 0; g < QG; g++) tf[g] = it > 0 ? (TFG ? tfc[g] : tf_of(g, tm_prev.v[g])) : -INF;
-        float mnY[NACC];
+        for (int g = 0; g < QG; g++) {
+            if constexpr (I8) tf[g] = it > 0 ? tic[g] : 0x7fffffff;
+            else tf[g] = it > 0 ? (TFG ? tfc[g] : tf_of(g, tm_prev.v[g])) : -INF;
+        }
+        AccT mnY[NACC];
         const uint32_t uY = step(X, Y, it % NBUF, dma_on, dd, tf, POS != 0, mnY);
         // PAIR: the pair's next tile is resident since its barrier -- its first fragments are
         // read now, so their latency hides under the slow path below
@@ -1315,16 +1405,23 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         // drain: the last tile's accumulators (ntiles is even: accB)
         const int last = ntiles - 1;
         if constexpr (TFG) tm_prev = tile_q(last % NBUF);  // (no DMA since: the buffer holds it)
-        float tf[QG];
+        AccT tf[QG];
 #pragma unroll
-        for (int g = 0; g < QG; g++) tf[g] = TFG ? tfc[g] : tf_of(g, tm_prev.v[g]);
+        for (int g = 0; g < QG; g++) {
+            if constexpr (I8) tf[g] = tic[g];
+            else tf[g] = TFG ? tfc[g] : tf_of(g, tm_prev.v[g]);
+        }
         if constexpr (RL) {
-            float mnB[NACC];
+            AccT mnB[NACC];
 #pragma unroll
             for (int c = 0; c < NACC; c++) {
-                mnB[c] = INF;
+                if constexpr (I8) mnB[c] = (int)0x80000000u;
+                else mnB[c] = INF;
 #pragma unroll
-                for (int v = 0; v < 16; v++) mnB[c] = fminf(mnB[c], accB[c][v]);
+                for (int v = 0; v < 16; v++) {
+                    if constexpr (I8) mnB[c] = max(mnB[c], accB[c][v]);
+                    else mnB[c] = fminf(mnB[c], accB[c][v]);
+                }
             }
             slow_rl(accB, last, tf, tm_prev, mnB, 0xffffffffu);
         } else {
@@ -1402,7 +1499,7 @@ __host__ __device__ inline FusedRangePiece knn_fused_range_piece(int64_t x, int6
 // last round of blocks ends together instead of a partial wave of whole query tiles.
 // Pieces of one query tile share thresholds through gthr like segments (piece id = block -
 // the first block of that query tile).  One call site of fused_piece (instruction cache).
-template <int RB, int MINW, int NBUF, int NW, int QG, int RG, int KR>
+template <int RB, int MINW, int NBUF, int NW, int QG, int RG, int KR, bool I8 = false>
 __global__ __launch_bounds__(64 * NW, MINW) void k_gemm_fused(GemmFilterArgs a) {
     if ((a.gate && *a.gate == 0) || (*a.status & KNN_STATUS_GEMM_UNSAFE)) return;  // not taken / exact path
     const int64_t T = a.tiles64;  // 64-row units per query tile
@@ -1455,7 +1552,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_gemm_fused(GemmFilterArgs a) 
             adv = t1 - t0;
         }
         if (!first) __syncthreads();  // every wave is done with the previous piece's LDS
-        fused_piece<RB, NBUF, NW, QG, RG, KR>(a, qt, seg, rb, re, rot, steps);
+        fused_piece<RB, NBUF, NW, QG, RG, KR, I8>(a, qt, seg, rb, re, rot, steps);
         if (KNN_FUSED_FORWARD || segmode) x += adv;
         else x1 -= adv;
     }
@@ -1493,6 +1590,7 @@ int knn_fused_schedule(GemmFilterArgs& a, int slots, int* nseg) {
 // ---------------------------------------------------------------------------------
 // plan and launch
 // ---------------------------------------------------------------------------------
+// (the int8 operand class's header has the bf16 form's slots: bn int32 words + the statistics)
 static size_t fused_lds_of(int row_bytes, int k, int nw, int rg, int nbuf, bool heaps, int qg = 1) {
     const int bn = 32 * rg, bm = 32 * qg * nw;
     const int hs = row_bytes % 64 == 0 ? bn / 4 + 1 : 0;  // (k_gemm_fused: TN header slots)
@@ -1524,8 +1622,10 @@ int knn_fused_row_bytes(int d) { return d == 64 && KNN_FUSED_AUG64 ? 2 * d + 32 
 //    8-wave blocks: pairs when they fit beside the heaps, else two buffers, else 32-row tiles.
 // Register lists, one per lane half: k <= 16 8 entries (KR = 8), k <= 32 16 (KR = 32: exact
 // 32-entry lists cost a block per CU of occupancy and 9 % of time on B).
-FilterPlan knn_fused_plan(int d, int k, int64_t nq, int num_cus, const FusedForce& force, int max_pieces) {
-    const int rb = knn_fused_row_bytes(d);
+FilterPlan knn_fused_plan(int d, int k, int64_t nq, int num_cus, const FusedForce& force, int max_pieces, bool i8) {
+    // int8 operand rows (d bytes): d = 128, the register-list shapes at their default tile groups
+    if (i8 && (d != 128 || k > 32 || force.m16 || force.nbuf != 0 || KNN_FUSED_AUG64)) return FilterPlan{0, 0, 0, 0, 0, 0, 0};
+    const int rb = i8 ? d : knn_fused_row_bytes(d);
     const size_t cap = 160 * 1024 - 256;  // room for the kernel's static LDS
     // d = 256, 32 < k <= 104 (C): per-half 52-entry register lists instead of LDS heaps, so
     // the tile buffers get the LDS the heaps held -- 32-row tiles in quads (one barrier per 128
@@ -1535,6 +1635,7 @@ FilterPlan knn_fused_plan(int d, int k, int64_t nq, int num_cus, const FusedForc
     auto make = [&](int nw, int rg, int minw, int nbuf, int qg = 1) {
         FilterPlan f{nw, qg, rg, minw, nbuf, 32 * qg * nw, fused_lds_of(rb, k, nw, rg, nbuf, kr == 0, qg)};
         f.kr = kr;
+        f.i8 = i8 ? 1 : 0;
         return f;
     };
     // Register-list shapes: 64 queries per wave on 32-row tiles (QG = 2: each A fragment read
@@ -1588,10 +1689,15 @@ FilterPlan knn_fused_plan(int d, int k, int64_t nq, int num_cus, const FusedForc
     return FilterPlan{0, 0, 0, 0, 0, 0, 0};  // k too large for the LDS heaps: not supported
 }
 
-template <int RB, int KR>
+template <int RB, int KR, bool I8 = false>
 static const void* fused_fn_k(const FilterPlan& f) {
-#define KNN_FUSED_FN(NB, NW, QG, RG) reinterpret_cast<const void*>(&k_gemm_fused<RB, 2, NB, NW, QG, RG, KR>)
-    if constexpr (KR == 104) {
+#define KNN_FUSED_FN(NB, NW, QG, RG) reinterpret_cast<const void*>(&k_gemm_fused<RB, 2, NB, NW, QG, RG, KR, I8>)
+    if constexpr (I8) {
+        // (knn_fused_plan: 64 queries per wave in octets, or 32 per wave on 64-row tiles in quads)
+        static_assert(KR == 8 || KR == 32, "int8 operands: register lists, k <= 32");
+        if (f.qg == 2) return f.nbuf == 16 ? KNN_FUSED_FN(16, 8, 2, 1) : nullptr;
+        return f.nbuf == 8 ? KNN_FUSED_FN(8, 8, 1, 2) : nullptr;
+    } else if constexpr (KR == 104) {
         return KNN_FUSED_FN(8, 8, 1, 1);
     } else if constexpr (KR > 0) {
         // register lists always fit the pairs shape
@@ -1618,6 +1724,10 @@ static const void* fused_fn(const FilterPlan& f) {
 }
 
 static const void* fused_ptr(int d, const FilterPlan& f) {
+    if (f.i8) {
+        if (d != 128 || f.m16) return nullptr;
+        return f.kr == 8 ? fused_fn_k<128, 8, true>(f) : f.kr == 32 ? fused_fn_k<128, 32, true>(f) : nullptr;
+    }
     if (f.m16) return knn_fused16_ptr(d, f);
     if (d == 64) {
         if constexpr (KNN_FUSED_AUG64) return fused_fn<160>(f);
@@ -1626,15 +1736,18 @@ static const void* fused_ptr(int d, const FilterPlan& f) {
     return d == 128 ? fused_fn<256>(f) : fused_fn<512>(f);
 }
 
+bool knn_fused_has_kernel(int d, const FilterPlan& f) { return knn_fused_supported(d) && f.nw > 0 && fused_ptr(d, f) != nullptr; }
+
 hipError_t knn_fused_occupancy(int d, const FilterPlan& f, int* blocks_per_cu) {
-    if (!knn_fused_supported(d) || f.nw == 0) return hipErrorInvalidValue;
+    if (!knn_fused_supported(d) || f.nw == 0 || !fused_ptr(d, f)) return hipErrorInvalidValue;
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fused_ptr(d, f), 64 * f.nw, f.lds);
 }
 
 hipError_t knn_launch_fused(const GemmFilterArgs& a, const FilterPlan& f, hipStream_t st) {
-    const int ld = knn_fused_row_bytes(a.d) / 2;  // operand row pitch in elements
+    const int ld = f.i8 ? a.d : knn_fused_row_bytes(a.d) / 2;  // operand row pitch in elements
     if (!knn_fused_supported(a.d) || f.nw == 0 || a.ld_t != ld || a.ld_q != ld || !a.qstat)
         return hipErrorInvalidValue;
+    if (f.i8 ? !(a.i8_s2 > 0.0f && fused_ptr(a.d, f)) : a.i8_s2 != 0.0f) return hipErrorInvalidValue;
     if (f.m16 && !knn_fused16_ptr(a.d, f)) return hipErrorInvalidValue;
     if (f.kr > 0 && !(f.nw == 8 && (((f.nbuf == 4 || f.nbuf == 8) && f.qg == 1 && f.rg == 2 && f.kr <= 32) ||
                                      ((f.nbuf == 4 || f.nbuf == 8 || f.nbuf == 16) && f.qg == 2 && f.rg == 1 && f.kr <= 32) ||

@@ -71,6 +71,9 @@ struct GemmFilterArgs {
     // running blocks}, zeroed before the launch -- a block ahead of its XCD's average waits a
     // bounded time (fused_pace), so the blocks of an XCD stream the same rows through its L2
     int32_t* pace;
+    // int8 operand class (k_gemm_fused<..., I8>): s2 = fl(2 s s) of the train set's scale s; the
+    // operand rows are int8, ld_t / ld_q in bytes; 0 for the bf16 operands
+    float i8_s2;
 };
 
 struct RescoreArgs {
@@ -228,13 +231,18 @@ hipError_t knn_launch_exact_scan(const ExactScanArgs& a, int grid, hipStream_t s
 size_t knn_exact_scan_lds(int d, int k, int C);
 // tstat (optional, train rows of the fused filter): per 64-row tile [ceil(n / 64)]
 //   {max ||x||^2, max ||x - rx||, max ||rx||, 0}, rx = rn_bf16(x) (upper bounds)
+// i8s > 0 (the int8 operand class, scale i8s): rx = i8s knn_i8_quant(x, i8s) in tstat and qstat
+//   (oscale is not used), and tstat's fourth word is max |tn - s2 knn_i8_norm_q(tn, s2)|
 // qstat (optional, query rows of the fused filter): per row {||x||, ||x - rx||} upper bounds,
 //   rx = rn_bf16(oscale x) / oscale (the operand the filter multiplies, unscaled)
 // gate (optional): the stage runs only when *gate != 0 (device-side control of AUTO's re-run)
 hipError_t knn_launch_row_norms(const void* x, int elem, int64_t n, int ld, int d, float* out,
                                 int32_t* status, uint32_t* maxo, float* outp, float c1, hipStream_t st,
                                 float4* tstat = nullptr, const int32_t* gate = nullptr,
-                                float2* qstat = nullptr, float oscale = 1.0f);
+                                float2* qstat = nullptr, float oscale = 1.0f, float i8s = 0.0f);
+// out (one word, zeroed by the caller) = max over the n x d fp32 elements of the bits of |x|
+// (the bits of non-negative floats order like the floats; NaN and inf end up >= 0x7f800000)
+hipError_t knn_launch_absmax(const float* x, int64_t n, int ld, int d, uint32_t* out, hipStream_t st);
 // row_bytes = d * element size: 128, 256 or 512
 bool knn_gemm_filter_supported(int elem, int row_bytes);
 // block shape of the filter for (element type, row bytes, k): waves per block, query
@@ -246,6 +254,7 @@ struct FilterPlan {
     int kr = 0;  // fused: register-list shape (16, 32, 104; 0 = LDS heaps)
     int ls = 0;  // fused: the kernel exchanges threshold lists between a query's pieces
     int m16 = 0;  // fused: the v_mfma_f32_16x16x32_bf16 form of the shape (k_gemm_fused16)
+    int i8 = 0;   // fused: int8 operand rows of d bytes on v_mfma_i32_32x32x32_i8 (d = 128, k <= 32)
 };
 FilterPlan knn_gemm_filter_plan(int elem, int row_bytes, int k);
 hipError_t knn_launch_gemm_filter(const GemmFilterArgs& a, int elem, int row_bytes, hipStream_t st);
@@ -280,8 +289,13 @@ struct FusedForce {
 // 512-query blocks, at most max_pieces per query tile, fill 80 % of a round of CUs, else 32 on
 // 64-row tiles (fewer pieces per query tile).  run_gemm computes the plan once per pass and sizes the
 // operands, the occupancy, the schedule and the launch from that one plan.
-FilterPlan knn_fused_plan(int d, int k, int64_t nq, int num_cus, const FusedForce& force, int max_pieces);
+// i8: the int8 operand class (rows of d bytes; d = 128 and k <= 32 only, and no forced tile group
+// or 16x16 form: nw == 0 otherwise)
+FilterPlan knn_fused_plan(int d, int k, int64_t nq, int num_cus, const FusedForce& force, int max_pieces,
+                          bool i8 = false);
 hipError_t knn_fused_occupancy(int d, const FilterPlan& f, int* blocks_per_cu);
+// whether the library holds a kernel for plan f (no GPU call)
+bool knn_fused_has_kernel(int d, const FilterPlan& f);
 // out = component maxima of n tile statistics (the fused filter's a.tsmax)
 hipError_t knn_launch_tile_stat_max(const float4* tstat, int64_t n, float4* out, hipStream_t st);
 // k_gemm_fused16's kernel for plan f (f.m16; knn_fused16.hip), nullptr if f has no 16x16x32 form
@@ -308,6 +322,15 @@ hipError_t knn_launch_aug_rows(const void* x, int elem, int64_t n, int64_t n_val
 hipError_t knn_launch_tn_rows(const void* x, int elem, int64_t n, int64_t n_valid, int ld, int d, const float* norms,
                               float scale, void* out, const float4* tstat, int bn, hipStream_t st,
                               const int32_t* gate = nullptr);
+// the int8 operand class (fp32 x, scale s; knn_i8_quant): queries [n][d] int8 (norms == NULL), or
+// train blocks of bn rows [bn][d] int8 | bn int32 -knn_i8_norm_q(tn, s2) | tstat of the enclosing
+// 64-row tile; pad rows: zero features and -2^30
+hipError_t knn_launch_i8_rows(const float* x, int64_t n, int64_t n_valid, int ld, int d, const float* norms, float s,
+                              void* out, const float4* tstat, int bn, hipStream_t st);
+// s2 = fl(2 s s) of scale s, as the kernels round it (knn_i8_s2, knn_device.h)
+float knn_i8_s2_of(float s);
+// the int8 filter's MFMA chain on [32][K] int8 operands (K % 32 == 0): out [32][32] int32
+hipError_t knn_launch_mfma_probe_i8(const int8_t* a, const int8_t* b, int K, int32_t* out, hipStream_t st);
 // bytes per operand row of the fused filter's tile image: 2d (2d + 32 in the KNN_STUDY_AUG64 build)
 int knn_fused_row_bytes(int d);
 hipError_t knn_launch_merge(const MergeArgs& a, hipStream_t st);

@@ -639,14 +639,16 @@ __global__ __launch_bounds__(256) void k_direct_rows(DirectTileArgs a) {
 __device__ __forceinline__ float norm_ub(float s, int d) {
     return sqrtf(fmaf((float)d, 0x1p-149f, s)) * (1.0f + 0x1p-12f);
 }
-template <typename E>
+// (I8: the statistics of the int8 operand class, scale i8s > 0 -- a template parameter, so the
+// bf16 instantiations carry none of it)
+template <typename E, bool I8 = false>
 __global__ __launch_bounds__(256) void k_row_norms(const E* __restrict__ x, int64_t n, int ld,
                                                    int d, float* __restrict__ out,
                                                    int32_t* __restrict__ status,
                                                    uint32_t* __restrict__ maxo,
                                                    float* __restrict__ outp, float c1,
                                                    float4* __restrict__ tstat, const int32_t* __restrict__ gate,
-                                                   float2* __restrict__ qstat, float oscale) {
+                                                   float2* __restrict__ qstat, float oscale, float i8s) {
     if (gate && *gate == 0) return;  // a gated stage (AUTO's re-run) that is not taken
     // rows [n, n + 64) of out/outp get +inf: the GEMM filter's tile tail reads them
     const int lane = threadIdx.x & 63;
@@ -663,8 +665,17 @@ __global__ __launch_bounds__(256) void k_row_norms(const E* __restrict__ x, int6
     auto acc = [&](float v) __attribute__((always_inline)) {
         a = fmaf(v, v, a);
         if (rstat) {
-            const float rv = __uint_as_float(bf16_rne(oscale * v) << 16) * inv;
-            const float e = v - rv;
+            // (int8 operands, i8s > 0: rx = i8s n is a real number; e is its residual rounded once
+            // and rv rounds once -- both inside norm_ub's factor)
+            float rv, e;
+            if constexpr (I8) {
+                const float nv = (float)knn_i8_quant(v, i8s);
+                rv = i8s * nv;
+                e = fmaf(-i8s, nv, v);
+            } else {
+                rv = __uint_as_float(bf16_rne(oscale * v) << 16) * inv;
+                e = v - rv;
+            }
             ae = fmaf(e, e, ae);
             ar = fmaf(rv, rv, ar);
         }
@@ -732,11 +743,20 @@ __global__ __launch_bounds__(256) void k_row_norms(const E* __restrict__ x, int6
     if (maxo || tstat) {
         // the wave's 64 rows are one 64-row tile of the fused filter (rows >= n count as 0)
         float m = s, me = r < n ? norm_ub(se, d) : 0.0f, mr = r < n ? norm_ub(sr, d) : 0.0f;
+        // (int8 operands) how far the row's integer norm term is from its norm
+        [[maybe_unused]] float mv = 0.0f;
+        if constexpr (I8) {
+            if (r < n) {
+                const float s2 = knn_i8_s2(i8s);
+                mv = knn_i8_norm_res(s, s2, knn_i8_norm_q(s, s2));
+            }
+        }
 #pragma unroll
         for (int j = 32; j > 0; j >>= 1) {
             m = fmaxf(m, __shfl_xor(m, j));
             me = fmaxf(me, __shfl_xor(me, j));
             mr = fmaxf(mr, __shfl_xor(mr, j));
+            if constexpr (I8) mv = fmaxf(mv, __shfl_xor(mv, j));
         }
         if ((threadIdx.x & 63) == 0) {
             // one word for the whole launch: the atomic only when it can raise the maximum (a
@@ -745,7 +765,7 @@ __global__ __launch_bounds__(256) void k_row_norms(const E* __restrict__ x, int6
                 const uint32_t mo = f2o(m);
                 if (mo > __hip_atomic_load(maxo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(maxo, mo);
             }
-            if (tstat && r < n) tstat[r >> 6] = make_float4(m, me, mr, 0.0f);
+            if (tstat && r < n) tstat[r >> 6] = make_float4(m, me, mr, mv);
         }
     }
 }
@@ -1866,6 +1886,32 @@ hipError_t knn_launch_mfma_probe(const uint16_t* a, const uint16_t* b, int K, fl
     return hipSuccess;
 }
 
+// k_mfma_probe_i8: the same for the int8 operand class -- per 32-wide k-step one
+// v_mfma_i32_32x32x32_i8, lane l feeding row / column l & 31 with bytes [32 s + 16 (l >> 5), +16)
+// (k_gemm_fused's fragments); a, b: [32][K] int8, K % 32 == 0; out int32, the same register map.
+__global__ __launch_bounds__(64) void k_mfma_probe_i8(const int8_t* __restrict__ a, const int8_t* __restrict__ b, int K,
+                                                      int32_t* __restrict__ out) {
+    typedef int intx4 __attribute__((ext_vector_type(4)));
+    typedef int intx16 __attribute__((ext_vector_type(16)));
+    const int lane = lane_id();
+    const int j = lane & 31, h = lane >> 5;
+    intx16 acc = intx16{};
+    for (int s = 0; s < K / 32; s++) {
+        const intx4 fa = *reinterpret_cast<const intx4*>(a + (int64_t)j * K + 32 * s + 16 * h);
+        const intx4 fb = *reinterpret_cast<const intx4*>(b + (int64_t)j * K + 32 * s + 16 * h);
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa, fb, acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; r++) out[((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + j] = acc[r];
+}
+
+hipError_t knn_launch_mfma_probe_i8(const int8_t* a, const int8_t* b, int K, int32_t* out, hipStream_t st) {
+    if (K <= 0 || K % 32) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mfma_probe_i8, dim3(1), dim3(64), 0, st, a, b, K, out);
+    KNN_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
 // ---------------------------------------------------------------------------------
 // k_generate: the synthetic rows of SURVEY.md 8d (same hash as oracle/knn_oracle.c)
 // ---------------------------------------------------------------------------------
@@ -2329,16 +2375,47 @@ hipError_t knn_launch_direct_tile(DirectTileArgs a, hipStream_t st) {
 
 hipError_t knn_launch_row_norms(const void* x, int elem, int64_t n, int ld, int d, float* out,
                                 int32_t* status, uint32_t* maxo, float* outp, float c1, hipStream_t st,
-                                float4* tstat, const int32_t* gate, float2* qstat, float oscale) {
+                                float4* tstat, const int32_t* gate, float2* qstat, float oscale, float i8s) {
     if (n <= 0) return hipSuccess;
     const int64_t rows = n + (outp ? 64 : 0);
     dim3 grid((unsigned)((rows + 255) / 256));
     if (elem == ELEM_BF16)
         hipLaunchKernelGGL(k_row_norms<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, n, ld, d, out,
-                           status, maxo, outp, c1, tstat, gate, qstat, oscale);
+                           status, maxo, outp, c1, tstat, gate, qstat, oscale, 0.0f);
+    else if (i8s > 0.0f)
+        hipLaunchKernelGGL((k_row_norms<float, true>), grid, dim3(256), 0, st, (const float*)x, n, ld, d, out,
+                           status, maxo, outp, c1, tstat, gate, qstat, oscale, i8s);
     else
         hipLaunchKernelGGL(k_row_norms<float>, grid, dim3(256), 0, st, (const float*)x, n, ld, d, out,
-                           status, maxo, outp, c1, tstat, gate, qstat, oscale);
+                           status, maxo, outp, c1, tstat, gate, qstat, oscale, 0.0f);
+    KNN_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------
+// k_absmax: *out = max over rows [0, n) x features [0, d) of the bits of |x| (the int8 operand
+// class's scale is max|t| / 127).  One float4 per thread and round, a wave maximum, then one
+// atomic per wave that can raise the word.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_absmax(const float* __restrict__ x, int64_t n, int ld, int d,
+                                                uint32_t* __restrict__ out) {
+    const int per_row = d >> 2;
+    uint32_t m = 0u;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n * per_row; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / per_row;
+        const float4 v = load4(x + r * ld + (int)(i - r * per_row) * 4);
+        m = max(max(m, __float_as_uint(v.x) & 0x7fffffffu), __float_as_uint(v.y) & 0x7fffffffu);
+        m = max(max(m, __float_as_uint(v.z) & 0x7fffffffu), __float_as_uint(v.w) & 0x7fffffffu);
+    }
+#pragma unroll
+    for (int j = 32; j > 0; j >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, j));
+    if ((threadIdx.x & 63) == 0 && m > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out, m);
+}
+
+hipError_t knn_launch_absmax(const float* x, int64_t n, int ld, int d, uint32_t* out, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    if (d % 4 || ld % 4) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_absmax, dim3(std::min(elementwise_grid(n * (d / 4)), 4096u)), dim3(256), 0, st, x, n, ld, d, out);
     KNN_LAUNCH_CHECK();
     return hipSuccess;
 }
