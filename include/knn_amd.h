@@ -491,8 +491,8 @@ int32_t knn_stage_times(const knn_ctx* ctx, const char** names, float* ms, int32
  * ran with the train norm folded into the MFMA (the fused-norm bf16 filter), [6] train
  * bytes and [7] query bytes a knn_predict call copied host -> device, [8] 1 when the
  * filter's train-side operands came from the KNN_OPT_CACHE_TRAIN cache (no train norm or
- * tile-block pass ran), [9] the fused filter's MFMA shape (32: v_mfma_f32_32x32x16_bf16,
- * 16: v_mfma_f32_16x16x32_bf16, 0: no fused filter ran), [10] the fused filter's queries per
+ * tile-block pass ran), [9] 32 when the fused filter ran (the rows of its MFMA tile; it has
+ * one shape), 0 when no fused filter ran, [10] the fused filter's queries per
  * wave (32 or 64, knn_fused_plan's rule; 0: no fused filter ran), [11] the element the filter
  * multiplied: 1 int8 (KNN_ALGO_GEMM_I8's form; [3] stays 3, fp32 rows rounded once to a narrow
  * MFMA operand), 0 the data's own type or bf16.  Returns the number written (<= 12); a caller

@@ -98,14 +98,12 @@ struct knn_ctx {
     struct { const void* feat; int64_t n; int d, ld, dtype; uint64_t gen, epoch; bool valid; }
         tpad{nullptr, 0, 0, 0, 0, 0, 0, false};
     int rescore_su = 0;  // test hook KNN_RESCORE_SU: the rescore's LDS staging size (0 = sized)
-    // study overrides of the fused filter's plan (KNN_FUSED_QG / _NBUF / _HEAPS), read once at
-    // knn_create: a call never reads the environment, and one pass uses one plan throughout
+    // test hooks of the fused filter's plan (KNN_FUSED_QG / _HEAPS), read once at knn_create: a
+    // call never reads the environment, and one pass uses one plan throughout
     FusedForce fforce;
     // the device entry points reuse derived train operands across calls only under
     // KNN_OPT_CACHE_TRAIN_DEVICE (the caller's device buffer may change behind the library)
     int cache_train_device = 0;
-    // study switches of run_gemm, read once at knn_create
-    bool no_lshare = false, no_cursor = false, rescore_all = false, no_pace = false;
     // host-API staging (device copies of host inputs / outputs)
     DBuf h_train, h_labels, h_test, h_pred, h_dist, h_idx;
     int32_t* ctrl_host = nullptr;  // pinned, mapped, fine-grained: [0] status, [1] fallback count,
@@ -123,7 +121,6 @@ struct knn_ctx {
     DBuf rg_part, rg_zero, rg_targets;
     DBuf arrive;              // k_direct_rows' fused merge: per query group, segments finished
     bool arrive_clean = false;  // arrive is all zero (the last launch ran to completion)
-    bool merge_kernel = false;  // study switch KNN_DIRECT_MERGE_KERNEL=1: k_direct_rows' segments via k_merge_vote
     // host-buffer calls (knn_predict): cached train upload, two query slots streamed on a copy stream
     int cache_train = 0;
     uint64_t generation = 0;
@@ -147,7 +144,6 @@ struct knn_ctx {
                                                       // bytes, train-side filter operands from the cache,
                                                       // MFMA form, queries per wave, [11] the filter's
                                                       // operand element (0: the data's / bf16, 1: int8)
-    int subs = 2;                           // candidate sub-slices per segment of the last GEMM pass
     int64_t rerun_stats[3] = {0, -1, 0};    // segments, operand type, fused of AUTO's gated split re-run
     int num_cus = 256;
 };
@@ -281,11 +277,11 @@ int choose_algo(const knn_ctx* c, int64_t nt, int64_t nq, int d, int k, int dtyp
     // Other widths keep the 10^9-pair rule.
     const double pairs = (double)nt * (double)nq;
     if (d >= 32 && nt >= 8192 && (pairs >= 1e9 || (knn_fused_supported(d) && nt >= 16384))) {
-        // fp32 rows at d = 128, k <= 32 with no forced study shape: the int8 operand class (half
+        // fp32 rows at d = 128, k <= 32: the int8 operand class (half
         // the MFMA work per feature), which run_gemm takes when the train set's range allows it
         // (finite, E8 <= R Ebf, not demoted) and otherwise runs as the bf16 operands
         if (gemm_ok(KNN_ALGO_GEMM_BF16))
-            return KNN_AUTO_I8 && dtype == KNN_F32 && d == 128 && k <= 32 && !c->fforce.m16 && c->fforce.nbuf == 0
+            return KNN_AUTO_I8 && dtype == KNN_F32 && d == 128 && k <= 32
                        ? KNN_ALGO_GEMM_I8 : KNN_ALGO_GEMM_BF16;
         if (gemm_ok(KNN_ALGO_GEMM_SPLIT)) return KNN_ALGO_GEMM_SPLIT;
         if (gemm_ok(KNN_ALGO_GEMM)) return KNN_ALGO_GEMM;
@@ -407,7 +403,7 @@ knn_status run_direct_tile(knn_ctx* c, const knn_dataset* tr, const knn_dataset*
     }
     HIP_OR_FAIL(c, c->seg_rec.ensure(sizeof(int32_t) * 3 * (size_t)k * (size_t)te->n * nseg));
     a.rec = c->seg_rec.as<int32_t>();
-    if (knn_direct_rows_shape(k, tr->d) && !c->merge_kernel) {
+    if (knn_direct_rows_shape(k, tr->d)) {
         // k_direct_rows merges its segments itself (the last wave of a query group to finish):
         // one launch, no k_merge_vote pass (config L: 0.012 ms of merge + a launch, round 6)
         const int64_t groups = knn_direct_rows_groups(te->n);
@@ -514,9 +510,9 @@ void certificate(int d, int felem, float* coef, float* eta) {
 }
 
 // Fused-norm filter (knn_fused.hip): y = fl_mfma(tn + sum -2 rq_i rt_i) -- the fp32 norm from
-// the tile block's header is the first MFMA's C operand, every d (the KNN_STUDY_AUG64 build
-// splits it over an augmented k-step at d = 64 instead: + tn_hi + tn_mid + tn_lo, the terms
-// the coefficient still covers), G = fl(qn + y), Delta = coef (qn +
+// the tile block's header is the first MFMA's C operand, every d (the coefficient still covers
+// the round-2 layout's three-term split of the norm over an augmented k-step, + tn_hi + tn_mid +
+// tn_lo), G = fl(qn + y), Delta = coef (qn +
 // tn) + eta; rq, rt = the bf16 operands (q, t themselves for bf16 data, rn(q), rn(t) for fp32
 // data).  With N = qn + tn (exact norms):
 //   MFMA accumulation of d + 3 terms (d + 1 with the C-operand norm) at <= 2u per add, terms
@@ -602,14 +598,13 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     // sets below, 64 sub-slices, k_rescore's limit).  The
     // workspace stays within 1.5 GiB.  The queries-per-wave choice (knn_fused_plan) still
     // counts the base list's pieces: 64-query waves cut into more than ~5 pieces lost to the
-    // 32-query shape (A's rows, 6,250 queries: 2.06 against 1.84 ms, r06bh).  (The 16x16x32
-    // study filter's quarter lists: 8 pieces.)
+    // 32-query shape (A's rows, 6,250 queries: 2.06 against 1.84 ms, r06bh).
     const size_t per_q = 12 * 64 * (size_t)KNN_RESCORE_CAPW, ws_lim = (size_t)1536 << 20;
     const bool idle = (nq + 255) / 256 * (int64_t)max_splits(nt, k, 64 * KNN_RESCORE_CAPW) * 5 < (int64_t)4 * c->num_cus;
     // (a handful of query tiles, idle even at 16 pieces each -- 1,000 queries: 4 tiles -- gets
     // an 8x list and up to 32 pieces, 64 sub-slices)
     const bool tiny = idle && (nq + 255) / 256 * 16 * 5 < (int64_t)4 * c->num_cus;
-    const int capmul = (c->fforce.m16 || !idle) ? 1
+    const int capmul = !idle ? 1
                      : tiny && (size_t)nq * per_q * 8 <= ws_lim ? 8
                      : (size_t)nq * per_q * 4 <= ws_lim ? 4
                      : (size_t)nq * per_q * 2 <= ws_lim ? 2 : 1;
@@ -627,7 +622,7 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     // the fused filter's plan, computed once: it sizes the tile blocks (bn_f), the occupancy,
     // the schedule and the launch of this pass
     // The int8 operand class (KNN_ALGO_GEMM_I8, fp32 data): taken when its plan exists (d = 128,
-    // k <= 32, no forced study shape) and the train set's range allows it; else this call runs
+    // k <= 32) and the train set's range allows it; else this call runs
     // the bf16 operands below unchanged.  own_train / may_cache: as for tprep below.
     // AUTO takes the class only for a train set whose operands this context keeps (may_cache):
     // the scale, the guard's statistics and the demotion mark live with that cache.  Without it
@@ -716,22 +711,21 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     // tile blocks (k_tn_rows), reused from an earlier call on the same train view when the
     // context caches train (no train pass at all then; main.cpp:40-43 re-reads every train row
     // per query, this is the part of that work that depends on train alone)
-    const bool fused_tn = fused && knn_fused_row_bytes(d) == 2 * d;
     const int bn_f = fused ? 32 * fplan.rg : 0;
     const bool own_train = tr->feat == c->h_train.p;  // knn_predict's uploaded copy
     // derived train operands are reused for knn_predict's own upload (KNN_OPT_CACHE_TRAIN), and
     // for a caller's device buffer only under KNN_OPT_CACHE_TRAIN_DEVICE
     const bool may_cache = c->cache_train && (own_train || c->cache_train_device);
     auto& tp = c->tprep;
-    const bool prep_hit = fused_tn && !gate && may_cache && tp.valid && tp.feat == tr->feat && tp.n == nt &&
+    const bool prep_hit = fused && !gate && may_cache && tp.valid && tp.feat == tr->feat && tp.n == nt &&
                           tp.d == d && tp.ld == tr->ld && tp.dtype == dtype && tp.bn == bn_f && tp.i8 == (i8 ? 1 : 0) &&
                           tp.gen == c->generation && tp.epoch == (own_train ? c->train_epoch : 0);
-    if (fused_tn && !gate) {
+    if (fused && !gate) {
         HIP_OR_FAIL(c, c->tctrl.ensure(4 * sizeof(int32_t)));
         tp.valid = false;  // (set again below once this call's train pass is enqueued)
     }
     stage_begin(c, st, gate ? "norms_rerun" : "norms");
-    if (fused_tn && !gate) {
+    if (fused && !gate) {
         // train norms into their own status words, then into this call's status word
         if (!prep_hit) {
             HIP_OR_FAIL(c, hipMemsetAsync(c->tctrl.p, 0, 4 * sizeof(int32_t), st));
@@ -768,7 +762,7 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     const void* ftrain = tr->feat;
     const void* ftest = te->feat;
     int fld_t = tr->ld, fld_q = te->ld;
-    if (fused_tn) {
+    if (fused) {
         // train as tile blocks [bn rows of rn(t) | bn norms | tile statistics] (the
         // filter starts each accumulator from the norms), queries as rn(-2 q) rows; one more
         // tile of pad blocks past the grid (the filter scans tiles in twos, k_gemm_fused).
@@ -800,22 +794,6 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
         c->stats[8] = prep_hit ? 1 : 0;
         if (may_cache)
             tp = {tr->feat, nt, d, tr->ld, dtype, bn_f, c->generation, own_train ? c->train_epoch : 0, true, i8 ? 1 : 0};
-    } else if (fused) {
-        // (study build KNN_STUDY_AUG64, d = 64) augmented bf16 rows: train [rn(t) | tn split],
-        // queries [-2 rn(q) | 1 1 1]
-        // (pad rows: zero features, a huge norm -- they never pass)
-        // (pad rows past the grid: the filter scans tiles in twos, k_gemm_fused)
-        const int64_t ntf = ntp + 256;
-        HIP_OR_FAIL(c, c->split_t.ensure(sizeof(uint16_t) * (size_t)(d + 16) * ntf));
-        HIP_OR_FAIL(c, c->split_q.ensure(sizeof(uint16_t) * (size_t)(d + 16) * nq));
-        stage_begin(c, st, gate ? "aug_rerun" : "aug");
-        HIP_OR_FAIL(c, knn_launch_aug_rows(tr->feat, dtype, ntf, nt, tr->ld, d, c->tnorm.as<float>(), 1.0f,
-                                           c->split_t.as<uint16_t>(), c->tmax.as<float4>(), st, gate));
-        HIP_OR_FAIL(c, knn_launch_aug_rows(te->feat, dtype, nq, nq, te->ld, d, nullptr, -2.0f,
-                                           c->split_q.as<uint16_t>(), nullptr, st, gate));
-        stage_end(c, st);
-        ftrain = c->split_t.p; ftest = c->split_q.p;
-        fld_t = fld_q = d + 16;
     } else if (felem == ELEM_SPLIT) {
         HIP_OR_FAIL(c, c->split_t.ensure(sizeof(uint16_t) * 2 * d * ntp));
         HIP_OR_FAIL(c, c->split_q.ensure(sizeof(uint16_t) * 2 * d * nq));
@@ -856,7 +834,7 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     }
 
     const FilterPlan plan = fused ? fplan : knn_gemm_filter_plan(kelem, rb, k);
-    const bool shared = fused && !c->no_lshare && knn_fused_list_share_width(plan) > 0;
+    const bool shared = fused && knn_fused_list_share_width(plan) > 0;
     const int64_t n_qtiles = (nq + plan.bm - 1) / plan.bm;
     GemmFilterArgs g{};
     g.nt = nt; g.n_qtiles = (int)n_qtiles;
@@ -893,8 +871,8 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     g.i8_s2 = i8 ? knn_i8_s2_of(i8s) : 0.0f;
     // per-XCD scan cursors for the multi-segment schedule (B: filter traffic beyond L2 664 ->
     // 494 GB per launch, time unchanged; with one segment or the balanced schedule they saved
-    // nothing: r03s).  KNN_NO_SCAN_CURSOR=1 turns them off (a diagnostic; same results).
-    if (fused && !c->no_cursor && g.g2 < 0 && nseg > 1) {
+    // nothing: r03s).
+    if (fused && g.g2 < 0 && nseg > 1) {
         HIP_OR_FAIL(c, c->cursor.ensure(sizeof(uint32_t) * 8));
         HIP_OR_FAIL(c, hipMemsetAsync(c->cursor.p, 0, sizeof(uint32_t) * 8, st));
         g.cursor = c->cursor.as<uint32_t>();
@@ -903,12 +881,11 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     // 22.0 -> 4.7 GB) when the balanced schedule is one round of blocks that start and
     // end together: there a leader's wait costs nothing.  With whole rounds of query tiles before
     // it a held block keeps its CU from the next round's (A's rows, 200,000 queries: 37.9 -> 41.4
-    // ms), so those grids are not paced.  KNN_NO_FUSED_PACE=1 turns it off (a diagnostic; same
-    // results).  The 64-query register-list shapes at d = 128 only (what was measured: A and
+    // ms), so those grids are not paced.  The 64-query register-list shapes at d = 128 only (what was measured: A and
     // its 2- and 4-GPU shares; B's and C's grids take segments or several rounds; the 32-query
     // instantiations compile no pacing code).  The two uses of c->cursor exclude each other
     // (segments: g2 < 0).
-    if (fused && !c->no_pace && g.g2 > 0 && g.p1_blocks == 0 && plan.qg == 2 && plan.kr > 0 && d == 128 && !plan.m16) {
+    if (fused && g.g2 > 0 && g.p1_blocks == 0 && plan.qg == 2 && plan.kr > 0 && d == 128) {
         HIP_OR_FAIL(c, c->cursor.ensure(sizeof(int32_t) * 16));
         HIP_OR_FAIL(c, hipMemsetAsync(c->cursor.p, 0, sizeof(int32_t) * 16, st));
         g.pace = c->cursor.as<int32_t>();
@@ -917,7 +894,7 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     // union's k-th smallest U is the bound a single scan would have.  The 32-queries-per-wave
     // shape only -- the small query counts, whose query tiles are cut into many pieces (A's
     // 8-GPU share: 5 pieces, 599 -> 447 kept rows per query, filter 3.38 -> 3.19 ms, r04g; on
-    // A and B, 3 and 2 pieces, it measured equal or slower).  KNN_NO_LIST_SHARE=1: off.
+    // A and B, 3 and 2 pieces, it measured equal or slower).
     if (shared && nseg > 1) {
         g.lshare_w = knn_fused_list_share_width(plan);
         const int64_t nls = nq * (int64_t)nseg * g.lshare_w;
@@ -927,8 +904,7 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     }
     g.status = c->ctrl.as<int32_t>();
     g.gate = gate;
-    // candidate sub-slices per segment: per lane half (32x32 filters), per quarter (k_gemm_fused16)
-    const int subs = fused ? knn_fused_subslices(plan) : 2;
+    const int subs = KNN_FILTER_SUBSLICES;  // candidate sub-slices per segment: one per lane half
     if (fused && g.g2 >= 0 && nseg > 1)  // whole query tiles write only their piece's sub-slices
         HIP_OR_FAIL(c, hipMemsetAsync(c->cnt.p, 0, sizeof(int32_t) * subs * nseg * nq, st));
     stage_begin(c, st, gate ? "gemm_filter_rerun" : "gemm_filter");
@@ -940,13 +916,13 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     r.train = tr->feat; r.labels = tr->labels; r.ld_t = tr->ld;
     r.test = te->feat; r.ld_q = te->ld; r.nq = nq; r.d = d; r.k = k; r.C = C; r.elem = dtype;
     r.cnt = g.cnt; r.cand = g.cand; r.cap = cap;
-    r.nseg = subs * nseg; r.cap_seg = g.cap_seg / subs;  // sub-slices: (segment, lane half or quarter)
+    r.nseg = subs * nseg; r.cap_seg = g.cap_seg / subs;  // sub-slices: (segment, lane half)
     r.out = out; r.status = c->ctrl.as<int32_t>();
     r.fb_list = c->fb_list.as<int32_t>(); r.fb_count = c->ctrl.as<int32_t>() + 1;
     r.gate = gate;
     // the fused filter's final thresholds: the selection stages only the candidates that can
-    // survive (KNN_RESCORE_ALL=1 stages every candidate: a study switch)
-    r.gthr = fused && !c->rescore_all ? g.gthr : nullptr;
+    // survive
+    r.gthr = fused ? g.gthr : nullptr;
     // LDS staging for about twice the expected kept rows -- k (1 + ln(nt / k)) for one scan,
     // +25 % per extra segment (they share thresholds through gthr), measured 238 per query on
     // A and 605 on B -- rounded to 64 by the launcher and capped at the list capacity: a
@@ -963,11 +939,10 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
         c->stats[2] = nseg;
         c->stats[3] = felem;
         c->stats[5] = fused;
-        c->stats[9] = fused ? (plan.m16 ? 16 : 32) : 0;
+        c->stats[9] = fused ? 32 : 0;
         c->stats[10] = fused ? 32 * plan.qg : 0;
         c->stats[11] = i8 ? 1 : 0;
         if (i8) c->i8_pass_nq = nq;
-        c->subs = subs;
     } else {
         c->rerun_stats[0] = nseg;
         c->rerun_stats[1] = felem;
@@ -997,17 +972,16 @@ knn_status knn_create(knn_ctx** out, const knn_opts* opts) {
         c->cache_train = (opts->flags & KNN_OPT_CACHE_TRAIN) != 0;
         c->cache_train_device = c->cache_train && (opts->flags & KNN_OPT_CACHE_TRAIN_DEVICE) != 0;
     }
-    // test hooks and study switches, read here once, never per call
+    // Test hooks: the only environment the library's plan depends on, read here once, never per
+    // call.  They let the tests run shapes and paths the product rules pick only at large sizes:
+    //   KNN_RESCORE_SU=n   the rescore's LDS staging size (entries; default: sized per call)
+    //   KNN_FUSED_QG=1|2   the fused filter's queries per wave, 32 or 64 (knn_fused_plan's fill rule)
+    //   KNN_FUSED_HEAPS    (set) the LDS-heap shape for 32 < k <= 104 at d = 256
+    //   KNN_WS_QUERIES=n   queries per pass of the GEMM path's candidate workspace
+    //   KNN_BATCH_ROWS=n   query rows per batch of the host pipeline
     if (const char* e = getenv("KNN_RESCORE_SU")) c->rescore_su = atoi(e);
     if (const char* e = getenv("KNN_FUSED_QG")) c->fforce.qg = atoi(e);
-    if (const char* e = getenv("KNN_FUSED_NBUF")) c->fforce.nbuf = atoi(e);
     c->fforce.heaps = getenv("KNN_FUSED_HEAPS") != nullptr;
-    c->fforce.m16 = getenv("KNN_FUSED_MFMA16") != nullptr && std::atoi(getenv("KNN_FUSED_MFMA16")) == 1;
-    c->no_lshare = getenv("KNN_NO_LIST_SHARE") != nullptr;
-    c->no_cursor = getenv("KNN_NO_SCAN_CURSOR") != nullptr;
-    c->no_pace = getenv("KNN_NO_FUSED_PACE") != nullptr;
-    c->rescore_all = getenv("KNN_RESCORE_ALL") != nullptr;
-    c->merge_kernel = getenv("KNN_DIRECT_MERGE_KERNEL") != nullptr;
     if (c->device < 0 || c->device >= ndev) { delete c; return KNN_ENODEV; }
     hipDeviceProp_t prop;
     if (hipSetDevice(c->device) != hipSuccess || hipGetDeviceProperties(&prop, c->device) != hipSuccess) {
@@ -1040,7 +1014,7 @@ knn_status knn_create(knn_ctx** out, const knn_opts* opts) {
             return KNN_EHIP;
         }
     // GEMM-path candidate workspace: 12 B x 64 CAPW per query; passes of at most a quarter of
-    // the free HBM (KNN_WS_QUERIES / KNN_BATCH_ROWS override, for tests)
+    // the free HBM (the test hooks above override)
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
         c->ws_queries = std::max<int64_t>(4096, (int64_t)(free_b / 4) / (12 * 64 * KNN_RESCORE_CAPW + 64));
@@ -1223,7 +1197,7 @@ knn_status predict_core(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te
     }
     if (c->profile == 2 && gemm) {
         // diagnostic only: total candidates kept by the filter (last pass)
-        std::vector<int32_t> h(std::min(pass, te->n) * c->subs * c->stats[2]);
+        std::vector<int32_t> h(std::min(pass, te->n) * KNN_FILTER_SUBSLICES * c->stats[2]);
         if (hipMemcpy(h.data(), c->cnt.p, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost) == hipSuccess) {
             int64_t tot = 0;
             for (int32_t v : h) tot += v;

@@ -1,5 +1,5 @@
 // knn_device.h -- device helpers shared by the kernel translation units of libknn_amd
-// (knn_kernels.hip, knn_metric.hip, knn_fused.hip, knn_fused16.hip, knn_vote_weighted.hip, knn_regress.hip): keys and
+// (knn_kernels.hip, knn_metric.hip, knn_fused.hip, knn_vote_weighted.hip, knn_regress.hip): keys and
 // wave bitonic networks, the vote and outputs of a finished wave list, the lane-shift insert, bf16 helpers, ordered-float bits, LDS-DMA issue and the GEMM filter tile
 // geometry.
 #pragma once
@@ -10,7 +10,6 @@
 #include <stdint.h>
 
 #include "knn_kernels.h"
-#include "knn_study.h"
 
 typedef unsigned long long u64;
 
@@ -467,7 +466,7 @@ __device__ void finish_query(const u64 (&T)[R], int k, int C, const int32_t* __r
     }
     if (lane == 0) {
         o.pred[q] = bad ? 0 : (int32_t)(0xffffffffu - (uint32_t)(best & 0xffffffffull));
-        if (bad && !KNN_STUDY_RESULTS_INVALID) atomicOr(status, KNN_STATUS_TOO_FEW);
+        if (bad) atomicOr(status, KNN_STATUS_TOO_FEW);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();

@@ -12,8 +12,7 @@
 // fma; the slow path takes each lane's passing values, computes the certificate bounds
 //   G = qn + y,  Delta = coef (qn + tmax_tile) + eta + rho,  L = G - Delta <= D <= U = G + Delta
 // (D: the reference's direct-form distance, main.cpp:14-23) and keeps (row, L, U) for
-// the exact rescore (k_rescore).  (The KNN_STUDY_AUG64 build keeps the round-2 layout at
-// d = 64: rows augmented by 16 bf16 columns carrying the norm split, k_aug_rows.)
+// the exact rescore (k_rescore).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,110 +23,17 @@
 
 #include "knn_device.h"
 #include "knn_kernels.h"
-#include "knn_study.h"
 
 // Constants of the filter (each measured against its alternatives; DESIGN.md "Filter studies")
-#ifndef KNN_STUDY_PF
 static constexpr int FUSED_PF = 6;            // A-fragment prefetch depth, in MFMAs
-#else
-static constexpr int FUSED_PF = KNN_STUDY_PF;  // (study builds pf4 / pf8)
-#endif
 static constexpr int FUSED_DEFER_EVERY = 64;  // 8-wave heap shapes: tiles between flushes of the queued values
 static constexpr int FUSED_SHARE_EVERY = 64;  // tiles between threshold exchanges of a query's pieces (gthr)
 static constexpr int FUSED_RQ = 4;            // queued passing values per lane (heap shapes)
-#ifndef KNN_FUSED_LIST_SHARE
-#define KNN_FUSED_LIST_SHARE 1                // pieces exchange threshold lists (a.lshare; QG = 1)
-#endif
-#ifndef KNN_FUSED_FORWARD
-#define KNN_FUSED_FORWARD 0                   // balanced ranges in range order (study; default: from the end)
-#endif
-#ifndef KNN_FUSED_LIST_FIRST
-#define KNN_FUSED_LIST_FIRST 31               // first list exchange after this tile (then doubling)
-#endif
-#ifndef KNN_FUSED_TF_GLOBAL
-#define KNN_FUSED_TF_GLOBAL 1                 // fast-test tile term from the maxima over all tiles (a.tsmax)
-#endif
-#ifndef KNN_FUSED_IDLE_SKIP
-#define KNN_FUSED_IDLE_SKIP 1                 // a wave with no valid query issues its tile DMAs and barriers only
-#endif
-#ifndef KNN_FUSED_DMA_FRONT
-#define KNN_FUSED_DMA_FRONT 0                 // (study) a group's tile DMAs all issued right after its barrier
-#endif
-#ifndef KNN_FUSED_LIST_EVERY
-#define KNN_FUSED_LIST_EVERY (1 << 30)        // list exchanges: tiles 32, 64, 128, ... (+ every this many)
-#endif
-
-// ---------------------------------------------------------------------------------
-// k_aug_rows<E>: rows of the fused filter, [n][d + 16] bf16.  Element c < d is
-// rn(scale * x[r][c]) (scale = 1: train, -2: queries; exact scaling by a power of two);
-// the augmented block is the three-term bf16 split of norms[r] (train: tn = hi + mid +
-// lo + r, |r| <= 2^-24 tn, each subtraction exact by Sterbenz) or (1, 1, 1) (queries,
-// norms == NULL), then zeros.  One thread per 4 elements: a float4 (or 4 bf16) in, one
-// 8-byte bf16 quad out.
-// ---------------------------------------------------------------------------------
-// bf16 bits of the smallest bf16 >= x (x >= 0 finite): an upper bound stays one
-__device__ __forceinline__ uint32_t bf16_up(float x) {
-    const uint32_t b = __float_as_uint(x);
-    return (b >> 16) + ((b & 0xffffu) ? 1u : 0u);
-}
-
-template <typename E>
-__global__ __launch_bounds__(256) void k_aug_rows(const E* __restrict__ x, int64_t n, int64_t n_valid, int ld,
-                                                  int d, const float* __restrict__ norms, float scale,
-                                                  bf16_t* __restrict__ out, const float4* __restrict__ tstat,
-                                                  const int32_t* __restrict__ gate) {
-    if (gate && *gate == 0) return;
-    const int per_row = (d + 16) >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n * per_row; i += (int64_t)gridDim.x * 256) {
-    const int64_t r = i / per_row;
-    const int c = (int)(i - r * per_row) * 4;
-    uint32_t w0 = 0u, w1 = 0u;
-    if (c == d + 8 && tstat && (r & 31) == 0 && (r >> 6) < (n_valid + 63) >> 6) {
-        // the 64-row tile's statistics (k_row_norms, over its valid rows), rounded up
-        const float4 t = tstat[r >> 6];
-        w0 = bf16_up(t.x) | (bf16_up(t.y) << 16);
-        w1 = bf16_up(t.z);
-    } else if (r >= n_valid) {
-        // pad rows up to the 64-row tile grid (train only): zero features and tn_hi = 0x1.fep127,
-        // so y = tn - 2 q.t ~ 1.7e38 never passes a fast test; their indices are past row_end
-        if (c == d && norms) w0 = 0x7f7fu;
-    } else if (c < d) {
-        const float4 v = load4(x + r * ld + c);
-        w0 = bf16_rne(scale * v.x) | (bf16_rne(scale * v.y) << 16);
-        w1 = bf16_rne(scale * v.z) | (bf16_rne(scale * v.w) << 16);
-    } else if (c == d) {
-        if (norms) {
-            const float t = norms[r];
-            const uint32_t hi = bf16_rne(t);
-            const float r1 = t - __uint_as_float(hi << 16);
-            const uint32_t mid = bf16_rne(r1);
-            const uint32_t lo = bf16_rne(r1 - __uint_as_float(mid << 16));
-            w0 = hi | (mid << 16);
-            w1 = lo;
-        } else {
-            w0 = 0x3f803f80u;  // bf16 1.0, 1.0
-            w1 = 0x00003f80u;  // 1.0, 0
-        }
-    }
-    *reinterpret_cast<uint2*>(out + r * (int64_t)(d + 16) + c) = make_uint2(w0, w1);
-    }
-}
-
-hipError_t knn_launch_aug_rows(const void* x, int elem, int64_t n, int64_t n_valid, int ld, int d, const float* norms,
-                               float scale, uint16_t* out, const float4* tstat, hipStream_t st, const int32_t* gate) {
-    const int64_t total = n * ((d + 16) / 4);
-    if (total <= 0) return hipSuccess;
-    if (d % 4 || ld % 4) return hipErrorInvalidValue;
-    const dim3 grid(gated_grid(elementwise_grid(total), gate));
-    if (elem == ELEM_BF16)
-        hipLaunchKernelGGL(k_aug_rows<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, n, n_valid, ld, d, norms, scale,
-                           (bf16_t*)out, tstat, gate);
-    else
-        hipLaunchKernelGGL(k_aug_rows<float>, grid, dim3(256), 0, st, (const float*)x, n, n_valid, ld, d, norms, scale,
-                           (bf16_t*)out, tstat, gate);
-    KNN_LAUNCH_CHECK();
-    return hipSuccess;
-}
+static constexpr int FUSED_LIST_FIRST = 31;   // first list exchange after this tile (then doubling: tiles 32, 64, 128, ...)
+// ... and after every this many tiles: never in practice (tile 2^30 - 1 is a doubling point
+// too), but the compiler does not see that, and without the term the list-exchange kernels lose
+// four instructions -- kept so that removing the study hooks left every kernel's code unchanged
+static constexpr int FUSED_LIST_EVERY = 1 << 30;
 
 // ---------------------------------------------------------------------------------
 // k_tn_rows<E>: operand rows of the filter (no augmented columns).
@@ -317,11 +223,11 @@ hipError_t knn_launch_tile_stat_max(const float4* tstat, int64_t n, float4* out,
 }
 
 // ---------------------------------------------------------------------------------
-// k_gemm_fused<RB, MINW, NBUF, NW, RG>: the filter (RB = bytes per augmented row,
-// 2d + 32).  Block = NW waves x 32 queries; a train tile has BN = 32 RG rows, copied
+// k_gemm_fused<RB, MINW, NBUF, NW, RG>: the filter (RB = bytes per operand row,
+// 2d; d for the int8 class).  Block = NW waves x 32 queries; a train tile has BN = 32 RG rows, copied
 // global -> LDS by LDS-DMA (NBUF buffers, one barrier per tile, pieces issued between
 // the MFMAs) with each row padded to RB + 16 bytes (conflict-free ds_read_b128 of the A
-// fragments).  Lane (j, h) holds 16 bytes of its query's augmented row per k-step in
+// fragments).  Lane (j, h) holds 16 bytes of its query's row per k-step in
 // VGPRs (the B fragment) for the whole scan; register r of accumulator c holds train
 // row 32c + (r & 3) + 8 (r >> 2) + 4h of the tile against query j.  Per tile each wave
 // issues the MFMAs of tile it into X while the fast test of tile it-1 (Y) runs in
@@ -338,19 +244,6 @@ hipError_t knn_launch_tile_stat_max(const float4* tstat, int64_t n, float4* out,
 // ---------------------------------------------------------------------------------
 // fused_piece: one piece of work -- query tile qt against train rows [row_begin, row_end),
 // piece (segment) id seg of that query tile (its candidate sub-slices, 2 seg + h)
-#if KNN_FUSED_STAMPS
-// per-wave sums over the launch: barrier wait, step, slow path, piece cycles, tiles with a
-// slow path, tiles, pieces (read by knn_debug_stamps; study build only)
-__device__ unsigned long long g_knn_stamps[8];
-extern "C" int knn_debug_stamps(unsigned long long* out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_knn_stamps), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-    if (reset) {
-        static const unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_knn_stamps), zero, sizeof(zero)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
 
 // Pacing of the blocks of one XCD (a.pace; the balanced schedule): every FUSED_SHARE_EVERY tiles
 // a block adds a step to its XCD's sum, and while it is more than FUSED_PACE_LEAD steps ahead of
@@ -409,24 +302,21 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     typedef typename std::conditional<I8, int4, float4>::type accx4;  // one header read of four accumulator starts
     typedef int intx4 __attribute__((ext_vector_type(4)));
     constexpr int EB = I8 ? 1 : 2;  // bytes per operand element
-    // TN (RB = 2d, the product): train tiles carry their rows' norms in a header, and each
-    // accumulator starts from them (the MFMA's C operand) -- no augmented k-step.  Otherwise
-    // (RB = 2d + 32, the KNN_STUDY_AUG64 build at d = 64) the norm rides in 16 augmented columns
-    // (one more k-step).
-    constexpr bool TN = RB % 64 == 0;
-    constexpr int BN_ = 32 * RG;
-    constexpr int HS = TN ? BN_ / 4 + 1 : 0;  // header slots: BN fp32 norms + the statistics
+    // train tiles carry their rows' norms in a header, and each accumulator starts from them (the
+    // MFMA's C operand)
+    static_assert(RB % 64 == 0, "operand rows: whole k-steps");
+    constexpr int HS = 32 * RG / 4 + 1;  // header slots: BN fp32 norms + the statistics
     // QG 32-query groups per wave (QG = 2: 64 queries per wave on 32-row tiles, the register-list
     // shapes only): accumulator c holds row group c % RG against query group c / RG, so each A
     // fragment read from LDS feeds QG MFMAs and each tile copy serves 32 QG NW queries
     typedef FilterTile<RB, NW, QG, RG, HS> FT;
     constexpr int NACC = FT::NACC, BN = FT::BN, BM = FT::BM, STRIDE = FT::STRIDE;
     constexpr int DMA_INS = FT::DMA_INS, TILE = FT::TILE, HDR = FT::HDR;
-    // bytes of one tile in the train operand (TN: a block of rows + header; else rows of pitch RB)
+    // bytes of one tile in the train operand (a block of rows + header)
     constexpr int64_t TB = (int64_t)BN * RB + 16 * HS;
     constexpr int NT = 64 * NW;
     constexpr int DMA_PER_WAVE = (DMA_INS + NW - 1) / NW;
-    constexpr int NS = RB / 32;                  // k-steps: d/16 feature steps (+ the norm step)
+    constexpr int NS = RB / 32;                  // k-steps: d/16 feature steps
     constexpr int VPS = (16 + NS - 1) / NS;      // fast-test values per k-step per accumulator
     static_assert(NBUF == 2 || NBUF == 4 || NBUF == 8 || NBUF == 16, "tile buffers: two, four (pairs), eight (quads), 16 (octets)");
     // NBUF = 4: tiles go in pairs -- one barrier per pair; the DMA of tile it + 2 is issued
@@ -442,8 +332,8 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     constexpr bool RL = KR > 0;                   // thresholds from per-lane register lists (else LDS heaps)
     // (QG = 2 on 64-row tiles, four accumulators, was tried at d = 64: 1.5 KB of scratch spills)
     static_assert(QG == 1 || (QG == 2 && RG == 1 && RL), "64-query waves: 32-row tiles, register lists");
-    static_assert(!I8 || (RL && KR <= 32 && TN && PAIR && KNN_FUSED_TF_GLOBAL && !KNN_STUDY_NO_NORM),
-                  "int8 operands: the register-list shapes, header norms, the global tile term");
+    static_assert(!I8 || (RL && KR <= 32 && PAIR),
+                  "int8 operands: the register-list shapes, the global tile term");
     constexpr int LL = KR == 104 ? 52 : KR == 8 ? 8 : 16;  // register list length (one per lane half)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* tiles = smem;                                     // [NBUF][TILE]
@@ -499,7 +389,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     bool any_q = false;
 #pragma unroll
     for (int g = 0; g < QG; g++) any_q = any_q || qvalid[g];
-    const bool wave_live = !KNN_FUSED_IDLE_SKIP || KNN_FUSED_DMA_FRONT || __ballot(any_q) != 0ull;
+    const bool wave_live = __ballot(any_q) != 0ull;
     float root = INF;  // (heap shapes, QG = 1) this query's heap root, mirrored in both lanes
     float qe2[QG], eq2[QG];  // 2 |q| and 2 |q - rq|, rounded up
 #pragma unroll
@@ -519,8 +409,8 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // covers the reordered additions); the slow path still bounds L, U with the tile's own
     // statistics, read when it runs (the tile's buffer is not rewritten before the next group's
     // DMA: PAIR shapes, AHEAD = GRP).  On uniform rows the tile maxima vary by a few 1e-4 of the
-    // band.  KNN_FUSED_TF_GLOBAL=0: the per-tile term (round 5).
-    constexpr bool TFG = KNN_FUSED_TF_GLOBAL && PAIR && TN;
+    // band.  The two-buffer shapes keep the per-tile term (round 5).
+    constexpr bool TFG = PAIR;
     float tk[QG], tfc[QG];  // (TFG) the tile term and the fast-test threshold, per query group
     [[maybe_unused]] int tic[QG];  // (I8) the integer fast-test threshold of tfc
     if constexpr (TFG) {
@@ -544,23 +434,14 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     auto tf_of = [&](int g, float2 tq) __attribute__((always_inline)) {
         return fmaf(coef + 0x1p-18f, tq.x, tfb[g]) + tq.y;
     };
-    // the tile's statistics, from its LDS image (TN: the header's last slot, fp32; the
-    // KNN_STUDY_AUG64 layout: augmented columns d+8..d+10 of row 0, bf16): one broadcast read,
-    // in order with the fragment reads -- no scalar memory load in the loop
+    // the tile's statistics, from its LDS image (the header's last slot, fp32): one broadcast
+    // read, in order with the fragment reads -- no scalar memory load in the loop
     struct TQ { float2 v[QG]; };
     auto tile_q = [&](int buf) __attribute__((always_inline)) -> TQ {
-        float tx, ty, tz;
-        if constexpr (TN) {
-            const float4 w = *reinterpret_cast<const float4*>(tiles + buf * TILE + HDR + 4 * BN);
-            tx = w.x; ty = w.y; tz = w.z;
-        } else {
-            const uint2 w = *reinterpret_cast<const uint2*>(tiles + buf * TILE + (RB - 16));
-            tx = __uint_as_float(w.x << 16); ty = __uint_as_float(w.x & 0xffff0000u);
-            tz = __uint_as_float(w.y << 16);
-        }
+        const float4 w = *reinterpret_cast<const float4*>(tiles + buf * TILE + HDR + 4 * BN);
         TQ r;
 #pragma unroll
-        for (int g = 0; g < QG; g++) r.v[g] = make_float2(tx, fmaf(qe2[g], ty, eq2[g] * tz));
+        for (int g = 0; g < QG; g++) r.v[g] = make_float2(w.x, fmaf(qe2[g], w.y, eq2[g] * w.z));
         if constexpr (I8) {  // the tile's nu joins the band
             const float nu = *reinterpret_cast<const float*>(tiles + buf * TILE + HDR + 4 * BN + 12) * (1.0f + 0x1p-20f);
 #pragma unroll
@@ -628,12 +509,11 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     struct DmaTile { const unsigned char* src; uint32_t lds; };
     // the source of a tile: its block in the train operand (the piece's first row is a multiple
     // of 64, BN divides 64)
-    const int64_t TBR = TN ? TB : (int64_t)BN * ldb;  // operand bytes per tile
-    const unsigned char* piece_src = trainb + (row_begin / BN) * TBR;
+    const unsigned char* piece_src = trainb + (row_begin / BN) * TB;
     auto dma_desc = [&](int buf, int t) -> DmaTile {  // logical tile t of the piece
         int pt = t + rot;
         pt = pt >= ntiles ? pt - ntiles : pt;
-        return DmaTile{piece_src + (int64_t)pt * TBR, lds_tiles + (uint32_t)(buf * TILE)};
+        return DmaTile{piece_src + (int64_t)pt * TB, lds_tiles + (uint32_t)(buf * TILE)};
     };
     // The last piece of a tile is issued whole: its lanes past the header re-read the header's
     // last slot into the buffer's slack (TILE = DMA_INS KiB), so no piece needs an exec mask.
@@ -651,11 +531,6 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // ---- one tile's MFMAs into X; in between, the fast test of the previous tile (Y): a v_min3
     // chain per accumulator; returns bit 16c (x 0xffff) when some lane of accumulator c holds a
     // passing value (the slow path builds the value set, pass_set)
-    [[maybe_unused]] accx16 cnorm;  // (KNN_ABLATE_NO_NORM only)
-    if constexpr (KNN_STUDY_NO_NORM) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) cnorm[r] = (AccT)((float)a.d * (1.0f / 3.0f));
-    }
     constexpr int PF = FUSED_PF / NACC;  // k-steps of A fragments read ahead
     uint4 pa[PF], pb[PF];                // PAIR: the odd step's first fragments, read early
     auto prefetch = [&](int buf) __attribute__((always_inline)) {
@@ -678,26 +553,16 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         // accumulators of a row group share them as the first MFMA's C operand)
         // (the norms land in row group rg's query-group-0 accumulator X[rg]; at k-step 0 the other
         // query groups' MFMAs take them as their C operand first, then X[rg]'s own -- no copy)
-        if constexpr (TN && !KNN_STUDY_NO_NORM) {
 #pragma unroll
-            for (int rg = 0; rg < RG; rg++) {
+        for (int rg = 0; rg < RG; rg++) {
 #pragma unroll
-                for (int g4 = 0; g4 < 4; g4++) {
-                    const accx4 v = *reinterpret_cast<const accx4*>(tile + fused_norm_off(HDR, h, rg, g4));
-                    X[rg][4 * g4] = v.x;
-                    X[rg][4 * g4 + 1] = v.y;
-                    X[rg][4 * g4 + 2] = v.z;
-                    X[rg][4 * g4 + 3] = v.w;
-                }
+            for (int g4 = 0; g4 < 4; g4++) {
+                const accx4 v = *reinterpret_cast<const accx4*>(tile + fused_norm_off(HDR, h, rg, g4));
+                X[rg][4 * g4] = v.x;
+                X[rg][4 * g4 + 1] = v.y;
+                X[rg][4 * g4 + 2] = v.z;
+                X[rg][4 * g4 + 3] = v.w;
             }
-        } else if constexpr (TN) {
-            // (ablation KNN_ABLATE_NO_NORM: every accumulator starts from the mean row norm d/3 of
-            // the uniform generator instead of its rows' norms -- no norm reads; results invalid)
-#pragma unroll
-            for (int rg = 0; rg < RG; rg++) X[rg] = cnorm;
-        } else {
-#pragma unroll
-            for (int rg = 0; rg < RG; rg++) X[rg] = accx16{};
         }
         // (I8: the running maximum -- the test is max_r a_r >= ti)
         AccT mn[NACC];
@@ -737,19 +602,16 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
                     X[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, __builtin_bit_cast(bf16x8, qf[g][s]),
                                                                    s == 0 ? X[rg] : X[c], 0, 0, 0);
                 }
-                if (!KNN_STUDY_NO_EPI) {
 #pragma unroll
-                    for (int v = s * VPS; v < (s + 1) * VPS && v < 16; v++) {
-                        if constexpr (I8) mn[c] = max(mn[c], Y[c][v]);
-                        else mn[c] = fminf(mn[c], Y[c][v]);
-                    }
-                    // computed here, beside this k-step's MFMAs: without the opaque use the
-                    // compiler sinks the whole v_min3 chain into the last k-step, where it
-                    // runs exposed after the final MFMA
-                    if (s * VPS < 16) asm volatile("" : "+v"(mn[c]));
+                for (int v = s * VPS; v < (s + 1) * VPS && v < 16; v++) {
+                    if constexpr (I8) mn[c] = max(mn[c], Y[c][v]);
+                    else mn[c] = fminf(mn[c], Y[c][v]);
                 }
+                // computed here, beside this k-step's MFMAs: without the opaque use the
+                // compiler sinks the whole v_min3 chain into the last k-step, where it
+                // runs exposed after the final MFMA
+                if (s * VPS < 16) asm volatile("" : "+v"(mn[c]));
             }
-            KNN_FUSED_KSTEP_ORDER();
         }
         // which accumulators hold a passing value; the slow path builds their value sets
         // (pass_set) -- usually one of the two
@@ -765,15 +627,11 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // append candidate (L, U) of global row t to query group g's sub-slice of this lane half
     // (past its capacity: counted only, the rescore then sends the query to the exact scan)
     auto store_cand32 = [&](int g, float L, float U, int32_t t) __attribute__((always_inline)) {
-#ifndef KNN_STUDY_NO_STORE
         if (ccnt[g] < cap_sub) {
             const int64_t o = q[g] * (int64_t)a.cap + (int64_t)(2 * seg + h) * cap_sub + ccnt[g];
             a.cand[o] = CandRec{t, L, U};
         }
         ccnt[g]++;
-#else  // (ablation build: no candidate stores, nothing counted -- every query takes the exact scan)
-        asm volatile("" ::"v"(L), "v"(U), "v"(t));
-#endif
     };
     auto store_cand = [&](int g, float L, float U, int64_t t) __attribute__((always_inline)) {
         store_cand32(g, L, U, (int32_t)t);
@@ -1187,12 +1045,6 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     TQ tm_prev;
 #pragma unroll
     for (int g = 0; g < QG; g++) tm_prev.v[g] = make_float2(0.0f, 0.0f);
-    // study build KNN_STUDY_STAMPS: shader-clock stamps per wave (barrier wait, step, slow path)
-    [[maybe_unused]] uint64_t st_bar = 0, st_step = 0, st_slow = 0, st_visits = 0;
-    [[maybe_unused]] const uint64_t st_start = KNN_FUSED_STAMPS ? __builtin_amdgcn_s_memtime() : 0;
-    auto now = [&]() __attribute__((always_inline)) -> uint64_t {
-        return KNN_FUSED_STAMPS ? __builtin_amdgcn_s_memtime() : 0;
-    };
     // threshold exchanges between the pieces of a query (gthr): every FUSED_SHARE_EVERY tiles
     // (also after tiles 2, 4, ..., 32 measured no fewer kept rows and B 3 % slower: r04d)
     auto share_now = [&](int it) __attribute__((always_inline)) {
@@ -1210,7 +1062,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // list holds (a looser bound, never a wrong one).  Per lane half (its rows), the
     // bound the larger of the two halves' union values.
     auto list_share_now = [&](int it) __attribute__((always_inline)) {
-        return (it >= KNN_FUSED_LIST_FIRST && ((it + 1) & it) == 0) || (it & (KNN_FUSED_LIST_EVERY - 1)) == KNN_FUSED_LIST_EVERY - 1;
+        return (it >= FUSED_LIST_FIRST && ((it + 1) & it) == 0) || (it & (FUSED_LIST_EVERY - 1)) == FUSED_LIST_EVERY - 1;
     };
     auto exchange_lists = [&]() __attribute__((always_inline)) {
         if constexpr (RL) {
@@ -1265,7 +1117,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // one tile of the scan; posc: the tile's place in its barrier group (it % GRP), static
     auto iter = [&](auto posc, accx16 (&X)[NACC], accx16 (&Y)[NACC], int it) {
         constexpr int POS = decltype(posc)::value;
-        if constexpr (RL && QG == 1 && KR <= 32 && KNN_FUSED_LIST_SHARE) {
+        if constexpr (RL && QG == 1 && KR <= 32) {
             if (a.lshare && list_share_now(it)) exchange_lists();
         }
         if (share_now(it)) {
@@ -1295,40 +1147,15 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         // the tiles of this step (both of a pair) have landed -- every wave's pieces: each wave
         // waits for all of its own vector-memory ops, then the barrier -- and every wave is done
         // with the buffers the next DMAs overwrite
-        const uint64_t t0 = now();
-        if (POS == 0) {
-            if constexpr (KNN_STUDY_NO_BARRIER) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            else wait_dma_barrier();
-        }
-        const uint64_t t1 = now();
+        if (POS == 0) wait_dma_barrier();
         // this tile's terms, for its fast test in the next iteration (the tile is resident:
         // landed before this step's barrier, not overwritten before the next one)
         TQ tm_cur;
         if constexpr (!TFG) tm_cur = tile_q(it % NBUF);
-        // Tile DMAs.  Spread (the round-4 order): step it issues tile it + AHEAD's pieces between
-        // its MFMAs -- so the next group's last tile goes out in the last step before the
-        // barrier that waits for it (vmcnt(0)), and its whole memory latency is exposed at every
-        // group barrier.  Front (KNN_FUSED_DMA_FRONT, groups of GRP >= 2 tiles): right after a
-        // group's barrier, when the previous group's buffers are free, every tile of the NEXT
-        // group is issued at once, so each has a whole group's compute to land.  Measured slower
-        // everywhere (r05d, same box: A 20.56 -> 21.03 ms, B 479.6 -> 493.2, C1 1729 -> 1796, A's
-        // 8-GPU share 3.27 -> 3.39): the barrier wait is the waves' slow-path skew, not the last
-        // DMA's latency, and the burst lands on the group's first fragment reads.  A study build.
-        constexpr bool FRONT = KNN_FUSED_DMA_FRONT && PAIR;
-        if constexpr (FRONT) {
-            if (POS == 0 && !KNN_STUDY_NO_DMA) {
-#pragma unroll
-                for (int p = 0; p < GRP; p++) {
-                    const int tn = it + GRP + p;
-                    if (tn < ntiles) {
-                        const DmaTile dp = dma_desc(tn % NBUF, tn);
-#pragma unroll
-                        for (int i = 0; i < DMA_PER_WAVE; i++) dma_piece(i, dp);
-                    }
-                }
-            }
-        }
-        const bool dma_on = !FRONT && !KNN_STUDY_NO_DMA && it + AHEAD < ntiles;
+        // Tile DMAs: step it issues tile it + AHEAD's pieces between its MFMAs.  (Every tile of the
+        // next group issued at once right after a group's barrier measured slower everywhere, r05d:
+        // the barrier wait is the waves' slow-path skew, not the last DMA's latency.  DESIGN.md)
+        const bool dma_on = it + AHEAD < ntiles;
         const DmaTile dd = dma_desc((it + AHEAD) % NBUF, it + AHEAD);
         AccT tf[QG];
 #pragma unroll
@@ -1341,27 +1168,15 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         // PAIR: the pair's next tile is resident since its barrier -- its first fragments are
         // read now, so their latency hides under the slow path below
         if (POS != GRP - 1 && it + 1 < ntiles) prefetch((it + 1) % NBUF);
-        const uint64_t t2 = now();
-        if (!KNN_STUDY_NO_SLOW) {
-            if (uY) {
-                // (TFG: the previous tile's own statistics, for the bounds, from its buffer now)
-                const TQ tq = TFG ? tile_q((it - 1) % NBUF) : tm_prev;
-                if constexpr (RL) slow_rl(Y, it - 1, tf, tq, mnY, uY);
-                else if constexpr (DEFER) record(Y, it - 1, tf[0], tq.v[0], uY);
-                else slow(Y, it - 1, tf[0], tq.v[0], uY);
-            }
-            if constexpr (DEFER) {
-                if ((it & (FUSED_DEFER_EVERY - 1)) == FUSED_DEFER_EVERY - 1 && __ballot(qcnt > 0)) flush();
-            }
-        } else {
-            asm volatile("" ::"s"(uY));
+        if (uY) {
+            // (TFG: the previous tile's own statistics, for the bounds, from its buffer now)
+            const TQ tq = TFG ? tile_q((it - 1) % NBUF) : tm_prev;
+            if constexpr (RL) slow_rl(Y, it - 1, tf, tq, mnY, uY);
+            else if constexpr (DEFER) record(Y, it - 1, tf[0], tq.v[0], uY);
+            else slow(Y, it - 1, tf[0], tq.v[0], uY);
         }
-        if constexpr (KNN_FUSED_STAMPS) {
-            const uint64_t t3 = now();
-            st_bar += t1 - t0;
-            st_step += t2 - t1;
-            st_slow += t3 - t2;
-            st_visits += uY ? 1 : 0;
+        if constexpr (DEFER) {
+            if ((it & (FUSED_DEFER_EVERY - 1)) == FUSED_DEFER_EVERY - 1 && __ballot(qcnt > 0)) flush();
         }
         if constexpr (!TFG) tm_prev = tm_cur;
     };
@@ -1371,7 +1186,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         // (no valid query) the same barriers, and this wave's pieces of every tile's DMA
         for (int it = 0; it < ntiles; it++) {
             if (it % GRP == 0) wait_dma_barrier();
-            if (!KNN_STUDY_NO_DMA && it + AHEAD < ntiles) {
+            if (it + AHEAD < ntiles) {
                 const DmaTile dd = dma_desc((it + AHEAD) % NBUF, it + AHEAD);
 #pragma unroll
                 for (int i = 0; i < DMA_PER_WAVE; i++) dma_piece(i, dd);
@@ -1448,19 +1263,6 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
 #pragma unroll
     for (int g = 0; g < QG; g++)
         if (qvalid[g]) a.cnt[(int64_t)(2 * seg + h) * a.nq + q[g]] = ccnt[g];
-#if KNN_FUSED_STAMPS
-    {
-        if (lane == 0) {
-            atomicAdd(&g_knn_stamps[0], (unsigned long long)st_bar);
-            atomicAdd(&g_knn_stamps[1], (unsigned long long)st_step);
-            atomicAdd(&g_knn_stamps[2], (unsigned long long)st_slow);
-            atomicAdd(&g_knn_stamps[3], (unsigned long long)(now() - st_start));
-            atomicAdd(&g_knn_stamps[4], (unsigned long long)st_visits);
-            atomicAdd(&g_knn_stamps[5], (unsigned long long)ntiles);
-            atomicAdd(&g_knn_stamps[6], 1ull);
-        }
-    }
-#endif
 }
 
 // One piece of a block's range [x, x1) of the balanced schedule's (query tile, 64-row unit)
@@ -1470,22 +1272,16 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
 // its switch at tau + g, g = T - (x1 - x) the same for every block: two sweeps that stream the
 // train rows together through the L2s and the Infinity Cache (in range order each block would
 // start from its own row, all 260 MB of A's train operand in use at once, cycling through a
-// 256 MiB cache; KNN_FUSED_FORWARD=1: range order, a study build).  A range inside ONE query
+// 256 MiB cache).  A range inside ONE query
 // tile (about 23 % of A's blocks) has t0 <= g: started at t0 it would be a private stream
 // somewhere between the two sweeps, so it starts at unit g instead, beside the second sweep,
 // and wraps to its first g - t0 units at the end (rot; the scan order is free, fused_piece).
 struct FusedRangePiece { int64_t ql, t0, t1, rot; };
 __host__ __device__ inline FusedRangePiece knn_fused_range_piece(int64_t x, int64_t x1, int64_t T, bool first) {
     FusedRangePiece p;
-#if KNN_FUSED_FORWARD
-    p.ql = x / T;
-    p.t0 = x - p.ql * T;
-    p.t1 = p.t0 + (x1 - x) < T ? p.t0 + (x1 - x) : T;
-#else
     p.ql = (x1 - 1) / T;
     p.t0 = (x > p.ql * T ? x : p.ql * T) - p.ql * T;
     p.t1 = x1 - p.ql * T;
-#endif
     const int64_t g = T - (x1 - x);
     p.rot = first && x / T == (x1 - 1) / T && g > p.t0 && g < p.t1 ? g - p.t0 : 0;
     return p;
@@ -1553,7 +1349,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_gemm_fused(GemmFilterArgs a) 
         }
         if (!first) __syncthreads();  // every wave is done with the previous piece's LDS
         fused_piece<RB, NBUF, NW, QG, RG, KR, I8>(a, qt, seg, rb, re, rot, steps);
-        if (KNN_FUSED_FORWARD || segmode) x += adv;
+        if (segmode) x += adv;
         else x1 -= adv;
     }
     if (QG == 2 && a.pace && threadIdx.x == 0) {
@@ -1593,39 +1389,42 @@ int knn_fused_schedule(GemmFilterArgs& a, int slots, int* nseg) {
 // (the int8 operand class's header has the bf16 form's slots: bn int32 words + the statistics)
 static size_t fused_lds_of(int row_bytes, int k, int nw, int rg, int nbuf, bool heaps, int qg = 1) {
     const int bn = 32 * rg, bm = 32 * qg * nw;
-    const int hs = row_bytes % 64 == 0 ? bn / 4 + 1 : 0;  // (k_gemm_fused: TN header slots)
+    const int hs = bn / 4 + 1;  // (fused_piece: header slots)
     const int ins = (bn * (row_bytes / 16 + 1) + hs + 63) / 64;
     // (+ 16 bytes: the block's scan rotation, k_gemm_fused)
     return (size_t)nbuf * ins * 1024 + (heaps ? (size_t)bm * heap_stride(k) * sizeof(float) : 0) + 16;
 }
 
 int knn_fused_list_share_width(const FilterPlan& f) {
-    if (!KNN_FUSED_LIST_SHARE || !f.ls || !(f.kr == 8 || f.kr == 32)) return 0;
+    if (!f.ls || !(f.kr == 8 || f.kr == 32)) return 0;
     return f.kr == 32 ? 32 : 16;  // (two lane halves' lists)
 }
 
 bool knn_fused_supported(int d) { return d == 64 || d == 128 || d == 256; }
 
-// bytes per operand row in the tile image: 2d -- the accumulators start from the norms in the
-// tile header (B, d = 64: 614 -> 586 ms against the augmented k-step, r03q); the augmented block
-// (2d + 32) stays as the study build KNN_STUDY_AUG64
-int knn_fused_row_bytes(int d) { return d == 64 && KNN_FUSED_AUG64 ? 2 * d + 32 : 2 * d; }
-
-// Shapes (d = features; rows of 2d bytes).  Block = NW waves x 32 QG queries:
-//  * k <= 32 (register lists, KR = 8 / 32): 8 waves; 64 queries per wave on 32-row tiles in
-//    octets for large query counts (below), else 32 per wave on 64-row tiles -- in quads when
-//    eight buffers fit (d <= 128), else in pairs (four buffers, one barrier per two tiles:
-//    A 33.4 -> 31.3 ms against two buffers, round 2; 8-wave blocks: B 765 -> 743 ms).
-//  * d = 256, 32 < k <= 104 (KR = 104): 8 waves, 32-row tiles in quads.
-//  * k > 32 otherwise (LDS heaps, KR = 0): d = 64 in 4-wave blocks, two buffers, two blocks per
-//    CU (the other block hides the per-tile barrier and fast test of 5-step tiles); d >= 128 in
-//    8-wave blocks: pairs when they fit beside the heaps, else two buffers, else 32-row tiles.
+// Shapes (d = features; rows of 2d bytes -- the accumulators start from the norms in the tile
+// header: B, d = 64, 614 -> 586 ms against a norm k-step, r03q; int8 rows: d bytes).
+// Block = NW waves x 32 QG queries; NBUF tile buffers, one barrier per NBUF / 2 tiles (NBUF = 2: per tile):
+//  * k <= 32 (register lists, KR = 8 / 32), 8 waves:
+//      d <= 128, many queries (below): 64 queries per wave on 32-row tiles, NBUF = 16 (octets)
+//      d <= 128 otherwise:             32 per wave on 64-row tiles, NBUF = 8 (quads), list exchange
+//      d = 256:                        32 per wave on 64-row tiles, NBUF = 4 (pairs: eight buffers
+//                                      do not fit), list exchange
+//    (pairs against two buffers: A 33.4 -> 31.3 ms, round 2; 8-wave blocks: B 765 -> 743 ms)
+//  * d = 256, 32 < k <= 104 (KR = 104): 8 waves, 32 per wave on 32-row tiles, NBUF = 8 (quads).
+//  * k > 32 otherwise (LDS heaps, KR = 0): d = 64 in 4-wave blocks on 64-row tiles, NBUF = 2, two
+//    blocks per CU (the other block hides the per-tile barrier and fast test of 5-step tiles) while
+//    two blocks' heaps fit; else 8-wave blocks: 64-row tiles with NBUF = 4 when they fit beside
+//    the heaps, else NBUF = 2, else 32-row tiles with NBUF = 2, else no plan (nw = 0).
 // Register lists, one per lane half: k <= 16 8 entries (KR = 8), k <= 32 16 (KR = 32: exact
 // 32-entry lists cost a block per CU of occupancy and 9 % of time on B).
+// The register-list tile groups above always fit: they hold no heaps, so their LDS does not
+// depend on k (d = 128: 16 x 9 KiB and 8 x 18 KiB = 144 KiB; d = 256: 4 x 34 KiB = 136 KiB and
+// 8 x 17 KiB).  k_gemm_fused is instantiated for exactly these (fused_fn_k).
 FilterPlan knn_fused_plan(int d, int k, int64_t nq, int num_cus, const FusedForce& force, int max_pieces, bool i8) {
-    // int8 operand rows (d bytes): d = 128, the register-list shapes at their default tile groups
-    if (i8 && (d != 128 || k > 32 || force.m16 || force.nbuf != 0 || KNN_FUSED_AUG64)) return FilterPlan{0, 0, 0, 0, 0, 0, 0};
-    const int rb = i8 ? d : knn_fused_row_bytes(d);
+    // int8 operand rows (d bytes): d = 128, the register-list shapes
+    if (i8 && (d != 128 || k > 32)) return FilterPlan{0, 0, 0, 0, 0, 0, 0};
+    const int rb = i8 ? d : 2 * d;
     const size_t cap = 160 * 1024 - 256;  // room for the kernel's static LDS
     // d = 256, 32 < k <= 104 (C): per-half 52-entry register lists instead of LDS heaps, so
     // the tile buffers get the LDS the heaps held -- 32-row tiles in quads (one barrier per 128
@@ -1652,35 +1451,24 @@ FilterPlan knn_fused_plan(int d, int k, int64_t nq, int num_cus, const FusedForc
     // k): 18,750 queries (37 tiles x 5 pieces = 71 % of the CUs) 4.57 -> 4.83, 21,875 (84 %)
     // 5.21 -> 5.02, 25,000 5.73 -> 5.19, 50,000 11.02 -> 10.10, 75,000 16.49 -> 14.50, 90,000
     // 18.27 -> 16.83; B's rows (2 pieces): 31,250 (48 %) 17.2 -> 29.1, 62,500 (96 %) 31.9 -> 30.7.
-    // force.qg = 1|2 forces the choice (a study override, snapshot at knn_create).
+    // force.qg = 1|2 forces the choice (a test hook, snapshot at knn_create).
     // (d = 256 keeps 32 queries per wave: two query groups' operands alone are 128 VGPRs)
     const bool fills = (nq + 511) / 512 * (int64_t)std::max(max_pieces, 1) * 5 >= (int64_t)4 * num_cus;
     const bool qg2 = d <= 128 && (force.qg == 2 || (force.qg != 1 && (nq >= (int64_t)384 * num_cus || fills)));
     // tiles in octets: 16 buffers, one barrier per eight 32-row tiles, the loop running whole
     // groups so each tile's place is static (pairs -> quads: B 557.2 -> 501.1 ms, A 22.61 ->
     // 21.67 ms, r04i; quads -> octets: A 21.49 -> 20.80 ms, B 504.6 -> 483.8 ms, r04y).
-    // force.nbuf = 4|8 forces pairs or quads (a study override).
-    // the v_mfma_f32_16x16x32_bf16 form of a register-list shape (k_gemm_fused16: same tiles,
-    // blocks, LDS image and schedule; a study switch until measured)
-    auto m16 = [&](FilterPlan f) {
-        if (force.m16 && knn_fused16_ptr(d, f)) f.m16 = 1;
-        return f;
-    };
-    if (kr > 0 && qg2) {
-        const int nb = force.nbuf == 4 || force.nbuf == 8 ? force.nbuf : 16;
-        return m16(make(8, 1, 2, fused_lds_of(rb, k, 8, 1, nb, false, 2) <= cap ? nb : 8, 2));
-    }
+    if (kr > 0 && qg2) return make(8, 1, 2, 16, 2);
     if (kr == 104) return make(8, 1, 2, 8);
     // list exchange between a query's pieces (a.lshare, knn_capi.cpp): the QG = 1 shapes only
     // (QG = 2 with it: A 21.81 -> 22.84 ms; on A's 8-GPU share, 10 pieces, 3.55 ms against
     // QG = 1's 3.38 -- more pieces, more kept rows: r04l, r04p)
     if (kr > 0) {
-        // 64-row tiles in quads when eight buffers fit (d <= 128): A's 8-GPU share 3.08 -> 2.96 ms,
-        // A at QG = 1 23.05 -> 22.31 (r04u); force.nbuf = 4 forces pairs (a study override)
-        const bool q8 = force.nbuf != 4 && fused_lds_of(rb, k, 8, 2, 8, false) <= cap;
-        FilterPlan f = make(8, 2, 2, q8 ? 8 : 4);
+        // 64-row tiles in quads where eight buffers fit (d <= 128): A's 8-GPU share 3.08 -> 2.96 ms,
+        // A at QG = 1 23.05 -> 22.31 (r04u)
+        FilterPlan f = make(8, 2, 2, d <= 128 ? 8 : 4);
         f.ls = 1;
-        return m16(f);
+        return f;
     }
     if (kr == 0 && d == 64 && fused_lds_of(rb, k, 4, 2, 2, true) <= cap / 2) return make(4, 2, 2, 2);
     if (fused_lds_of(rb, k, 8, 2, 4, kr == 0) <= cap) return make(8, 2, 2, 4);
@@ -1689,26 +1477,18 @@ FilterPlan knn_fused_plan(int d, int k, int64_t nq, int num_cus, const FusedForc
     return FilterPlan{0, 0, 0, 0, 0, 0, 0};  // k too large for the LDS heaps: not supported
 }
 
+// the kernel of plan f's shape; nullptr: a shape knn_fused_plan never makes
 template <int RB, int KR, bool I8 = false>
 static const void* fused_fn_k(const FilterPlan& f) {
 #define KNN_FUSED_FN(NB, NW, QG, RG) reinterpret_cast<const void*>(&k_gemm_fused<RB, 2, NB, NW, QG, RG, KR, I8>)
-    if constexpr (I8) {
-        // (knn_fused_plan: 64 queries per wave in octets, or 32 per wave on 64-row tiles in quads)
-        static_assert(KR == 8 || KR == 32, "int8 operands: register lists, k <= 32");
+    static_assert(!I8 || ((KR == 8 || KR == 32) && RB == 128), "int8 operands: register lists, k <= 32, d = 128");
+    if constexpr (KR == 104) {
+        return KNN_FUSED_FN(8, 8, 1, 1);
+    } else if constexpr (KR > 0 && RB <= 256) {  // d <= 128: 64 queries per wave in octets, or quads of 64-row tiles
         if (f.qg == 2) return f.nbuf == 16 ? KNN_FUSED_FN(16, 8, 2, 1) : nullptr;
         return f.nbuf == 8 ? KNN_FUSED_FN(8, 8, 1, 2) : nullptr;
-    } else if constexpr (KR == 104) {
-        return KNN_FUSED_FN(8, 8, 1, 1);
-    } else if constexpr (KR > 0) {
-        // register lists always fit the pairs shape
-        if constexpr (RB <= 256) {  // (QG = 2: d <= 128, knn_fused_plan)
-            if (f.qg == 2)
-                return f.nbuf == 16 ? KNN_FUSED_FN(16, 8, 2, 1) : f.nbuf == 8 ? KNN_FUSED_FN(8, 8, 2, 1) : KNN_FUSED_FN(4, 8, 2, 1);
-        }
-        if constexpr (RB <= 256) {  // (quads of 64-row tiles: d <= 128, knn_fused_plan)
-            if (f.nbuf == 8) return KNN_FUSED_FN(8, 8, 1, 2);
-        }
-        return KNN_FUSED_FN(4, 8, 1, 2);
+    } else if constexpr (KR > 0) {  // d = 256: pairs
+        return f.qg == 1 && f.nbuf == 4 ? KNN_FUSED_FN(4, 8, 1, 2) : nullptr;
     } else {
         if (f.nw == 4) return KNN_FUSED_FN(2, 4, 1, 2);
         if (f.rg == 2) return f.nbuf == 4 ? KNN_FUSED_FN(4, 8, 1, 2) : KNN_FUSED_FN(2, 8, 1, 2);
@@ -1725,15 +1505,10 @@ static const void* fused_fn(const FilterPlan& f) {
 
 static const void* fused_ptr(int d, const FilterPlan& f) {
     if (f.i8) {
-        if (d != 128 || f.m16) return nullptr;
+        if (d != 128) return nullptr;
         return f.kr == 8 ? fused_fn_k<128, 8, true>(f) : f.kr == 32 ? fused_fn_k<128, 32, true>(f) : nullptr;
     }
-    if (f.m16) return knn_fused16_ptr(d, f);
-    if (d == 64) {
-        if constexpr (KNN_FUSED_AUG64) return fused_fn<160>(f);
-        else return fused_fn<128>(f);
-    }
-    return d == 128 ? fused_fn<256>(f) : fused_fn<512>(f);
+    return d == 64 ? fused_fn<128>(f) : d == 128 ? fused_fn<256>(f) : fused_fn<512>(f);
 }
 
 bool knn_fused_has_kernel(int d, const FilterPlan& f) { return knn_fused_supported(d) && f.nw > 0 && fused_ptr(d, f) != nullptr; }
@@ -1744,13 +1519,11 @@ hipError_t knn_fused_occupancy(int d, const FilterPlan& f, int* blocks_per_cu) {
 }
 
 hipError_t knn_launch_fused(const GemmFilterArgs& a, const FilterPlan& f, hipStream_t st) {
-    const int ld = f.i8 ? a.d : knn_fused_row_bytes(a.d) / 2;  // operand row pitch in elements
-    if (!knn_fused_supported(a.d) || f.nw == 0 || a.ld_t != ld || a.ld_q != ld || !a.qstat)
-        return hipErrorInvalidValue;
-    if (f.i8 ? !(a.i8_s2 > 0.0f && fused_ptr(a.d, f)) : a.i8_s2 != 0.0f) return hipErrorInvalidValue;
-    if (f.m16 && !knn_fused16_ptr(a.d, f)) return hipErrorInvalidValue;
-    if (f.kr > 0 && !(f.nw == 8 && (((f.nbuf == 4 || f.nbuf == 8) && f.qg == 1 && f.rg == 2 && f.kr <= 32) ||
-                                     ((f.nbuf == 4 || f.nbuf == 8 || f.nbuf == 16) && f.qg == 2 && f.rg == 1 && f.kr <= 32) ||
+    // (operand rows are packed: a pitch of d elements, bf16 or int8)
+    if (!knn_fused_has_kernel(a.d, f) || a.ld_t != a.d || a.ld_q != a.d || !a.qstat) return hipErrorInvalidValue;
+    if (f.i8 ? !(a.i8_s2 > 0.0f) : a.i8_s2 != 0.0f) return hipErrorInvalidValue;
+    if (f.kr > 0 && !(f.nw == 8 && ((f.nbuf == (a.d == 256 ? 4 : 8) && f.qg == 1 && f.rg == 2 && f.kr <= 32) ||
+                                     (f.nbuf == 16 && f.qg == 2 && f.rg == 1 && f.kr <= 32) ||
                                      (f.nbuf == 8 && f.qg == 1 && f.rg == 1 && f.kr == 104 && a.d == 256))))
         return hipErrorInvalidValue;  // (fused_fn_k)
     void* args[] = {const_cast<GemmFilterArgs*>(&a)};
@@ -1769,13 +1542,13 @@ hipError_t knn_launch_fused(const GemmFilterArgs& a, const FilterPlan& f, hipStr
 // per tile, LDS row stride, slots per row, header offset, header slots, DMA pieces, buffer bytes}
 template <int RB, int RG>
 static void fused_image_of(int* out) {
-    constexpr int HS = RB % 64 == 0 ? 32 * RG / 4 + 1 : 0;  // (as fused_piece)
+    constexpr int HS = 32 * RG / 4 + 1;  // (as fused_piece)
     typedef FilterTile<RB, 8, 1, RG, HS> FT;
     const int v[8] = {RB, FT::BN, FT::STRIDE, FT::SLOTS, FT::HDR, HS, FT::DMA_INS, FT::TILE};
     for (int i = 0; i < 8; i++) out[i] = v[i];
 }
 extern "C" int knn_fused_debug_image(int d, int rg, int* out) {
-    if (!knn_fused_supported(d) || KNN_FUSED_AUG64 || (rg != 1 && rg != 2)) return -1;
+    if (!knn_fused_supported(d) || (rg != 1 && rg != 2)) return -1;
     if (d == 64) rg == 1 ? fused_image_of<128, 1>(out) : fused_image_of<128, 2>(out);
     else if (d == 128) rg == 1 ? fused_image_of<256, 1>(out) : fused_image_of<256, 2>(out);
     else rg == 1 ? fused_image_of<512, 1>(out) : fused_image_of<512, 2>(out);
@@ -1811,6 +1584,21 @@ extern "C" int knn_fused_debug_piece_map(int d, int nw, int rg, int tiles, uint3
     return ins;
 }
 
+// The plan knn_fused_plan makes (qg 0|1|2 and heaps as FusedForce): out[11] = {nw, qg, rg, minw,
+// nbuf, bm, lds, kr, ls, i8, whether the library holds the plan's kernel}
+extern "C" int knn_fused_debug_plan(int d, int k, long long nq, int num_cus, int qg, int heaps, int max_pieces, int i8,
+                                    long long* out) {
+    if (!knn_fused_supported(d) || k < 1) return -1;
+    FusedForce force;
+    force.qg = qg;
+    force.heaps = heaps != 0;
+    const FilterPlan f = knn_fused_plan(d, k, nq, num_cus, force, max_pieces, i8 != 0);
+    const long long v[11] = {f.nw, f.qg, f.rg, f.minw, f.nbuf, f.bm, (long long)f.lds, f.kr, f.ls, f.i8,
+                             knn_fused_has_kernel(d, f) ? 1 : 0};
+    for (int i = 0; i < 11; i++) out[i] = v[i];
+    return 0;
+}
+
 // The pieces of the balanced schedule of n_qtiles query tiles against nt train rows on `slots`
 // resident blocks, in the order the blocks run them: out[6 i] = {block, query tile, t0, t1,
 // rot, the piece's place in its block} (64-row units); with bn > 0 also out[6 i + 4] in tiles as
@@ -1842,8 +1630,7 @@ extern "C" int knn_fused_debug_schedule(long long nt, int n_qtiles, int slots, i
                 o[4] = fused_rot_tiles(p.rot, bn, grp, nt_p);
                 o[5] = nt_p;
             }
-            if (KNN_FUSED_FORWARD) x += p.t1 - p.t0;
-            else x1 -= p.t1 - p.t0;
+            x1 -= p.t1 - p.t0;
         }
     }
     return n;

@@ -253,7 +253,6 @@ struct FilterPlan {
     size_t lds;
     int kr = 0;  // fused: register-list shape (16, 32, 104; 0 = LDS heaps)
     int ls = 0;  // fused: the kernel exchanges threshold lists between a query's pieces
-    int m16 = 0;  // fused: the v_mfma_f32_16x16x32_bf16 form of the shape (k_gemm_fused16)
     int i8 = 0;   // fused: int8 operand rows of d bytes on v_mfma_i32_32x32x32_i8 (d = 128, k <= 32)
 };
 FilterPlan knn_gemm_filter_plan(int elem, int row_bytes, int k);
@@ -274,23 +273,20 @@ hipError_t knn_launch_rescore(const RescoreArgs& a, hipStream_t st);
 // fused-norm filter (knn_fused.hip), d in {64, 128, 256}: train as tile blocks [bn rows rn(t) |
 // bn fp32 norms | tile statistics] (k_tn_rows), each accumulator starting from the norms
 bool knn_fused_supported(int d);
-// Study overrides of the fused plan (the product plan is knn_fused_plan's rule; a context
-// snapshots these once, at knn_create, from KNN_FUSED_QG / KNN_FUSED_NBUF / KNN_FUSED_HEAPS so
-// the tests can run every shape): qg 1|2 forces the queries per wave, nbuf 4|8|16 the tile
-// group, heaps the LDS-heap shape for 32 < k <= 104 at d = 256.  0 / false: the rule.
+// Test hooks of the fused plan (the product plan is knn_fused_plan's rule; a context snapshots
+// these once, at knn_create, from KNN_FUSED_QG / KNN_FUSED_HEAPS so the tests can run every
+// shape): qg 1|2 forces the queries per wave, heaps the LDS-heap shape for 32 < k <= 104 at
+// d = 256.  0 / false: the rule.
 struct FusedForce {
     int qg = 0;
-    int nbuf = 0;
     bool heaps = false;
-    bool m16 = false;  // KNN_FUSED_MFMA16=1: the 16x16x32 form of the register-list shapes (k_gemm_fused16)
 };
 // nw == 0: k too large.  nq, num_cus and max_pieces (the most pieces a query's candidate list
 // allows) pick the queries per wave (register-list shapes): 64 on 32-row tiles when the
 // 512-query blocks, at most max_pieces per query tile, fill 80 % of a round of CUs, else 32 on
 // 64-row tiles (fewer pieces per query tile).  run_gemm computes the plan once per pass and sizes the
 // operands, the occupancy, the schedule and the launch from that one plan.
-// i8: the int8 operand class (rows of d bytes; d = 128 and k <= 32 only, and no forced tile group
-// or 16x16 form: nw == 0 otherwise)
+// i8: the int8 operand class (rows of d bytes; d = 128 and k <= 32 only: nw == 0 otherwise)
 FilterPlan knn_fused_plan(int d, int k, int64_t nq, int num_cus, const FusedForce& force, int max_pieces,
                           bool i8 = false);
 hipError_t knn_fused_occupancy(int d, const FilterPlan& f, int* blocks_per_cu);
@@ -298,10 +294,8 @@ hipError_t knn_fused_occupancy(int d, const FilterPlan& f, int* blocks_per_cu);
 bool knn_fused_has_kernel(int d, const FilterPlan& f);
 // out = component maxima of n tile statistics (the fused filter's a.tsmax)
 hipError_t knn_launch_tile_stat_max(const float4* tstat, int64_t n, float4* out, hipStream_t st);
-// k_gemm_fused16's kernel for plan f (f.m16; knn_fused16.hip), nullptr if f has no 16x16x32 form
-const void* knn_fused16_ptr(int d, const FilterPlan& f);
-// candidate sub-slices per segment (piece) of plan f: one per lane half (32x32), per quarter (16x16)
-inline int knn_fused_subslices(const FilterPlan& f) { return f.m16 ? 4 : 2; }
+// candidate sub-slices per segment (piece) of the GEMM filters: one per lane half
+static constexpr int KNN_FILTER_SUBSLICES = 2;
 // whether plan f's kernel exchanges threshold lists between a query's pieces (a.lshare, lshare_w floats per piece)
 int knn_fused_list_share_width(const FilterPlan& f);
 // fills a.p1_blocks / g2 / w2 / tiles64 for the balanced schedule over `slots` resident
@@ -310,14 +304,7 @@ int knn_fused_list_share_width(const FilterPlan& f);
 int knn_fused_schedule(GemmFilterArgs& a, int slots, int* nseg);
 // f: the plan run_gemm sized the grid and operands with (knn_fused_plan)
 hipError_t knn_launch_fused(const GemmFilterArgs& a, const FilterPlan& f, hipStream_t st);
-// (study build KNN_STUDY_AUG64 only, d = 64) x [n_valid][ld] (fp32 or bf16) -> bf16 [n][d + 16]:
-// rn(scale * x) | split of norms[r] (or 1 1 1) | 0,
-// and (tstat != NULL, train) the 64-row tile statistics in columns d+8..d+10 of rows 32i;
-// rows n_valid .. n-1 (train: padding to the 64-row tile grid) never pass the filter
-hipError_t knn_launch_aug_rows(const void* x, int elem, int64_t n, int64_t n_valid, int ld, int d, const float* norms,
-                               float scale, uint16_t* out, const float4* tstat, hipStream_t st,
-                               const int32_t* gate = nullptr);
-// knn_fused_row_bytes(d) == 2d: x -> queries [n][d] bf16 rn(scale x) (norms == NULL),
+// the fused filter's operands: x -> queries [n][d] bf16 rn(scale x) (norms == NULL),
 // or train blocks of bn rows [bn][d] bf16 | bn fp32 norms | tstat of the enclosing 64-row tile
 hipError_t knn_launch_tn_rows(const void* x, int elem, int64_t n, int64_t n_valid, int ld, int d, const float* norms,
                               float scale, void* out, const float4* tstat, int bn, hipStream_t st,
@@ -331,8 +318,6 @@ hipError_t knn_launch_i8_rows(const float* x, int64_t n, int64_t n_valid, int ld
 float knn_i8_s2_of(float s);
 // the int8 filter's MFMA chain on [32][K] int8 operands (K % 32 == 0): out [32][32] int32
 hipError_t knn_launch_mfma_probe_i8(const int8_t* a, const int8_t* b, int K, int32_t* out, hipStream_t st);
-// bytes per operand row of the fused filter's tile image: 2d (2d + 32 in the KNN_STUDY_AUG64 build)
-int knn_fused_row_bytes(int d);
 hipError_t knn_launch_merge(const MergeArgs& a, hipStream_t st);
 hipError_t knn_launch_generate(const GenerateArgs& a, hipStream_t st);
 // the bf16 filter's MFMA chain on [32][K] bf16 operands (certificate self-test)

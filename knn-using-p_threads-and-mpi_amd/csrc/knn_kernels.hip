@@ -37,7 +37,6 @@
 #include <type_traits>
 
 #include "knn_kernels.h"
-#include "knn_study.h"
 
 #include "knn_device.h"
 
@@ -157,7 +156,6 @@ __global__ __launch_bounds__(256) void k_exact_scan(ExactScanArgs a) {
     if (a.C > KNN_VOTE_LDS_MAX_C) counts = nullptr;  // table-free vote (vote_ballot)
     const int lane = lane_id();
     const int wave = threadIdx.x >> 6;
-    KNN_STUDY_SKIP_FALLBACK(a.qlist);
     const int64_t n_work = a.qlist ? (int64_t)(*a.qcount) : a.nq;
     const E* train = reinterpret_cast<const E*>(a.train);
     const E* test = reinterpret_cast<const E*>(a.test);
@@ -1050,13 +1048,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_gemm_filter(GemmFilterArgs a)
                     }
 #pragma unroll
                     for (int vv = 0; vv < VPS; vv++) {
-                        if (!KNN_STUDY_NO_EPI) {
-                            const float y = epi_y(16 * c + s * VPS + vv);
-                            asm volatile("" ::"v"(y));  // computed here, beside this MFMA
-                            mn[c] = fminf(mn[c], y);
-                        } else {
-                            asm volatile("" ::"v"(Y[c][(s * VPS + vv) & 15]));
-                        }
+                        const float y = epi_y(16 * c + s * VPS + vv);
+                        asm volatile("" ::"v"(y));  // computed here, beside this MFMA
+                        mn[c] = fminf(mn[c], y);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);  // keep this k-step's order (prefetch, MFMA, VALU)
@@ -1077,10 +1071,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_gemm_filter(GemmFilterArgs a)
 #pragma unroll
                 for (int c = 0; c < NACC; c++)
 #pragma unroll
-                    for (int vv = 0; vv < VPS; vv++) {
-                        if (!KNN_STUDY_NO_EPI) mn[c] = fminf(mn[c], epi_y(16 * c + s * VPS + vv));
-                        else asm volatile("" ::"v"(Y[c][(s * VPS + vv) & 15]));
-                    }
+                    for (int vv = 0; vv < VPS; vv++) mn[c] = fminf(mn[c], epi_y(16 * c + s * VPS + vv));
             }
         }
         bool any = false;
@@ -1286,18 +1277,14 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_gemm_filter(GemmFilterArgs a)
         // tile it landed; every wave is done with the buffer / ring slot the next DMA
         // overwrites (tile it-1's, read last iteration)
         wait_dma_barrier();
-        const bool dma_on = !KNN_STUDY_NO_DMA && it + NBUF - 1 < ntiles;
+        const bool dma_on = it + NBUF - 1 < ntiles;
         const DmaTile dd = dma_desc((it + NBUF - 1) % NBUF, (it + NBUF - 1) % NR, r0 + (int64_t)(NBUF - 1) * BN);
         const bool any = step(X, Y, it % NBUF, (it + NR - 1) % NR, dma_on, dd);
-        if (!KNN_STUDY_NO_SLOW) {
-            if constexpr (DEFER) {
-                if (any && it > 0) record(Y, it - 1);
-                if ((it & (DEFER_EVERY - 1)) == DEFER_EVERY - 1 && __ballot(qcnt > 0)) flush();
-            } else if (any && it > 0) {
-                slow(Y, it - 1);
-            }
-        } else if (any) {
-            asm volatile("" ::"v"(Y[0][0]), "v"(Y[NACC - 1][3]));
+        if constexpr (DEFER) {
+            if (any && it > 0) record(Y, it - 1);
+            if ((it & (DEFER_EVERY - 1)) == DEFER_EVERY - 1 && __ballot(qcnt > 0)) flush();
+        } else if (any && it > 0) {
+            slow(Y, it - 1);
         }
     };
     for (int it = 0; it < ntiles; it += 2) {
@@ -1349,27 +1336,8 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_gemm_filter(GemmFilterArgs a)
 //  * The survivors (L <= threshold) reuse su as their compact index list.
 // LDS per wave: q row [ld_pad] f32 | counts [C] i32 (C <= KNN_VOTE_LDS_MAX_C) | su [su_cap]
 // ---------------------------------------------------------------------------------
-#if KNN_FUSED_STAMPS
-// study build (KNN_STUDY_STAMPS): per-query phase cycles of k_rescore, written (plain vector
-// stores, no shared counter) into a caller's [nq][10] u64 buffer -- [0] fill counts, [1]
-// records staged, [2] bisection, [3] compaction, [4] survivor distances, [5] selection + vote,
-// [6] 1, [7] survivors, [8] record batches, [9] bisection rounds
-__device__ unsigned long long* g_knn_rst_buf;
-__device__ long long g_knn_rst_n;
-extern "C" int knn_debug_rescore_stamps_buffer(void* buf, long long n) {
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_knn_rst_buf), &buf, sizeof(buf)) != hipSuccess) return -1;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_knn_rst_n), &n, sizeof(n)) == hipSuccess ? 0 : -1;
-}
-#endif
-
 template <int R, int CAPW, typename E>
 __device__ __forceinline__ void rescore_query(const RescoreArgs& a, const int64_t q, unsigned char* my) {
-    [[maybe_unused]] uint64_t rst[7] = {};
-    [[maybe_unused]] int rounds = 0;
-    auto rstamp = [&](int i) __attribute__((always_inline)) {
-        if constexpr (KNN_FUSED_STAMPS) rst[i] = __builtin_amdgcn_s_memtime();
-    };
-    rstamp(0);
     const int lane = lane_id();
     float* qs = reinterpret_cast<float*>(my);
     int* counts = a.c_lds_bytes ? reinterpret_cast<int*>(my + a.q_lds_bytes) : nullptr;  // NULL: vote_ballot
@@ -1397,7 +1365,6 @@ __device__ __forceinline__ void rescore_query(const RescoreArgs& a, const int64_
         if (lane >= j) incl += o;
     }
     const int total = __shfl(incl, 63);
-    rstamp(1);
     if (overflow || total < k) {
         if (lane == 0) a.fb_list[atomicAdd(a.fb_count, 1)] = (int32_t)q;
         return;
@@ -1420,18 +1387,6 @@ __device__ __forceinline__ void rescore_query(const RescoreArgs& a, const int64_
     // expected count) re-reads the rest from the candidate arrays in each bisection round
     const int su_cap = a.su_cap;
     int m = 0;
-    [[maybe_unused]] auto rstamps_flush = [&]() __attribute__((always_inline)) {
-#if KNN_FUSED_STAMPS
-        rstamp(6);
-        unsigned long long* o = g_knn_rst_buf;
-        if (o && q < g_knn_rst_n && lane < 10) {
-            const unsigned long long v = lane < 6 ? (unsigned long long)(rst[lane + 1] - rst[lane])
-                                       : lane == 6 ? 1ull : lane == 7 ? (unsigned long long)m
-                                       : lane == 8 ? (unsigned long long)nreg : (unsigned long long)rounds;
-            o[q * 10 + lane] = v;
-        }
-#endif
-    };
     // survivors' indices in su[0, m): exact distances, selection, vote
     auto finish_selection = [&](const int m) __attribute__((always_inline)) {
         u64 T[R];
@@ -1462,10 +1417,6 @@ __device__ __forceinline__ void rescore_query(const RescoreArgs& a, const int64_
                 key = make_key(direct_dist_batched(qs, train + (int64_t)t * a.ld_t, a.d), t);
             }
             if (lane < m && key == KEY_NONE) key = 0xffffffff00000000ull | t;
-            if constexpr (KNN_FUSED_STAMPS) {
-                (void)__ballot(key != 0ull);  // (the distances are in registers before the stamp)
-                rstamp(5);
-            }
             int rank = 0;
             for (int jj = 0; jj < m; jj++) {
                 const u64 kj = ((u64)__builtin_amdgcn_readlane((uint32_t)(key >> 32), jj) << 32) |
@@ -1478,10 +1429,8 @@ __device__ __forceinline__ void rescore_query(const RescoreArgs& a, const int64_
             T[0] = hi == 0xffffffffu ? KEY_NONE : (((u64)hi << 32) | lo);
             const int labp = __builtin_amdgcn_ds_permute(dst, lab);
             finish_query<R>(T, k, a.C, a.labels, counts, q, a.out, a.status, &labp);
-            rstamps_flush();
             return;
         } else {
-            rstamp(5);
             u64 kth = KEY_NONE;
             for (int b = 0; b < m; b += 64) {
                 u64 key = KEY_NONE;
@@ -1497,7 +1446,6 @@ __device__ __forceinline__ void rescore_query(const RescoreArgs& a, const int64_
             }
         }
         finish_query<R>(T, k, a.C, a.labels, counts, q, a.out, a.status);
-        rstamps_flush();
     };
     // Staged selection (the fused filter: a.gthr).  tb = the filter's final bound for this
     // query, >= the k-th smallest U of all its candidates; a candidate with L > tb cannot
@@ -1561,7 +1509,6 @@ __device__ __forceinline__ void rescore_query(const RescoreArgs& a, const int64_
                 cmin = min(cmin, (uint32_t)__shfl_xor((int)cmin, j));
                 cmax = max(cmax, (uint32_t)__shfl_xor((int)cmax, j));
             }
-            rstamp(2);
             uint32_t lo = cmin, hi = cmax;
             while (hi - lo > 1024u) {
                 const uint32_t mid = lo + ((hi - lo) >> 1);
@@ -1570,10 +1517,8 @@ __device__ __forceinline__ void rescore_query(const RescoreArgs& a, const int64_
                 for (int b = 0; b < 4; b++)
                     if (b < nbc) c += __popcll(__ballot(ub[b] <= mid));
                 if (c >= k) hi = mid; else lo = mid + 1;
-                if constexpr (KNN_FUSED_STAMPS) rounds++;
             }
             const float thr = o2f(hi);
-            rstamp(3);
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();  // every staged entry is in registers: su is free
             m = 0;
@@ -1644,7 +1589,6 @@ __device__ __forceinline__ void rescore_query(const RescoreArgs& a, const int64_
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        rstamp(2);
         // the threshold: the smallest x with #{U <= x} >= k, or any x above it -- every x >= it
         // is a valid bound (it only admits more survivors) -- so the bisection stops at 2^10
         // ordered-float steps (2^-13 relative), far inside the certificate's band
@@ -1668,10 +1612,8 @@ __device__ __forceinline__ void rescore_query(const RescoreArgs& a, const int64_
                 c += __popcll(__ballot(e < total && u <= mid));
             }
             if (c >= k) hi = mid; else lo = mid + 1;
-            if constexpr (KNN_FUSED_STAMPS) rounds++;
         }
         const float thr = o2f(hi);
-        rstamp(3);
         // compact survivors L <= thr into su (a write never overtakes an unread entry; more
         // survivors than su holds -- pathological ties -- send the query to the exact scan)
         m = 0;
@@ -1708,7 +1650,6 @@ __device__ __forceinline__ void rescore_query(const RescoreArgs& a, const int64_
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
-    rstamp(4);
     finish_selection(m);
 }
 
@@ -1850,7 +1791,7 @@ __global__ __launch_bounds__(256) void k_merge_vote(MergeArgs a) {
     }
     if (lane == 0) {
         o.pred[q] = bad ? 0 : (int32_t)(0xffffffffu - (uint32_t)(best & 0xffffffffull));
-        if (bad && !KNN_STUDY_RESULTS_INVALID) atomicOr(a.status, KNN_STATUS_TOO_FEW);
+        if (bad) atomicOr(a.status, KNN_STATUS_TOO_FEW);
     }
 }
 

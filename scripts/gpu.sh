@@ -5,7 +5,6 @@
 #   RUNS="tag cfg [VAR=v ...] [--flag=v ...]; ..."
 #                      same-box bench lines: one bench.py run per spec, its summary printed
 #                      (step, filter, rescore, candidates per query); STEPS / WARMUP per run
-#   STAMPS=<variant>   scripts/stamps.py on build/study/libknn_amd_<variant>.so (a -DKNN_STUDY_STAMPS build)
 #   TESTS=1            the whole -m gpu suite (PYTEST_K narrows it, PYTEST_ENV="VAR=v ..." sets env;
 #                      TESTS_ALT_ENV="VAR=v ..." runs it a second time under that env)
 #   BENCHES="A L B"    full bench lines (default steps, CPU baselines on) -> gpurun_out/${TAG}_bench_<cfg>.log
@@ -38,12 +37,6 @@ for spec in "${SPECS[@]}"; do
       || { echo "bench $tag failed"; tail -5 gpurun_out/${TAG}_$tag.log; exit 1; }
   summ gpurun_out/${TAG}_$tag.log
 done
-
-if [ -n "$STAMPS" ]; then  # per-wave cycle split of the filter (study build, scripts/build_variant.sh)
-  KNN_AMD_LIB=$R/knn-using-p_threads-and-mpi_amd/build/study/libknn_amd_$STAMPS.so timeout -k 10 400 \
-      python -u scripts/stamps.py > gpurun_out/${TAG}_stamps.log 2>&1 || { echo "stamps failed"; tail -5 gpurun_out/${TAG}_stamps.log; exit 1; }
-  grep -v amdgpu.ids gpurun_out/${TAG}_stamps.log
-fi
 
 if [ "$TESTS" = 1 ]; then
   env $PYTEST_ENV timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread \

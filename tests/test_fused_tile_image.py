@@ -1,10 +1,12 @@
-"""CPU-side checks of the fused filter's tile copy and schedule (k_gemm_fused), through the
+"""CPU-side checks of the fused filter's tile copy, schedule and plan (k_gemm_fused), through the
 host views the library exports of the functions and tile geometry its kernel runs
 (knn_fused_debug_image, knn_fused_debug_read_off, knn_fused_debug_piece_map,
-knn_fused_debug_schedule): the bank model of the LDS image's fragment reads, the piece map of
-the LDS-DMA (which wave issues which 1 KiB piece, and from which source bytes), and the balanced
-schedule's cover and rotations.  No GPU call."""
+knn_fused_debug_schedule, knn_fused_debug_plan): the bank model of the LDS image's fragment reads,
+the piece map of the LDS-DMA (which wave issues which 1 KiB piece, and from which source bytes),
+the balanced schedule's cover and rotations, and the plan rule's shapes (each has a kernel and
+fits the LDS).  No GPU call."""
 import ctypes
+import itertools
 import math
 
 import numpy as np
@@ -29,6 +31,8 @@ def lib(knn):
     lib.knn_fused_debug_read_off.argtypes = [I, I, I, I, I, I, I, P, P]
     lib.knn_fused_debug_read_off.restype = I
     lib.knn_fused_debug_schedule.restype = I
+    lib.knn_fused_debug_plan.argtypes = [I, I, ctypes.c_longlong, I, I, I, I, I, P]
+    lib.knn_fused_debug_plan.restype = I
     return lib
 
 
@@ -183,3 +187,61 @@ def test_balanced_schedule_covers_and_rotates(lib, nqt, cus, nt, bn, grp):
         assert pieces.max() <= max_splits(nt, 10)
     if (nqt, nt) == (196, 1_000_000):
         assert (units[:, 4] > 0).sum() >= 0.2 * grid.value   # A: about 23 % of the blocks
+
+
+PLAN_FIELDS = ("nw", "qg", "rg", "minw", "nbuf", "bm", "lds", "kr", "ls", "i8", "has_kernel")
+PLAN_GRID = dict(d=[64, 128, 256], k=[1, 8, 16, 17, 32, 33, 64, 100, 104, 105, 128],
+                 nq=[1, 255, 256, 512, 3125, 12500, 25000, 100000, 1000000], num_cus=[64, 256],
+                 max_pieces=[1, 2, 5, 8, 16, 32], qg=[0, 1, 2], heaps=[0, 1], i8=[0, 1])
+
+
+def plan_grid(lib):
+    """Every point of PLAN_GRID with the plan knn_fused_plan makes for it."""
+    out = np.zeros(len(PLAN_FIELDS), np.int64)
+    ptr = out.ctypes.data
+    for d, k, nq, cus, mp, qg, heaps, i8 in itertools.product(*PLAN_GRID.values()):
+        assert lib.knn_fused_debug_plan(d, k, nq, cus, qg, heaps, mp, i8, ptr) == 0
+        yield (d, k, nq, cus, mp, qg, heaps, i8), dict(zip(PLAN_FIELDS, out.tolist()))
+
+
+def test_every_plan_has_a_kernel_and_fits_the_lds(lib):
+    """Over PLAN_GRID (every k at which the rule changes shape, query counts on both sides of the
+    fill rule, both forced queries per wave, the forced heap shape, both operand classes): a
+    plan has a kernel in the library and fits 160 KiB of LDS less the 256 bytes the plan leaves
+    for the kernel's static LDS; 64-query waves only at d <= 128; int8 plans only at d = 128,
+    k <= 32; and each shape has the tile buffers the comment block above knn_fused_plan states --
+    for the heap shapes, whose buffers depend on k, the largest group that fits."""
+    cap = 160 * 1024 - 256
+    tile = {(d, rg): image(lib, d, rg)["tile"] for d in (64, 128, 256) for rg in (1, 2)}
+    n_plans = 0
+    for (d, k, nq, cus, mp, qg, heaps, i8), f in plan_grid(lib):
+        at = (d, k, nq, cus, mp, qg, heaps, i8)
+        kr = 8 if k <= 16 else 32 if k <= 32 else 104 if (k <= 104 and d == 256 and not heaps) else 0
+        if i8 and not (d == 128 and k <= 32):
+            assert f["nw"] == 0, at
+            continue
+        if f["nw"] == 0:
+            assert kr == 0 and not f["has_kernel"], at   # only the LDS heaps can be too large
+            continue
+        n_plans += 1
+        assert f["has_kernel"] == 1 and 0 < f["lds"] <= cap, (at, f)
+        assert f["kr"] == kr and f["i8"] == i8 and f["bm"] == 32 * f["qg"] * f["nw"] and f["minw"] == 2, (at, f)
+        assert f["qg"] == 1 or (f["qg"] == 2 and d <= 128 and kr in (8, 32)), (at, f)
+        if qg == 1 or (qg == 2 and d <= 128 and kr in (8, 32)):
+            assert f["qg"] == qg, (at, f)
+        shape = (f["nw"], f["qg"], f["rg"], f["nbuf"], f["ls"])
+        if kr in (8, 32):
+            want = (8, 2, 1, 16, 0) if f["qg"] == 2 else (8, 1, 2, 8 if d <= 128 else 4, 1)
+            assert shape == want, (at, f)
+        elif kr == 104:
+            assert shape == (8, 1, 1, 8, 0), (at, f)
+        else:
+            # LDS heaps: lds = nbuf tiles + the block's heaps (4 hs bytes per query) + 16
+            heap8 = (f["lds"] - 16 - f["nbuf"] * tile[d, f["rg"]]) * 256 // f["bm"]
+            small = 2 * tile[d, 2] + heap8 // 2 + 16          # the 4-wave shape's LDS
+            if d == 64 and small <= cap // 2:
+                assert shape == (4, 1, 2, 2, 0), (at, f)
+                continue
+            fits = [(rg, nb) for rg, nb in ((2, 4), (2, 2), (1, 2)) if nb * tile[d, rg] + heap8 + 16 <= cap]
+            assert fits and shape == (8, 1, fits[0][0], fits[0][1], 0), (at, f, fits)
+    assert n_plans >= 12960   # (at least the register-list points: 5 of 11 k, and int8 at d = 128)

@@ -7,7 +7,7 @@ exact fp32 rescore unchanged -- so every output must equal the direct form's bit
     C oracle on a sample, at d = 128, k in {1, 10, 16, 17, 32}, both queries-per-wave shapes, on
     uniform / clustered / aligned-residual / duplicate / saturating / planted inputs, with tails on
     both axes, and on a shape whose query tiles are cut into many pieces (list exchange);
-  * eligibility (non-finite rows, forced study shapes), the operand cache and the scale rebuild.
+  * eligibility (non-finite rows, an outlier's scale), the operand cache and the scale rebuild.
 
 Every parity case asserts stats()["filter_element"] == "i8": the form under test really ran.
 """
@@ -253,15 +253,6 @@ def test_outlier_scale_stays_exact(knn, oracle):
     assert _same(got, ref)
 
 
-def test_forced_16x16_shape_has_no_i8_form(knn, oracle, monkeypatch):
-    monkeypatch.setenv("KNN_FUSED_MFMA16", "1")
-    nt, nq, k = 65_536, 1024, 10
-    train, labels, test = _inputs(knn, oracle, nt, nq, "uniform")
-    got, st = _pair(knn, "gemm_i8", train, labels, test, k)
-    assert st["filter_element"] == "bf16" and st["filter_mfma"] == 16, st
-    assert _same(got, _reference(knn, oracle, nt, nq, "uniform", k))
-
-
 def test_auto_takes_i8_on_unit_range_rows(knn, oracle):
     """AUTO at a filter size (d = 128, k <= 32, fp32): the int8 form, under the class's code."""
     nt, nq, k = 65_536, 1024, 10
@@ -297,15 +288,6 @@ def test_auto_nonfinite_train_runs_bf16(knn, oracle):
     assert st["filter_element"] == "bf16", st
     ref, _ = _pair(knn, "direct", t2, labels, test, k)
     assert _same(got, ref)
-
-
-def test_auto_forced_16x16_runs_bf16(knn, oracle, monkeypatch):
-    monkeypatch.setenv("KNN_FUSED_MFMA16", "1")
-    nt, nq, k = 65_536, 1024, 10
-    train, labels, test = _inputs(knn, oracle, nt, nq, "uniform")
-    got, st = _pair(knn, "auto", train, labels, test, k, cache_train=True)
-    assert st["filter_element"] == "bf16", st
-    assert _same(got, _reference(knn, oracle, nt, nq, "uniform", k))
 
 
 def test_auto_without_train_cache_keeps_bf16(knn, oracle):
