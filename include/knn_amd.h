@@ -495,8 +495,10 @@ int32_t knn_stage_times(const knn_ctx* ctx, const char** names, float* ms, int32
  * one shape), 0 when no fused filter ran, [10] the fused filter's queries per
  * wave (32 or 64, knn_fused_plan's rule; 0: no fused filter ran), [11] the element the filter
  * multiplied: 1 int8 (KNN_ALGO_GEMM_I8's form; [3] stays 3, fp32 rows rounded once to a narrow
- * MFMA operand), 0 the data's own type or bf16.  Returns the number written (<= 12); a caller
- * that asks for 11 gets the first 11 as before. */
+ * MFMA operand), 0 the data's own type or bf16, [12] the records the int8 filter parked in LDS
+ * for its batched slow path in the last pass (counted under profile = 2 only, like [0]; 0
+ * otherwise).  Returns the number written (<= 13); a caller that asks for 11 or 12 gets the
+ * first 11 or 12 as before. */
 int32_t knn_last_stats(const knn_ctx* ctx, int64_t* out, int32_t n);
 
 /*

@@ -74,6 +74,8 @@ struct knn_ctx {
     DBuf cursor;            // fused filter: per-XCD scan cursors (64-row units; performance hint only) on the
                             // segment schedule, or the per-XCD pacing words (int32 pairs) on the balanced one
     DBuf lshare;            // fused filter: per (query, piece) threshold lists shared between pieces
+    DBuf parkcnt;           // fused filter, profile = 2: the records its parked passes held (one 64-bit word)
+    bool park_counted = false;  // the last pass's filter counted into parkcnt
     DBuf qstat;             // fused filter: per-query {|q|, |q - rq|} upper bounds
     DBuf tblk;              // fused filter: train tile blocks [bn rows rn(t) | bn norms | tile stats]
     DBuf tctrl;             // the train norms' share of the status word: [unsafe bits, 0, max norm, 0]
@@ -98,7 +100,7 @@ struct knn_ctx {
     struct { const void* feat; int64_t n; int d, ld, dtype; uint64_t gen, epoch; bool valid; }
         tpad{nullptr, 0, 0, 0, 0, 0, 0, false};
     int rescore_su = 0;  // test hook KNN_RESCORE_SU: the rescore's LDS staging size (0 = sized)
-    // test hooks of the fused filter's plan (KNN_FUSED_QG / _HEAPS), read once at knn_create: a
+    // test hooks of the fused filter's plan (KNN_FUSED_QG / _HEAPS / _PARK), read once at knn_create: a
     // call never reads the environment, and one pass uses one plan throughout
     FusedForce fforce;
     // the device entry points reuse derived train operands across calls only under
@@ -139,11 +141,13 @@ struct knn_ctx {
     bool stage_open = false;  // the last stage_begin recorded an event (profile = 3 skips some)
     std::vector<float> stage_ms;
     std::vector<const char*> stage_names;
-    int64_t stats[12] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
+    int64_t stats[13] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
                                                       // operand type, rerun, fused, train / query H2D
                                                       // bytes, train-side filter operands from the cache,
                                                       // MFMA form, queries per wave, [11] the filter's
-                                                      // operand element (0: the data's / bf16, 1: int8)
+                                                      // operand element (0: the data's / bf16, 1: int8),
+                                                      // [12] records parked by the last pass's filter
+                                                      // (profile = 2 only, like the candidates)
     int64_t rerun_stats[3] = {0, -1, 0};    // segments, operand type, fused of AUTO's gated split re-run
     int num_cus = 256;
 };
@@ -904,6 +908,14 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     }
     g.status = c->ctrl.as<int32_t>();
     g.gate = gate;
+    // the parked passes' count, like the candidates a diagnostic of profile = 2 only: the timed
+    // path hands the kernel no counter
+    if (fused && plan.park && c->profile == 2 && !gate) {
+        HIP_OR_FAIL(c, c->parkcnt.ensure(sizeof(unsigned long long)));
+        HIP_OR_FAIL(c, hipMemsetAsync(c->parkcnt.p, 0, sizeof(unsigned long long), st));
+        g.park_cnt = c->parkcnt.as<unsigned long long>();
+    }
+    if (!gate) c->park_counted = g.park_cnt != nullptr;
     const int subs = KNN_FILTER_SUBSLICES;  // candidate sub-slices per segment: one per lane half
     if (fused && g.g2 >= 0 && nseg > 1)  // whole query tiles write only their piece's sub-slices
         HIP_OR_FAIL(c, hipMemsetAsync(c->cnt.p, 0, sizeof(int32_t) * subs * nseg * nq, st));
@@ -977,11 +989,13 @@ knn_status knn_create(knn_ctx** out, const knn_opts* opts) {
     //   KNN_RESCORE_SU=n   the rescore's LDS staging size (entries; default: sized per call)
     //   KNN_FUSED_QG=1|2   the fused filter's queries per wave, 32 or 64 (knn_fused_plan's fill rule)
     //   KNN_FUSED_HEAPS    (set) the LDS-heap shape for 32 < k <= 104 at d = 256
+    //   KNN_FUSED_PARK=0|1 the int8 filter's parked passes off (the immediate slow path) / on
     //   KNN_WS_QUERIES=n   queries per pass of the GEMM path's candidate workspace
     //   KNN_BATCH_ROWS=n   query rows per batch of the host pipeline
     if (const char* e = getenv("KNN_RESCORE_SU")) c->rescore_su = atoi(e);
     if (const char* e = getenv("KNN_FUSED_QG")) c->fforce.qg = atoi(e);
     c->fforce.heaps = getenv("KNN_FUSED_HEAPS") != nullptr;
+    if (const char* e = getenv("KNN_FUSED_PARK")) c->fforce.park = atoi(e) != 0 ? 1 : 0;
     if (c->device < 0 || c->device >= ndev) { delete c; return KNN_ENODEV; }
     hipDeviceProp_t prop;
     if (hipSetDevice(c->device) != hipSuccess || hipGetDeviceProperties(&prop, c->device) != hipSuccess) {
@@ -1028,7 +1042,7 @@ void knn_destroy(knn_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     for (DBuf* b : {&c->tnorm, &c->tnp, &c->qnorm, &c->gthr, &c->cnt, &c->cand,
-                    &c->fb_list, &c->ctrl, &c->scratch, &c->split_t, &c->split_q, &c->pad_t, &c->seg_rec, &c->arrive, &c->tmax, &c->tsmax, &c->qstat, &c->tblk, &c->tctrl, &c->cursor, &c->lshare, &c->h_train, &c->h_labels, &c->h_test, &c->h_pred,
+                    &c->fb_list, &c->ctrl, &c->scratch, &c->split_t, &c->split_q, &c->pad_t, &c->seg_rec, &c->arrive, &c->tmax, &c->tsmax, &c->qstat, &c->tblk, &c->tctrl, &c->cursor, &c->lshare, &c->parkcnt, &c->h_train, &c->h_labels, &c->h_test, &c->h_pred,
                     &c->h_dist, &c->h_idx, &c->sw_dist, &c->sw_idx, &c->sw_pred, &c->sw_qside, &c->sw_acc, &c->sw_scores,
                     &c->rg_part, &c->rg_zero, &c->rg_targets})
         b->release();
@@ -1166,7 +1180,7 @@ knn_dataset offset_rows(const knn_dataset& x, int64_t r0, int64_t n) {
 
 void reset_stats(knn_ctx* c) {
     c->stages.clear();
-    for (int i = 0; i < 12; i++) c->stats[i] = 0;
+    for (int i = 0; i < 13; i++) c->stats[i] = 0;
     c->stats[3] = -1;
 }
 
@@ -1203,6 +1217,11 @@ knn_status predict_core(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te
             for (int32_t v : h) tot += v;
             c->stats[0] = tot;
         }
+        // ... and the records the int8 filter parked (last pass; the int8 pass was not re-run on bf16)
+        unsigned long long parked = 0;
+        if (c->stats[11] == 1 && c->park_counted &&
+            hipMemcpy(&parked, c->parkcnt.p, sizeof(parked), hipMemcpyDeviceToHost) == hipSuccess)
+            c->stats[12] = (int64_t)parked;
     }
     return KNN_OK;
 }
@@ -1965,7 +1984,7 @@ int32_t knn_stage_times(const knn_ctx* c, const char** names, float* ms, int32_t
 
 int32_t knn_last_stats(const knn_ctx* c, int64_t* out, int32_t n) {
     if (!c || !out) return 0;
-    int32_t m = std::min(n, 12);
+    int32_t m = std::min(n, 13);
     for (int32_t i = 0; i < m; i++) out[i] = c->stats[i];
     return m;
 }

@@ -352,6 +352,22 @@ __host__ __device__ constexpr int fused_frag_off(int row, int h, int s, int stri
 __host__ __device__ constexpr int fused_norm_off(int hdr, int h, int rg, int g4) {
     return hdr + 4 * (4 * h) + 4 * (32 * rg + 8 * g4);
 }
+// Parked passes (k_gemm_fused<..., PARK>, DESIGN.md "Parked passes"): every thread of the block
+// owns FUSED_PARK_SLOTS record slots in LDS past the tile buffers (and the 16 bytes of the scan
+// rotation).  A record is one accumulator's 16 values of that lane, as four 16-byte quarters,
+// and one word.  Quarters lie [slot][quarter][thread] in 16-byte units, so the 64 lanes of a
+// wave reading one (slot, quarter) read 1 KiB of consecutive bytes (every b128 lane group
+// touches each bank once); the words follow, [slot][thread].  v < 4: quarter v; v == 4: the word.
+// (the slot count is a power of two: a slot index is masked with it - 1, never compared)
+static constexpr int FUSED_PARK_SLOTS = 2;
+static_assert((FUSED_PARK_SLOTS & (FUSED_PARK_SLOTS - 1)) == 0, "parked passes: slot index by mask");
+__host__ __device__ constexpr int fused_park_base(int tile_bytes) { return tile_bytes + 16; }
+__host__ __device__ constexpr int fused_park_off(int tile_bytes, int nt, int t, int s, int v) {
+    return fused_park_base(tile_bytes) +
+           (v < 4 ? ((s * 4 + v) * nt + t) * 16 : FUSED_PARK_SLOTS * 4 * nt * 16 + (s * nt + t) * 4);
+}
+__host__ __device__ constexpr int fused_park_bytes(int nt) { return FUSED_PARK_SLOTS * nt * (64 + 4); }
+
 // Tiles a fused-filter piece of `rows` rows scans: whole barrier groups (at least pairs) of bn-row
 // tiles, the extra ones past the piece's end (rejected by index)
 __host__ __device__ constexpr int fused_piece_tiles(int64_t rows, int bn, int grp) {

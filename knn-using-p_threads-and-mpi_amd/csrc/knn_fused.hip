@@ -34,6 +34,8 @@ static constexpr int FUSED_LIST_FIRST = 31;   // first list exchange after this 
 // too), but the compiler does not see that, and without the term the list-exchange kernels lose
 // four instructions -- kept so that removing the study hooks left every kernel's code unchanged
 static constexpr int FUSED_LIST_EVERY = 1 << 30;
+// parked passes on the int8 shapes unless KNN_FUSED_PARK says otherwise (knn_fused_plan)
+static constexpr bool FUSED_PARK_DEFAULT = true;
 
 // ---------------------------------------------------------------------------------
 // k_tn_rows<E>: operand rows of the filter (no augmented columns).
@@ -293,7 +295,14 @@ __device__ __forceinline__ void fused_pace(int32_t* p, int steps) {
 // the fast test max_r a_r >= ti (ti: knn_i8_fast_thr of the same tf, which carries nu) and the
 // slow path's G = qn - s2 float(a) with nu in the band.  Three sites differ from the bf16 form:
 // the MFMA, the accumulators' start, the fast test and its scans' compares.
-template <int RB, int NBUF, int NW, int QG, int RG, int KR, bool I8>
+//
+// PARK (the int8 register-list shapes; DESIGN.md "Parked passes"): a tile that passes the fast
+// test is not visited at once.  Its passing lanes copy their accumulator into a slot of their own
+// in LDS (fused_park_off) and the wave goes on with the next tile's MFMAs; every
+// FUSED_SHARE_EVERY tiles, before a list exchange and at the end of the piece all lanes take their
+// parked records through the slow path together (flush_ring).  A tile whose passing lanes do not
+// all have a free slot takes the immediate path, as without PARK.
+template <int RB, int NBUF, int NW, int QG, int RG, int KR, bool I8, bool PARK>
 __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int qt, const int seg,
                                             const int64_t row_begin, const int64_t row_end,
                                             const int64_t rot_units, int& steps) {
@@ -334,6 +343,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     static_assert(QG == 1 || (QG == 2 && RG == 1 && RL), "64-query waves: 32-row tiles, register lists");
     static_assert(!I8 || (RL && KR <= 32 && PAIR),
                   "int8 operands: the register-list shapes, the global tile term");
+    static_assert(!PARK || (I8 && NW == 8 && QG * RG == 2), "parked passes: the int8 shapes, two accumulators");
     constexpr int LL = KR == 104 ? 52 : KR == 8 ? 8 : 16;  // register list length (one per lane half)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* tiles = smem;                                     // [NBUF][TILE]
@@ -484,6 +494,12 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         *blk_rot = r0;
     }
     int rot = 0;  // (set after the barrier)
+    // (PARK) this thread's slots: quarter v of slot s at park_v + (4 s + v) 16 NT, the word at
+    // park_w + s 4 NT; pcnt: the records it holds, in slots 0 .. pcnt - 1 (a flush takes them all)
+    constexpr int PR = FUSED_PARK_SLOTS;
+    [[maybe_unused]] unsigned char* park_v = smem + fused_park_off(NBUF * TILE, 64 * NW, (int)threadIdx.x, 0, 0);
+    [[maybe_unused]] unsigned char* park_w = smem + fused_park_off(NBUF * TILE, 64 * NW, (int)threadIdx.x, 0, 4);
+    [[maybe_unused]] int pcnt = 0;
     // the first row of logical tile t (t < ntiles): physical tile (t + rot) mod ntiles
     auto tile_row = [&](int t) __attribute__((always_inline)) -> int64_t {
         int pt = t + rot;
@@ -972,6 +988,121 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         }
     };
 
+    // ---- parked passes (PARK).  park(): after a fast test with passing lanes.  When every
+    // passing lane has a free slot for each of its passing accumulators, those lanes write their
+    // records -- the accumulator's 16 values and the word 2 (logical tile) + accumulator -- under
+    // their exec mask and the tile is done for now (returns true); else nothing is written and
+    // the caller takes the immediate path.  A slot index is pcnt masked to the ring, and pcnt < PR
+    // holds wherever a record is written, so no store leaves the thread's own slots.
+    auto park = [&](accx16 (&Y)[NACC], int tp, const AccT (&tf)[QG], const AccT (&mnY)[NACC]) __attribute__((always_inline)) -> bool {
+        if constexpr (PARK) {
+            bool ps[NACC];
+            int need = 0;
+#pragma unroll
+            for (int c = 0; c < NACC; c++) {
+                ps[c] = mnY[c] >= tf[c / RG];
+                need += ps[c] ? 1 : 0;
+            }
+            if (__ballot(pcnt + need > PR)) return false;
+#pragma unroll
+            for (int c = 0; c < NACC; c++) {
+                if (ps[c]) {
+                    const int s = pcnt & (PR - 1);
+                    unsigned char* pv = park_v + s * (4 * 16 * NT);
+#pragma unroll
+                    for (int v = 0; v < 4; v++)
+                        *reinterpret_cast<int4*>(pv + v * (16 * NT)) =
+                            make_int4(Y[c][4 * v], Y[c][4 * v + 1], Y[c][4 * v + 2], Y[c][4 * v + 3]);
+                    *reinterpret_cast<int*>(park_w + s * (4 * NT)) = 2 * tp + c;
+                    pcnt++;
+                }
+            }
+            return true;
+        }
+        return false;
+    };
+    // flush_ring(): every lane's records, oldest first, one slot per round for all lanes at once.
+    // The 16 values are scanned again against the CURRENT fast-test threshold (it only tightens;
+    // any processing order keeps every true neighbour, lane_rounds), then bounds, row_end test,
+    // candidate store and list insert as slow_rl's visit.  The tile's statistics for the bounds
+    // come from its header in the train operand (its LDS buffer may be overwritten by now): the
+    // words tile_q reads, so L and U are the immediate path's bits.  make_tfb once per query group
+    // at the end.  Called at two places only (the share tile's place and the end of the piece),
+    // so the code of the other tile places holds no copy.
+    auto flush_ring = [&](const unsigned char* piece_base) __attribute__((always_inline)) {
+        if constexpr (PARK) {
+            if (!__ballot(pcnt > 0)) return;
+            uint32_t nrec = 0;
+#pragma unroll 1
+            for (int s = 0; s < PR; s++) {
+                const bool have = pcnt > s;
+                const uint64_t hm = __ballot(have);
+                if (!hm) break;
+                nrec += (uint32_t)__popcll(hm);
+                accx16 V = accx16{};
+                int w = 0;
+                float4 st = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (have) {
+                    w = *reinterpret_cast<const int*>(park_w + s * (4 * NT));
+                    int pt = (w >> 1) + rot;
+                    pt = pt >= ntiles ? pt - ntiles : pt;
+                    st = *reinterpret_cast<const float4*>(piece_base + (int64_t)pt * TB + BN * RB + 4 * BN);
+                    const unsigned char* pv = park_v + s * (4 * 16 * NT);
+#pragma unroll
+                    for (int v = 0; v < 4; v++) {
+                        const int4 x = *reinterpret_cast<const int4*>(pv + v * (16 * NT));
+                        V[4 * v] = x.x; V[4 * v + 1] = x.y; V[4 * v + 2] = x.z; V[4 * v + 3] = x.w;
+                    }
+                }
+                const int cl = w & 1;
+                int ptl = (w >> 1) + rot;
+                ptl = ptl >= ntiles ? ptl - ntiles : ptl;
+                const int64_t tbase = row_begin + (int64_t)ptl * BN;
+                AccT mx = V[0];
+#pragma unroll
+                for (int v = 1; v < 16; v++) mx = max(mx, V[v]);
+                const float nu = st.w * (1.0f + 0x1p-20f);
+#pragma unroll
+                for (int g = 0; g < QG; g++) {
+                    const bool act = have && cl / RG == g;
+                    if (!__ballot(act)) continue;
+                    const float2 tq = make_float2(st.x, fmaf(qe2[g], st.y, eq2[g] * st.z) + nu);  // (tile_q)
+                    uint32_t m = 0u;
+                    asm volatile(KNN_FUSED_SCAN16("v_cmp_ge_i32_e32") : "+v"(m) : "v"(tic[g]), KNN_FUSED_SCAN16_Y(V) : "vcc");
+                    m = act ? m : 0u;
+                    // (as lane_rounds, k <= 32: a lane with one passing value passes with its maximum)
+                    AccT yv = mx;
+                    int idx;
+                    if (__ballot((m & (m - 1u)) != 0u)) {
+                        uint32_t e = 0u;
+                        asm volatile(KNN_FUSED_SCAN16("v_cmp_eq_i32_e32") : "+v"(e) : "v"(yv), KNN_FUSED_SCAN16_Y(V) : "vcc");
+                        idx = __ffs((int)(m & e)) - 1;
+                    } else {
+                        idx = __ffs((int)m) - 1;
+                    }
+#pragma unroll 1
+                    for (int round = 0; round < 16; round++) {
+                        const int row = 32 * (cl % RG) + (idx & 3) + 8 * (idx >> 2) + 4 * h;
+                        const int64_t t = tbase + row;
+                        float L, U;
+                        bounds(g, yv, tq, L, U);
+                        keep_row(g, idx >= 0 && t < row_end && L <= thr[g], L, U, t);
+                        m = idx >= 0 ? m & ~(1u << idx) : 0u;
+                        if (!__ballot(m != 0u)) break;
+                        idx = __ffs((int)m) - 1;
+                        yv = 0;
+#pragma unroll
+                        for (int v = 0; v < 16; v++) yv = idx == v ? V[v] : yv;
+                    }
+                }
+            }
+            pcnt = 0;
+#pragma unroll
+            for (int g = 0; g < QG; g++) make_tfb(g);
+            if (a.park_cnt && lane == 0) atomicAdd(a.park_cnt, (unsigned long long)nrec);
+        }
+    };
+
     // deferred slow path (8-wave heap shapes): passing values with L <= thr are queued -- (L,
     // U, row) in registers -- and flushed through accept() every FUSED_DEFER_EVERY tiles by all
     // waves together, or when some lane's queue is full.  A threshold waiting for the flush is
@@ -1117,6 +1248,11 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     // one tile of the scan; posc: the tile's place in its barrier group (it % GRP), static
     auto iter = [&](auto posc, accx16 (&X)[NACC], accx16 (&Y)[NACC], int it) {
         constexpr int POS = decltype(posc)::value;
+        // (PARK) the parked records go through the slow path before the thresholds are exchanged:
+        // share tiles and list exchanges all fall on a group's last place (tiles 31, 63, 127, ...)
+        if constexpr (PARK && POS == GRP - 1) {
+            if (share_now(it) || (QG == 1 && a.lshare && list_share_now(it))) flush_ring(piece_src);
+        }
         if constexpr (RL && QG == 1 && KR <= 32) {
             if (a.lshare && list_share_now(it)) exchange_lists();
         }
@@ -1168,7 +1304,7 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
         // PAIR: the pair's next tile is resident since its barrier -- its first fragments are
         // read now, so their latency hides under the slow path below
         if (POS != GRP - 1 && it + 1 < ntiles) prefetch((it + 1) % NBUF);
-        if (uY) {
+        if (uY && !park(Y, it - 1, tf, mnY)) {
             // (TFG: the previous tile's own statistics, for the bounds, from its buffer now)
             const TQ tq = TFG ? tile_q((it - 1) % NBUF) : tm_prev;
             if constexpr (RL) slow_rl(Y, it - 1, tf, tq, mnY, uY);
@@ -1249,6 +1385,8 @@ __device__ __forceinline__ void fused_piece(const GemmFilterArgs& a, const int q
     if constexpr (DEFER) {
         if (__ballot(qcnt > 0)) flush();
     }
+    // (PARK) the records still parked: the ring is empty at every return
+    if constexpr (PARK) flush_ring(piece_src);
     // the final bound of this piece, any segment count: k_rescore stages only the candidates
     // with L <= gthr (every value there is a k-th smallest U of kept rows, so >= the k-th
     // smallest U of all of them)
@@ -1295,7 +1433,7 @@ __host__ __device__ inline FusedRangePiece knn_fused_range_piece(int64_t x, int6
 // last round of blocks ends together instead of a partial wave of whole query tiles.
 // Pieces of one query tile share thresholds through gthr like segments (piece id = block -
 // the first block of that query tile).  One call site of fused_piece (instruction cache).
-template <int RB, int MINW, int NBUF, int NW, int QG, int RG, int KR, bool I8 = false>
+template <int RB, int MINW, int NBUF, int NW, int QG, int RG, int KR, bool I8 = false, bool PARK = false>
 __global__ __launch_bounds__(64 * NW, MINW) void k_gemm_fused(GemmFilterArgs a) {
     if ((a.gate && *a.gate == 0) || (*a.status & KNN_STATUS_GEMM_UNSAFE)) return;  // not taken / exact path
     const int64_t T = a.tiles64;  // 64-row units per query tile
@@ -1348,7 +1486,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_gemm_fused(GemmFilterArgs a) 
             adv = t1 - t0;
         }
         if (!first) __syncthreads();  // every wave is done with the previous piece's LDS
-        fused_piece<RB, NBUF, NW, QG, RG, KR, I8>(a, qt, seg, rb, re, rot, steps);
+        fused_piece<RB, NBUF, NW, QG, RG, KR, I8, PARK>(a, qt, seg, rb, re, rot, steps);
         if (segmode) x += adv;
         else x1 -= adv;
     }
@@ -1387,12 +1525,14 @@ int knn_fused_schedule(GemmFilterArgs& a, int slots, int* nseg) {
 // plan and launch
 // ---------------------------------------------------------------------------------
 // (the int8 operand class's header has the bf16 form's slots: bn int32 words + the statistics)
-static size_t fused_lds_of(int row_bytes, int k, int nw, int rg, int nbuf, bool heaps, int qg = 1) {
+static size_t fused_lds_of(int row_bytes, int k, int nw, int rg, int nbuf, bool heaps, int qg = 1, bool park = false) {
     const int bn = 32 * rg, bm = 32 * qg * nw;
     const int hs = bn / 4 + 1;  // (fused_piece: header slots)
     const int ins = (bn * (row_bytes / 16 + 1) + hs + 63) / 64;
     // (+ 16 bytes: the block's scan rotation, k_gemm_fused)
-    return (size_t)nbuf * ins * 1024 + (heaps ? (size_t)bm * heap_stride(k) * sizeof(float) : 0) + 16;
+    // (+ the parked passes' ring, fused_park_off: past the rotation word)
+    return (size_t)nbuf * ins * 1024 + (heaps ? (size_t)bm * heap_stride(k) * sizeof(float) : 0) + 16 +
+           (park ? (size_t)fused_park_bytes(64 * nw) : 0);
 }
 
 int knn_fused_list_share_width(const FilterPlan& f) {
@@ -1432,9 +1572,13 @@ FilterPlan knn_fused_plan(int d, int k, int64_t nq, int num_cus, const FusedForc
     // tiles in pairs, the other way to the same barrier count, spill: two more accumulators.)
     const int kr = k <= 16 ? 8 : k <= 32 ? 32 : (k <= 104 && d == 256 && !force.heaps) ? 104 : 0;
     auto make = [&](int nw, int rg, int minw, int nbuf, int qg = 1) {
-        FilterPlan f{nw, qg, rg, minw, nbuf, 32 * qg * nw, fused_lds_of(rb, k, nw, rg, nbuf, kr == 0, qg)};
+        // parked passes: the int8 register-list shapes (their half-size tiles leave the ring's
+        // 68 KiB free); force.park = 0 keeps the immediate path (a test hook, as force.qg)
+        const bool park = i8 && kr > 0 && kr <= 32 && (force.park < 0 ? FUSED_PARK_DEFAULT : force.park != 0);
+        FilterPlan f{nw, qg, rg, minw, nbuf, 32 * qg * nw, fused_lds_of(rb, k, nw, rg, nbuf, kr == 0, qg, park)};
         f.kr = kr;
         f.i8 = i8 ? 1 : 0;
+        f.park = park ? 1 : 0;
         return f;
     };
     // Register-list shapes: 64 queries per wave on 32-row tiles (QG = 2: each A fragment read
@@ -1478,10 +1622,11 @@ FilterPlan knn_fused_plan(int d, int k, int64_t nq, int num_cus, const FusedForc
 }
 
 // the kernel of plan f's shape; nullptr: a shape knn_fused_plan never makes
-template <int RB, int KR, bool I8 = false>
+template <int RB, int KR, bool I8 = false, bool PARK = false>
 static const void* fused_fn_k(const FilterPlan& f) {
-#define KNN_FUSED_FN(NB, NW, QG, RG) reinterpret_cast<const void*>(&k_gemm_fused<RB, 2, NB, NW, QG, RG, KR, I8>)
+#define KNN_FUSED_FN(NB, NW, QG, RG) reinterpret_cast<const void*>(&k_gemm_fused<RB, 2, NB, NW, QG, RG, KR, I8, PARK>)
     static_assert(!I8 || ((KR == 8 || KR == 32) && RB == 128), "int8 operands: register lists, k <= 32, d = 128");
+    static_assert(!PARK || I8, "parked passes: the int8 shapes");
     if constexpr (KR == 104) {
         return KNN_FUSED_FN(8, 8, 1, 1);
     } else if constexpr (KR > 0 && RB <= 256) {  // d <= 128: 64 queries per wave in octets, or quads of 64-row tiles
@@ -1506,6 +1651,7 @@ static const void* fused_fn(const FilterPlan& f) {
 static const void* fused_ptr(int d, const FilterPlan& f) {
     if (f.i8) {
         if (d != 128) return nullptr;
+        if (f.park) return f.kr == 8 ? fused_fn_k<128, 8, true, true>(f) : f.kr == 32 ? fused_fn_k<128, 32, true, true>(f) : nullptr;
         return f.kr == 8 ? fused_fn_k<128, 8, true>(f) : f.kr == 32 ? fused_fn_k<128, 32, true>(f) : nullptr;
     }
     return d == 64 ? fused_fn<128>(f) : d == 128 ? fused_fn<256>(f) : fused_fn<512>(f);
@@ -1522,6 +1668,7 @@ hipError_t knn_launch_fused(const GemmFilterArgs& a, const FilterPlan& f, hipStr
     // (operand rows are packed: a pitch of d elements, bf16 or int8)
     if (!knn_fused_has_kernel(a.d, f) || a.ld_t != a.d || a.ld_q != a.d || !a.qstat) return hipErrorInvalidValue;
     if (f.i8 ? !(a.i8_s2 > 0.0f) : a.i8_s2 != 0.0f) return hipErrorInvalidValue;
+    if (f.park && !f.i8) return hipErrorInvalidValue;
     if (f.kr > 0 && !(f.nw == 8 && ((f.nbuf == (a.d == 256 ? 4 : 8) && f.qg == 1 && f.rg == 2 && f.kr <= 32) ||
                                      (f.nbuf == 16 && f.qg == 2 && f.rg == 1 && f.kr <= 32) ||
                                      (f.nbuf == 8 && f.qg == 1 && f.rg == 1 && f.kr == 104 && a.d == 256))))
@@ -1597,6 +1744,26 @@ extern "C" int knn_fused_debug_plan(int d, int k, long long nq, int num_cus, int
                              knn_fused_has_kernel(d, f) ? 1 : 0};
     for (int i = 0; i < 11; i++) out[i] = v[i];
     return 0;
+}
+
+// The parked passes' ring of the int8 plan with qg 1|2 query groups per wave (d = 128):
+// out[5] = {slots per thread, threads, bytes of the tile buffers, first byte of the ring, one
+// past its last}
+extern "C" int knn_fused_debug_park(int qg, long long* out) {
+    if (qg != 1 && qg != 2) return -1;
+    int im[8];
+    if (knn_fused_debug_image(64, qg == 2 ? 1 : 2, im) != 0) return -1;  // (rows of 128 bytes: d = 64 bf16, d = 128 int8)
+    const int tiles = (qg == 2 ? 16 : 8) * im[7], nt = 512;
+    const long long v[5] = {FUSED_PARK_SLOTS, nt, tiles, fused_park_base(tiles), fused_park_base(tiles) + fused_park_bytes(nt)};
+    for (int i = 0; i < 5; i++) out[i] = v[i];
+    return 0;
+}
+// the LDS byte offset of thread t's slot s, quarter v (0..3: 16 bytes of values; 4: the word) --
+// the kernel's fused_park_off on that plan; -1: no such slot
+extern "C" long long knn_fused_debug_park_off(int qg, int t, int s, int v) {
+    long long g[5];
+    if (knn_fused_debug_park(qg, g) != 0 || t < 0 || t >= g[1] || s < 0 || s >= g[0] || v < 0 || v > 4) return -1;
+    return fused_park_off((int)g[2], (int)g[1], t, s, v);
 }
 
 // The pieces of the balanced schedule of n_qtiles query tiles against nt train rows on `slots`

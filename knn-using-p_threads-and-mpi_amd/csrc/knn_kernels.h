@@ -74,6 +74,8 @@ struct GemmFilterArgs {
     // int8 operand class (k_gemm_fused<..., I8>): s2 = fl(2 s s) of the train set's scale s; the
     // operand rows are int8, ld_t / ld_q in bytes; 0 for the bf16 operands
     float i8_s2;
+    // fused filter, parked passes (optional, profile = 2): the records parked, added per flush
+    unsigned long long* park_cnt;
 };
 
 struct RescoreArgs {
@@ -254,6 +256,7 @@ struct FilterPlan {
     int kr = 0;  // fused: register-list shape (16, 32, 104; 0 = LDS heaps)
     int ls = 0;  // fused: the kernel exchanges threshold lists between a query's pieces
     int i8 = 0;   // fused: int8 operand rows of d bytes on v_mfma_i32_32x32x32_i8 (d = 128, k <= 32)
+    int park = 0;  // fused, int8: passing tiles are parked in LDS and visited in batches (lds holds the ring)
 };
 FilterPlan knn_gemm_filter_plan(int elem, int row_bytes, int k);
 hipError_t knn_launch_gemm_filter(const GemmFilterArgs& a, int elem, int row_bytes, hipStream_t st);
@@ -274,12 +277,13 @@ hipError_t knn_launch_rescore(const RescoreArgs& a, hipStream_t st);
 // bn fp32 norms | tile statistics] (k_tn_rows), each accumulator starting from the norms
 bool knn_fused_supported(int d);
 // Test hooks of the fused plan (the product plan is knn_fused_plan's rule; a context snapshots
-// these once, at knn_create, from KNN_FUSED_QG / KNN_FUSED_HEAPS so the tests can run every
-// shape): qg 1|2 forces the queries per wave, heaps the LDS-heap shape for 32 < k <= 104 at
-// d = 256.  0 / false: the rule.
+// these once, at knn_create, from KNN_FUSED_QG / KNN_FUSED_HEAPS / KNN_FUSED_PARK so the tests can
+// run every shape): qg 1|2 forces the queries per wave, heaps the LDS-heap shape for 32 < k <= 104
+// at d = 256, park 0|1 the int8 shapes' parked passes off / on.  0 / false / -1: the rule.
 struct FusedForce {
     int qg = 0;
     bool heaps = false;
+    int park = -1;  // KNN_FUSED_PARK=0|1: the int8 shapes' parked passes off / on; -1: the rule
 };
 // nw == 0: k too large.  nq, num_cus and max_pieces (the most pieces a query's candidate list
 // allows) pick the queries per wave (register-list shapes): 64 on 32-row tiles when the
