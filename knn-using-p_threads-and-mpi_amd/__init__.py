@@ -460,7 +460,10 @@ class Context:
     def predict_device(self, train, labels, test, k, num_classes, pred, dist=None, idx=None,
                        stream=None, d=None):
         """Device tensors (torch, on this context's device) in and out (knn_predict_device).
-        train/test: [n][ld] float32 contiguous; labels/pred/idx int32; dist float32.
+        train/test: [n][ld] float32 or bfloat16 (both the same) with unit stride along the
+        features and 16-byte-aligned rows: a contiguous tensor, or a column view x[:, c0:c0 + d]
+        of a wider one (ld = its row stride); d (optional) reads only the first d columns.
+        labels/pred/idx int32, contiguous; dist float32, contiguous.
         With cache_train the train-side filter operands are kept across calls on the same,
         unmodified train tensor (rewrites through torch are seen; after writing it by other
         means call set_generation)."""

@@ -830,7 +830,10 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
         pk.valid = false;
         if (!hit) {
             HIP_OR_FAIL(c, c->pad_t.ensure(pitch * (size_t)ntp));
-            HIP_OR_FAIL(c, hipMemcpyAsync(c->pad_t.p, tr->feat, pitch * (size_t)nt, hipMemcpyDeviceToDevice, st));
+            // (the last row ends after its d elements: the caller's buffer may end there too -- a
+            // column view of a wider table, or exactly (nt - 1) * ld + d elements)
+            HIP_OR_FAIL(c, hipMemcpyAsync(c->pad_t.p, tr->feat, pitch * (size_t)(nt - 1) + es * (size_t)d,
+                                          hipMemcpyDeviceToDevice, st));
             HIP_OR_FAIL(c, hipMemsetAsync((unsigned char*)c->pad_t.p + pitch * (size_t)nt, 0, pitch * (size_t)(ntp - nt), st));
         }
         if (may_cache) pk = {tr->feat, nt, d, tr->ld, dtype, c->generation, ep, true};
