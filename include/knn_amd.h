@@ -479,6 +479,87 @@ knn_status knn_regress_sweep(knn_ctx* ctx, const knn_dataset* train, const knn_d
                              const float* query_targets, float* out_pred_all, double* out_sse,
                              double* out_sae);
 
+/*
+ * Radius neighbours: "which train rows lie within thr of this query, how many, and what do they
+ * vote?" (sklearn's radius_neighbors, RadiusNeighborsClassifier and RadiusNeighborsRegressor; no
+ * reference counterpart).  A neighbourhood may hold any number of rows, or none, so the answer is a
+ * count and a CSR list per query, not a fixed-length top-k list.
+ *   threshold  thr is a binary32 value in the units of the distance the context reports: the
+ *              SQUARED Euclidean distance under the default metric, D itself under Manhattan /
+ *              Chebyshev.  KNN_EINVAL unless 0 <= thr < FLT_MAX (NaN refused).
+ *   membership train row t is a neighbour of query q iff D(q, t) <= thr, where D is the value, bit
+ *              for bit, that knn_predict_device exports for that pair under the context's metric:
+ *              Euclidean df = fl(q_i - t_i), sum = fl(sum + fl(df * df)), i ascending, no FMA
+ *              ("Semantics"); Manhattan / Chebyshev by the rules of "Metrics", the fmaxf NaN rule
+ *              included.  A NaN or inf D is never <= thr.  bf16 rows widen exactly.
+ *   self       with self_base >= 0, train row self_base + q is not a neighbour of q.  The test is by
+ *              index: equal copies of the row stay.  Requires self_base + nq <= n_train.
+ *   counts     d_count[q], int32: the number of neighbours.  d_class_counts[q][c], int32
+ *              [nq][num_classes]: the number of neighbours with label c.  These are integers, so
+ *              any accumulation order is exact (integer atomics are used; no floating-point atomic
+ *              is used anywhere in this feature).  A train label outside [0, num_classes) gives
+ *              KNN_EINVAL, whether or not that row is anyone's neighbour; num_classes <= 16384.
+ *   vote       d_pred[q] = the argmax over c of class_counts[q][c], ties to the smallest label.  A
+ *              query with no neighbour gets outlier_label, an int32 that may take any value; this is
+ *              not an error.  d_correct (int64[1], needs d_query_labels) = the number of q with
+ *              pred[q] == label[q].
+ *   lists      CSR: d_offsets int64 [nq + 1] is the exclusive scan of count, total = offsets[nq];
+ *              d_idx int32 [total], d_dist fp32 [total].  Query q's segment is
+ *              [offsets[q], offsets[q + 1]), in ASCENDING TRAIN INDEX: a fixed order, whatever the
+ *              train segments of the pass, which makes every later sum reproducible.  The lists are
+ *              NOT distance-sorted; a caller who wants that sorts each segment itself.
+ *   weighted vote on lists: w_j is the weighted vote's binary32 weight (knn_weight: the same three
+ *              kinds and the same metric mapping -- under a non-Euclidean metric KNN_W_INV_DIST is
+ *              1.0f / D and KNN_W_INV_SQDIST is KNN_EINVAL).  Zero rule: if ANY entry of the segment
+ *              has d == 0, those entries weigh 1 and all others 0 (the lists are not distance-ordered,
+ *              so the top-k lists' "first entry" becomes "any entry").  S_c = fl(S_c + w_j) in
+ *              binary32 in ascending list position; the vote is the argmax of S_c, ties to the
+ *              smallest label.  An empty segment gives outlier_label and an all +0 score row.
+ *              d_scores is fp32 [nq][num_classes].  With KNN_W_UNIFORM this equals the count pass's
+ *              pred, and its class counts as floats.
+ *   regression on lists: N = N + (double)w_j * (double)y_j and Dn = Dn + (double)w_j in list order,
+ *              pred = (float)(N / Dn), the weights and the zero rule as above.  An empty segment
+ *              predicts NaN (as sklearn does) and is not an error.  There are no error sums.
+ *
+ * knn_radius_count_device: one distance pass (k_radius_tile, whatever the context's algo: algo
+ *   chooses among top-k forms only) under the context's metric, one synchronisation.  d_count,
+ *   d_class_counts, d_pred, d_correct and d_offsets are each optional, but not all may be NULL;
+ *   train->labels may be NULL when none of d_class_counts / d_pred / d_correct is asked.
+ * knn_radius_fill_device: the pass again, storing the lists.  The caller read offsets[nq] from a
+ *   count call with the SAME train, test, thr, self_base and metric, and allocated d_idx (and
+ *   d_dist, optional) with that many elements.  A query whose neighbours do not number
+ *   offsets[q + 1] - offsets[q] gives KNN_EINVAL ("offsets do not belong to this call"); no element
+ *   outside [offsets[q], offsets[q + 1]) is written for query q in any case.
+ * knn_radius_vote_device / knn_radius_regress_device: the vote / regression alone on lists the
+ *   caller holds (d_dist may be NULL with KNN_W_UNIFORM).  A distance that is NaN or negative, an
+ *   index outside [0, n_train) (it is not followed), offsets that decrease, or a label outside
+ *   [0, num_classes) give KNN_EINVAL.  d_pred, d_correct and d_scores are each optional, not all
+ *   NULL; regression's d_pred is fp32 [nq].
+ * nq == 0 returns KNN_OK.  With profile = 1 the stages are named "radius_count", "radius_fill",
+ * "radius_vote" and "radius_regress" (and "radius_scan" for the scan of the counts, "radius_argmax"
+ * for the vote of a pass that did not vote itself: several train segments, or more than 64 classes);
+ * knn_last_stats()[2] is the number of train segments of the pass.
+ * Not here: host-buffer entry points, a multi-rank driver (counts and class counts add over train
+ * shards, CSR lists concatenate by shard), several thresholds in one pass, distance-sorted
+ * segments, regression error sums, and an MFMA-filtered pass for high d -- the radius pass is the
+ * direct form at every shape.
+ */
+knn_status knn_radius_count_device(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test, float thr,
+                                   int32_t num_classes, int64_t self_base, int32_t outlier_label,
+                                   const int32_t* d_query_labels, int32_t* d_count, int32_t* d_class_counts,
+                                   int32_t* d_pred, int64_t* d_correct, int64_t* d_offsets, void* hip_stream);
+knn_status knn_radius_fill_device(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test, float thr,
+                                  int64_t self_base, const int64_t* d_offsets, int32_t* d_idx, float* d_dist,
+                                  void* hip_stream);
+knn_status knn_radius_vote_device(knn_ctx* ctx, int64_t nq, int64_t n_train, const int64_t* d_offsets,
+                                  const int32_t* d_idx, const float* d_dist, const int32_t* d_train_labels,
+                                  int32_t num_classes, int32_t weights, int32_t outlier_label,
+                                  const int32_t* d_query_labels, int32_t* d_pred, int64_t* d_correct,
+                                  float* d_scores, void* hip_stream);
+knn_status knn_radius_regress_device(knn_ctx* ctx, int64_t nq, int64_t n_train, const int64_t* d_offsets,
+                                     const int32_t* d_idx, const float* d_dist, const float* d_train_targets,
+                                     int32_t weights, float* d_pred, void* hip_stream);
+
 /* Per-stage device times (ms) of the last predict call when opts.profile >= 1.
  * names: optional array of n const char* to receive stage names. Returns the
  * number of stages recorded (<= n). */

@@ -191,6 +191,16 @@ int* KNN_sweep_loo_weighted(ArffData* train, int kmax, int weights);
 float* KNN_regress_sweep(ArffData* train, ArffData* test, int kmax, int weights, double* sse, double* sae);
 // Leave-one-out on the train set: row i predicted with row i taken out, scored against its target.
 float* KNN_regress_sweep_loo(ArffData* train, int kmax, int weights, double* sse, double* sae);
+// Radius classifier (knn_amd.h "Radius neighbours"; sklearn's RadiusNeighborsClassifier): the vote
+// of the train rows within `radius` of each test row -- the distance itself under every metric
+// (under the Euclidean metric the library compares the squared distance with radius * radius in
+// binary32).  weights: knn_weight.  A row with no neighbour gets outlier_label.  Returns malloc'd
+// int[n_test], caller frees; *outliers (optional) receives the number of rows with no neighbour.
+// Runs on the first device.
+int* KNN_radius(ArffData* train, ArffData* test, float radius, int weights, int outlier_label,
+                long* outliers = nullptr);
+// Leave-one-out on the train set: row i voted by the other rows within the radius.
+int* KNN_radius_loo(ArffData* train, float radius, int weights, int outlier_label, long* outliers = nullptr);
 // main.cpp:87 -- calloc'd int[C*C], C = dataset->num_classes(), row = true class.
 int* computeConfusionMatrix(int* predictions, ArffData* dataset);
 // main.cpp:102

@@ -135,6 +135,10 @@ def load_library(path=LIB_PATH):
         "knn_regress_sweep_device": (I32, [P, DS, DS, P, I32, I32, I64, P, P, P, P, P, P, P]),
         "knn_regress_device": (I32, [P, DS, DS, P, I32, I32, P, P, P, P]),
         "knn_regress_sweep": (I32, [P, DS, DS, P, I32, I32, I64, P, P, P, P]),
+        "knn_radius_count_device": (I32, [P, DS, DS, F, I32, I64, I32, P, P, P, P, P, P, P]),
+        "knn_radius_fill_device": (I32, [P, DS, DS, F, I64, P, P, P, P]),
+        "knn_radius_vote_device": (I32, [P, I64, I64, P, P, P, P, I32, I32, I32, P, P, P, P, P]),
+        "knn_radius_regress_device": (I32, [P, I64, I64, P, P, P, P, I32, P, P]),
         "knn_arff_copy_targets": (I32, [P, P, I32, P]),
         "knn_stage_times": (I32, [P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(F), I32]),
         "knn_last_stats": (I32, [P, ctypes.POINTER(I64), I32]),
@@ -776,6 +780,165 @@ class Context:
                                                _weight_kind(weights), _self_base(self_base),
                                                _ptr(qt), _ptr(pred_all), _ptr(sse), _ptr(sae)))
         return pred_all, sse, sae
+
+    # radius neighbours (knn_amd.h "Radius neighbours")
+    def _threshold(self, radius, threshold):
+        """The binary32 threshold of a radius call: exactly one of radius= (float32(r) * float32(r)
+        under the Euclidean metric, whose distances are squared; float32(r) otherwise) and
+        threshold= (passed as it is, in the units of the reported distance)."""
+        if (radius is None) == (threshold is None):
+            raise KnnError(KNN_EINVAL, "give exactly one of radius= and threshold=")
+        if threshold is not None:
+            return float(np.float32(threshold))
+        r = np.float32(radius)
+        if r < 0:
+            raise KnnError(KNN_EINVAL, f"radius must be >= 0, got {radius}")
+        with np.errstate(over="ignore"):
+            return float(r * r if self.metric == "euclidean" else r)
+
+    def radius_count_device(self, train, labels, test, radius=None, threshold=None, num_classes=None,
+                            query_labels=None, self_base=None, outlier_label=-1, class_counts=False, offsets=False,
+                            stream=None, d=None):
+        """How many train rows lie within the radius of each query, and their uniform vote
+        (knn_radius_count_device; one distance pass, no lists).  labels and num_classes may be None
+        when no class output is wanted.  Returns (count int32 [nq], pred int32 [nq] or None without
+        labels, correct int64 [1] or None without query_labels, class_counts int32 [nq][C] or None,
+        offsets int64 [nq + 1] or None).  A query with no neighbour predicts outlier_label."""
+        import torch
+        thr = self._threshold(radius, threshold)
+        tr, te = self._datasets_arg(train, labels, test, d)
+        dev = test.device
+        voting = labels is not None
+        if (voting or class_counts) and (labels is None or num_classes is None):
+            raise KnnError(KNN_EINVAL, "class outputs need labels and num_classes")
+        count = torch.empty(te.n, dtype=torch.int32, device=dev)
+        pred = torch.empty(te.n, dtype=torch.int32, device=dev) if voting else None
+        correct = None
+        if query_labels is not None:
+            if not voting:
+                raise KnnError(KNN_EINVAL, "query_labels need labels and num_classes")
+            _check_tensor(query_labels, "query_labels", torch.int32, te.n)
+            correct = torch.zeros(1, dtype=torch.int64, device=dev)
+        cc = torch.empty((te.n, num_classes), dtype=torch.int32, device=dev) if class_counts else None
+        off = torch.empty(te.n + 1, dtype=torch.int64, device=dev) if offsets else None
+        self._check(self.lib.knn_radius_count_device(
+            self.h, ctypes.byref(tr), ctypes.byref(te), thr, num_classes or 0, _self_base(self_base), outlier_label,
+            _opt_ptr(query_labels), count.data_ptr(), _opt_ptr(cc), _opt_ptr(pred), _opt_ptr(correct), _opt_ptr(off),
+            self._stream(stream, test)))
+        return count, pred, correct, cc, off
+
+    def radius_fill_device(self, train, test, offsets, radius=None, threshold=None, self_base=None,
+                           return_distance=True, stream=None, d=None):
+        """The lists that go with a count call's offsets (knn_radius_fill_device): the same train,
+        test, threshold, self_base and metric.  Reads offsets[-1] (one synchronisation) to size
+        idx int32 [total] and dist float32 [total] (None with return_distance=False)."""
+        import torch
+        thr = self._threshold(radius, threshold)
+        tr, te = self._datasets_arg(train, None, test, d)
+        _check_tensor(offsets, "offsets", torch.int64, te.n + 1)
+        total = int(offsets[te.n].item())
+        # (at least one element: an empty tensor has no address to hand to the library)
+        idx = torch.empty(max(total, 1), dtype=torch.int32, device=test.device)
+        dist = torch.empty(max(total, 1), dtype=torch.float32, device=test.device) if return_distance else None
+        self._check(self.lib.knn_radius_fill_device(
+            self.h, ctypes.byref(tr), ctypes.byref(te), thr, _self_base(self_base), offsets.data_ptr(),
+            idx.data_ptr(), _opt_ptr(dist), self._stream(stream, test)))
+        return idx[:total], None if dist is None else dist[:total]
+
+    def radius_neighbors_device(self, train, test, radius=None, threshold=None, self_base=None, return_distance=True,
+                                stream=None, d=None):
+        """sklearn's radius_neighbors as CSR lists: (offsets int64 [nq + 1], idx int32 [total], dist
+        float32 [total] or None).  Query q's neighbours are idx[offsets[q]:offsets[q + 1]], in
+        ascending train index -- NOT sorted by distance.  Runs the count pass, one .item() on
+        offsets[-1], then the fill pass."""
+        _, _, _, _, off = self.radius_count_device(train, None, test, radius, threshold, self_base=self_base,
+                                                   offsets=True, stream=stream, d=d)
+        idx, dist = self.radius_fill_device(train, test, off, radius, threshold, self_base, return_distance,
+                                            stream, d)
+        return off, idx, dist
+
+    def radius_vote_device(self, offsets, idx, dist, train_labels, num_classes, weights="uniform", outlier_label=-1,
+                           query_labels=None, scores=True, stream=None):
+        """The weighted vote alone on CSR lists the caller holds (knn_radius_vote_device; dist may
+        be None with "uniform").  Returns (pred int32 [nq], correct int64 [1] or None, scores
+        float32 [nq][C] or None)."""
+        import torch
+        self._on_device(idx)
+        nq = offsets.numel() - 1
+        _check_tensor(offsets, "offsets", torch.int64, 1)
+        _check_tensor(idx, "idx", torch.int32)
+        if dist is not None:
+            _check_tensor(dist, "dist", torch.float32, idx.numel())
+        _check_tensor(train_labels, "train_labels", torch.int32)
+        pred = torch.empty(nq, dtype=torch.int32, device=idx.device)
+        scores = self._scores_arg(scores, nq, num_classes, idx.device)
+        correct = None
+        if query_labels is not None:
+            _check_tensor(query_labels, "query_labels", torch.int32, nq)
+            correct = torch.zeros(1, dtype=torch.int64, device=idx.device)
+        self._check(self.lib.knn_radius_vote_device(
+            self.h, nq, train_labels.numel(), offsets.data_ptr(), idx.data_ptr(), _opt_ptr(dist),
+            train_labels.data_ptr(), num_classes, _weight_kind(weights), outlier_label, _opt_ptr(query_labels),
+            pred.data_ptr(), _opt_ptr(correct), _opt_ptr(scores), self._stream(stream, idx)))
+        return pred, correct, scores
+
+    def radius_regress_vote_device(self, offsets, idx, dist, train_targets, weights="uniform", stream=None):
+        """The regression alone on CSR lists the caller holds (knn_radius_regress_device): pred
+        float32 [nq], NaN for a query with no neighbour."""
+        import torch
+        self._on_device(idx)
+        nq = offsets.numel() - 1
+        _check_tensor(offsets, "offsets", torch.int64, 1)
+        _check_tensor(idx, "idx", torch.int32)
+        if dist is not None:
+            _check_tensor(dist, "dist", torch.float32, idx.numel())
+        _check_tensor(train_targets, "train_targets", torch.float32)
+        pred = torch.empty(nq, dtype=torch.float32, device=idx.device)
+        self._check(self.lib.knn_radius_regress_device(
+            self.h, nq, train_targets.numel(), offsets.data_ptr(), idx.data_ptr(), _opt_ptr(dist),
+            train_targets.data_ptr(), _weight_kind(weights), pred.data_ptr(), self._stream(stream, idx)))
+        return pred
+
+    def radius_predict_device(self, train, labels, test, radius=None, threshold=None, num_classes=None,
+                              weights="uniform", outlier_label=-1, query_labels=None, self_base=None, scores=True,
+                              stream=None, d=None):
+        """RadiusNeighborsClassifier.predict: returns (pred int32 [nq], scores float32 [nq][C] or
+        None with scores=False, count int32 [nq]); with query_labels a fourth element, correct int64
+        [1].  "uniform" takes the count pass alone (no lists are built; the scores are the class
+        counts as floats); the weighted kinds run count, fill and the vote on the lists."""
+        import torch
+        if _weight_kind(weights) == WEIGHTS["uniform"]:
+            count, pred, correct, cc, _ = self.radius_count_device(
+                train, labels, test, radius, threshold, num_classes, query_labels, self_base, outlier_label,
+                class_counts=bool(scores), stream=stream, d=d)
+            sc = cc.to(torch.float32) if cc is not None else None
+        else:
+            count, _, _, _, off = self.radius_count_device(train, None, test, radius, threshold,
+                                                           self_base=self_base, offsets=True, stream=stream, d=d)
+            idx, dist = self.radius_fill_device(train, test, off, radius, threshold, self_base, True, stream, d)
+            pred, correct, sc = self.radius_vote_device(off, idx, dist, labels, num_classes, weights, outlier_label,
+                                                        query_labels, scores, stream)
+        return (pred, sc, count) if query_labels is None else (pred, sc, count, correct)
+
+    def radius_loo_device(self, train, labels, radius=None, threshold=None, num_classes=None, weights="uniform",
+                          outlier_label=-1, scores=True, stream=None, d=None):
+        """Leave-one-out on the train set: every row predicted from the other rows within the
+        radius and scored against its own label.  Returns (pred, scores or None, count, correct)."""
+        return self.radius_predict_device(train, labels, train, radius, threshold, num_classes, weights,
+                                          outlier_label, query_labels=labels, self_base=0, scores=scores,
+                                          stream=stream, d=d)
+
+    def radius_regress_device(self, train, targets, test, radius=None, threshold=None, weights="uniform",
+                              self_base=None, stream=None, d=None):
+        """RadiusNeighborsRegressor.predict: the weighted mean of the targets of the train rows
+        within the radius, NaN where there is none.  Returns (pred float32 [nq], count int32 [nq])."""
+        import torch
+        _check_tensor(targets, "targets", torch.float32, train.shape[0])
+        count, _, _, _, off = self.radius_count_device(train, None, test, radius, threshold, self_base=self_base,
+                                                       offsets=True, stream=stream, d=d)
+        need_dist = _weight_kind(weights) != WEIGHTS["uniform"]
+        idx, dist = self.radius_fill_device(train, test, off, radius, threshold, self_base, need_dist, stream, d)
+        return self.radius_regress_vote_device(off, idx, dist, targets, weights, stream), count
 
     def generate(self, feat, labels, row0, d, kind, seed, stream_id, num_classes, dtype=None,
                  stream=None):

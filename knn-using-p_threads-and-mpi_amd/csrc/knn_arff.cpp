@@ -887,6 +887,100 @@ float* KNN_regress_sweep_loo(ArffData* train, int kmax, int weights, double* sse
     return regress_on_device0(train, train, kmax, true, weights, sse, sae);
 }
 
+// the radius classifier on the first device.  There is no host-buffer radius entry point: the train
+// set goes through the context's cached upload (knn_ctx_train_device), the queries are uploaded
+// here, and the device entry points run on the context's stream.  Uniform: the count pass alone;
+// weighted: count, fill and the vote on the lists.
+knn_status knn_ctx_train_device(knn_ctx* c, const knn_dataset* tr, knn_dataset* dtr);  // (knn_capi.cpp)
+
+static int* radius_on_device0(ArffData* train, ArffData* test, float radius, int weights, int outlier_label, bool loo,
+                              long* outliers) {
+    const KnnFlatView& tr = train->flat();
+    const KnnFlatView& te = test->flat();
+    if (!(radius >= 0.0f)) throwf("KNN_radius: radius=%g must be >= 0", (double)radius);
+    if (tr.d != te.d) throwf("KNN_radius: train has %d features, test has %d", tr.d, te.d);
+    const int64_t nq = te.n;
+    const int C = (int)train->num_classes();
+    int* pred = (int*)std::malloc(sizeof(int) * (size_t)(nq > 0 ? nq : 1));
+    if (!pred) throwf("KNN_radius: out of memory");
+    std::vector<int32_t> count((size_t)nq);
+    std::string why;
+    knn_status s = KNN_OK;
+    try {
+        std::vector<knn_ctx*>& cs = contexts();
+        knn_ctx* c = cs[0];
+        std::lock_guard<std::mutex> busy(*devices().busy[0]);
+        // the reported distance is squared under the Euclidean metric (one binary32 product)
+        const float thr = knn_get_metric(c) == KNN_METRIC_SQEUCLIDEAN ? radius * radius : radius;
+        const int dev = knn_ctx_device(c);
+        hipStream_t st = (hipStream_t)knn_ctx_stream(c);
+        knn_dataset htr{tr.feat.data(), tr.labels.data(), tr.n, tr.d, tr.ld, KNN_F32}, dtr{}, dte{};
+        s = knn_set_generation(c, tr.uid);
+        if (s == KNN_OK) s = knn_ctx_train_device(c, &htr, &dtr);
+        DevMem dq(dev, loo ? 0 : sizeof(float) * (size_t)te.ld * (size_t)nq);
+        DevMem dpred(dev, sizeof(int32_t) * (size_t)nq), dcount(dev, sizeof(int32_t) * (size_t)nq);
+        DevMem doff(dev, sizeof(int64_t) * (size_t)(nq + 1));
+        if (s == KNN_OK && (!dq.p || !dpred.p || !dcount.p || !doff.p)) throwf("KNN_radius: device allocation failed");
+        if (s == KNN_OK) {
+            if (loo) {
+                dte = dtr;
+                dte.labels = nullptr;
+            } else {
+                if (hipMemcpyAsync(dq.p, te.feat.data(), sizeof(float) * (size_t)te.ld * (size_t)nq, hipMemcpyHostToDevice,
+                                   st) != hipSuccess)
+                    throwf("KNN_radius: upload failed");
+                dte = knn_dataset{dq.p, nullptr, nq, te.d, te.ld, KNN_F32};
+            }
+            const int64_t self_base = loo ? 0 : -1;
+            if (weights == KNN_W_UNIFORM) {
+                s = knn_radius_count_device(c, &dtr, &dte, thr, C, self_base, outlier_label, nullptr, (int32_t*)dcount.p,
+                                            nullptr, (int32_t*)dpred.p, nullptr, nullptr, st);
+            } else {
+                s = knn_radius_count_device(c, &dtr, &dte, thr, 0, self_base, outlier_label, nullptr, (int32_t*)dcount.p,
+                                            nullptr, nullptr, nullptr, (int64_t*)doff.p, st);
+                int64_t total = 0;
+                if (s == KNN_OK && nq > 0 &&
+                    hipMemcpy(&total, (int64_t*)doff.p + nq, sizeof(total), hipMemcpyDeviceToHost) != hipSuccess)
+                    throwf("KNN_radius: download failed");
+                DevMem didx(dev, sizeof(int32_t) * (size_t)total), ddist(dev, sizeof(float) * (size_t)total);
+                if (s == KNN_OK && (!didx.p || !ddist.p)) throwf("KNN_radius: device allocation failed");
+                if (s == KNN_OK)
+                    s = knn_radius_fill_device(c, &dtr, &dte, thr, self_base, (const int64_t*)doff.p, (int32_t*)didx.p,
+                                               (float*)ddist.p, st);
+                if (s == KNN_OK)
+                    s = knn_radius_vote_device(c, nq, tr.n, (const int64_t*)doff.p, (const int32_t*)didx.p,
+                                               (const float*)ddist.p, dtr.labels, C, weights, outlier_label, nullptr,
+                                               (int32_t*)dpred.p, nullptr, nullptr, st);
+            }
+            if (s == KNN_OK && nq > 0 &&
+                (hipMemcpy(pred, dpred.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost) != hipSuccess ||
+                 hipMemcpy(count.data(), dcount.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost) != hipSuccess))
+                throwf("KNN_radius: download failed");
+        }
+        if (s != KNN_OK) why = knn_last_error(c);
+    } catch (...) {
+        std::free(pred);
+        throw;
+    }
+    if (s != KNN_OK) {
+        std::free(pred);
+        throwf("KNN_radius: %s (status %d)", why.c_str(), (int)s);
+    }
+    if (outliers) {
+        *outliers = 0;
+        for (int32_t n : count) *outliers += n == 0;
+    }
+    return pred;
+}
+
+int* KNN_radius(ArffData* train, ArffData* test, float radius, int weights, int outlier_label, long* outliers) {
+    return radius_on_device0(train, test, radius, weights, outlier_label, false, outliers);
+}
+
+int* KNN_radius_loo(ArffData* train, float radius, int weights, int outlier_label, long* outliers) {
+    return radius_on_device0(train, train, radius, weights, outlier_label, true, outliers);
+}
+
 void* KNN(void* params) {
     arguments* a = static_cast<arguments*>(params);
     predict_range(a->train, a->test, a->k, a->start, a->end, predictions + a->start);

@@ -6,11 +6,13 @@
 //   DIRECT:  k_exact_scan                                  (fused distance/top-k/vote)
 //   GEMM:    k_row_norms x2 -> k_gemm_filter -> k_rescore -> k_exact_scan(fallback list)
 //   a non-Euclidean metric (knn_set_metric): k_metric_tile (-> k_merge_vote), every shape
+//   radius neighbours (knn_radius_*): k_radius_tile (-> k_radius_scan / k_radius_argmax), every shape
 // Train-sharded runs use the same pipeline per shard with the vote
 // replaced by a packed (dist, global idx, label) neighbour list, then k_merge_vote.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -121,6 +123,22 @@ struct knn_ctx {
     // the vote-less pass runs with (the caller has no classes), and the host entry point's device
     // copy of the train targets
     DBuf rg_part, rg_zero, rg_targets;
+    // radius neighbours: per-(segment, query) counts [nseg][nq] and list bases [nseg][nq] int64 of
+    // a segmented pass; class counts [nq][C] / scores [nq][C] the caller did not ask for but the
+    // vote needs
+    DBuf rd_segcnt, rd_base, rd_cc, rd_scores;
+    // the pass rd_segcnt's counts came from: a fill whose pass has the same key takes them as they
+    // are instead of counting again.  (Rows rewritten in place in between are caught where stale
+    // counts would matter: the fill checks every (segment, query) count against its own.)
+    struct RadiusKey {
+        const void *train, *test; int64_t nt, nq, self_base; int d, ld_t, ld_q, dtype, metric, nseg; uint32_t thr_bits;
+        bool valid;
+        bool same(const RadiusKey& o) const {
+            return valid && o.valid && train == o.train && test == o.test && nt == o.nt && nq == o.nq &&
+                   self_base == o.self_base && d == o.d && ld_t == o.ld_t && ld_q == o.ld_q && dtype == o.dtype &&
+                   metric == o.metric && nseg == o.nseg && thr_bits == o.thr_bits;
+        }
+    } rd_key{};
     DBuf arrive;              // k_direct_rows' fused merge: per query group, segments finished
     bool arrive_clean = false;  // arrive is all zero (the last launch ran to completion)
     // host-buffer calls (knn_predict): cached train upload, two query slots streamed on a copy stream
@@ -189,7 +207,7 @@ knn_status fail(knn_ctx* c, knn_status s, const char* fmt, ...) {
 // 3.44 -> 3.56 ms per step, A 22.58 -> 22.73 (scripts/event_overhead.py, profiles/r04n).
 static bool hot_stage(const char* n) {
     static const char* const hot[] = {"gemm_filter", "rescore", "direct_tile", "metric_tile", "exact_scan", "merge_vote",
-                                      "exchange"};
+                                      "exchange", "radius_count", "radius_fill"};
     for (const char* h : hot)
         if (!strcmp(n, h)) return true;
     return false;
@@ -312,6 +330,8 @@ knn_status check_status(knn_ctx* c, const int32_t* ctrl) {
     if (status & KNN_STATUS_UNSORTED)
         return fail(c, KNN_EINVAL, "merge: a source neighbour list is not ascending by (distance, index)");
     if (status & KNN_STATUS_BAD_DIST) return fail(c, KNN_EINVAL, "weighted vote: a neighbour distance is NaN or negative");
+    if (status & KNN_STATUS_BAD_OFFSETS) return fail(c, KNN_EINVAL, "radius: the offsets do not belong to this call");
+    if (status & KNN_STATUS_BAD_INDEX) return fail(c, KNN_EINVAL, "radius: a list index is outside [0, n_train)");
     if (status & KNN_STATUS_TOO_FEW) return fail(c, KNN_ERANGE, "fewer than k train rows have a finite distance (< FLT_MAX)");
     return KNN_OK;
 }
@@ -354,6 +374,20 @@ hipError_t reset_ctrl(knn_ctx* c, hipStream_t st) {
 // k_direct_tile segments: enough (query block, segment) units to fill whole waves of
 // resident blocks (more segments only when they raise the filled fraction by > 2 %, each
 // one costs a merge pass), at least 4 tiles per segment, records within 2 GB
+// (rec_bytes: workspace bytes per query and segment; nqb query blocks over `slots` resident blocks)
+int fill_segments(int64_t nt, int64_t nq, int64_t nqb, int64_t slots, double rec_bytes) {
+    int best = 1;
+    double best_eff = 0.0;
+    for (int s = 1; s <= 32; s++) {
+        if (s > 1 && nt / s < 256) break;
+        if (s > 1 && (double)s * (double)nq * rec_bytes > 2e9) break;
+        const int64_t w = nqb * s;
+        const double eff = (double)w / (double)(((w + slots - 1) / slots) * slots);
+        if (eff > best_eff + 0.02) { best = s; best_eff = eff; }
+    }
+    return best;
+}
+
 int choose_direct_segments(const knn_ctx* c, int64_t nt, int64_t nq, int d, int k, int C, int elem) {
     int qb = 1, occ = 1;
     // (a metric has no rows form: its units are k_metric_tile's blocks for every shape)
@@ -375,16 +409,15 @@ int choose_direct_segments(const knn_ctx* c, int64_t nt, int64_t nq, int d, int 
         while (s > 1 && (double)s * (double)nq * 12.0 * k > 2e9) s--;
         return (int)s;
     }
-    int best = 1;
-    double best_eff = 0.0;
-    for (int s = 1; s <= 32; s++) {
-        if (s > 1 && nt / s < 256) break;
-        if (s > 1 && (double)s * (double)nq * 12.0 * k > 2e9) break;
-        const int64_t w = nqb * s;
-        const double eff = (double)w / (double)(((w + slots - 1) / slots) * slots);
-        if (eff > best_eff + 0.02) { best = s; best_eff = eff; }
-    }
-    return best;
+    return fill_segments(nt, nq, nqb, slots, 12.0 * k);
+}
+
+// k_radius_tile segments: the same rule from that kernel's own blocks per CU (64 queries a block;
+// 12 bytes of counts and bases per query and segment)
+int choose_radius_segments(const knn_ctx* c, int64_t nt, int64_t nq, int d, int C, int elem) {
+    int qb = 64, occ = 1;
+    if (knn_radius_units(c->metric, elem, d, C, &qb, &occ) != hipSuccess || occ < 1) occ = 1;
+    return fill_segments(nt, nq, (nq + qb - 1) / qb, (int64_t)occ * c->num_cus, 12.0);
 }
 
 // the direct form over the whole query set: k_direct_tile (+ k_merge_vote of its segments)
@@ -1047,7 +1080,7 @@ void knn_destroy(knn_ctx* c) {
     for (DBuf* b : {&c->tnorm, &c->tnp, &c->qnorm, &c->gthr, &c->cnt, &c->cand,
                     &c->fb_list, &c->ctrl, &c->scratch, &c->split_t, &c->split_q, &c->pad_t, &c->seg_rec, &c->arrive, &c->tmax, &c->tsmax, &c->qstat, &c->tblk, &c->tctrl, &c->cursor, &c->lshare, &c->parkcnt, &c->h_train, &c->h_labels, &c->h_test, &c->h_pred,
                     &c->h_dist, &c->h_idx, &c->sw_dist, &c->sw_idx, &c->sw_pred, &c->sw_qside, &c->sw_acc, &c->sw_scores,
-                    &c->rg_part, &c->rg_zero, &c->rg_targets})
+                    &c->rg_part, &c->rg_zero, &c->rg_targets, &c->rd_segcnt, &c->rd_base, &c->rd_cc, &c->rd_scores})
         b->release();
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; i++) {
@@ -1275,6 +1308,22 @@ knn_status train_device(knn_ctx* c, const knn_dataset* tr, hipStream_t st, knn_d
 }
 
 }  // namespace
+
+// knn_arff.cpp's radius calls have no host-buffer entry point to go through: the host train set
+// on the device by the host entry points' own upload path (train_device: cached under
+// KNN_OPT_CACHE_TRAIN), enqueued on the context's stream
+knn_status knn_ctx_train_device(knn_ctx* c, const knn_dataset* tr, knn_dataset* dtr) {
+    if (!c || !tr || !dtr) return KNN_EINVAL;
+    c->err.clear();
+    knn_status s;
+    if ((s = check_dataset(c, tr, "train", true)) != KNN_OK) return s;
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    if ((s = train_device(c, tr, c->stream, dtr)) != KNN_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        c->tcache.valid = false;
+    }
+    return s;
+}
 
 extern "C" {
 
@@ -1813,6 +1862,247 @@ knn_status knn_regress_sweep(knn_ctx* c, const knn_dataset* tr, const knn_datase
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------------
+// Radius neighbours (knn_amd.h "Radius neighbours"): k_radius_tile under the context's metric,
+// whatever its algo
+// ---------------------------------------------------------------------------------
+namespace {
+
+// what the count and the fill pass check of their datasets and threshold
+knn_status radius_check(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, float thr, int64_t self_base,
+                        bool need_labels) {
+    knn_status s;
+    if ((s = check_dataset(c, tr, "train", need_labels)) != KNN_OK) return s;
+    if ((s = check_dataset(c, te, "test", false)) != KNN_OK) return s;
+    if (tr->d != te->d) return fail(c, KNN_EINVAL, "feature count mismatch: train d=%d test d=%d", tr->d, te->d);
+    if (tr->dtype != te->dtype) return fail(c, KNN_EINVAL, "train and test dtypes differ");
+    if (!(thr >= 0.0f && thr < FLT_MAX)) return fail(c, KNN_EINVAL, "radius: the threshold must be in [0, FLT_MAX)");
+    if (tr->n > 0x7fffffffLL) return fail(c, KNN_EINVAL, "train row indices exceed 2^31-1");
+    const int es = elem_size(tr->dtype);
+    if (((int64_t)tr->ld * es) % 16 || ((int64_t)te->ld * es) % 16 || (((uintptr_t)tr->feat) & 15) ||
+        (((uintptr_t)te->feat) & 15))
+        return fail(c, KNN_EINVAL, "device rows must be 16-byte aligned (ld * element size %% 16 == 0)");
+    if (self_base >= 0 && self_base + te->n > tr->n)
+        return fail(c, KNN_EINVAL, "radius: self rows [%lld, %lld) outside the %lld train rows", (long long)self_base,
+                    (long long)(self_base + te->n), (long long)tr->n);
+    return KNN_OK;
+}
+
+knn_ctx::RadiusKey radius_key(const knn_ctx* c, const RadiusTileArgs& a) {
+    uint32_t tb;
+    std::memcpy(&tb, &a.thr, sizeof(tb));
+    return {a.train, a.test, a.nt, a.nq, a.self_base, a.d, a.ld_t, a.ld_q, a.elem, c->metric, a.nseg, tb, true};
+}
+
+RadiusTileArgs radius_args(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, float thr, int64_t self_base,
+                           int C) {
+    RadiusTileArgs a{};
+    a.train = tr->feat; a.labels = tr->labels; a.nt = tr->n; a.ld_t = tr->ld;
+    a.test = te->feat; a.ld_q = te->ld; a.nq = te->n;
+    a.d = tr->d; a.C = C; a.elem = tr->dtype;
+    a.thr = thr; a.self_base = self_base;
+    a.nseg = c->train_splits > 0 ? std::min(32, c->train_splits)
+                                 : choose_radius_segments(c, tr->n, te->n, tr->d, C, tr->dtype);
+    a.seg_len = (tr->n + a.nseg - 1) / a.nseg;
+    a.status = c->ctrl.as<int32_t>();
+    c->stats[2] = a.nseg;
+    return a;
+}
+
+knn_status weights_check(knn_ctx* c, const char* what, int32_t weights) {
+    if (weights != KNN_W_UNIFORM && weights != KNN_W_INV_DIST && weights != KNN_W_INV_SQDIST)
+        return fail(c, KNN_EINVAL, "%s: unknown weights=%d", what, weights);
+    if (weights == KNN_W_INV_SQDIST && c->metric != KNN_METRIC_SQEUCLIDEAN)
+        return fail(c, KNN_EINVAL, "%s: KNN_W_INV_SQDIST needs the squared Euclidean metric (metric=%d)", what,
+                    c->metric);
+    return KNN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+knn_status knn_radius_count_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, float thr, int32_t C,
+                                   int64_t self_base, int32_t outlier_label, const int32_t* d_query_labels,
+                                   int32_t* d_count, int32_t* d_class_counts, int32_t* d_pred, int64_t* d_correct,
+                                   int64_t* d_offsets, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    reset_stats(c);
+    const bool classes = d_class_counts || d_pred || d_correct;
+    knn_status s;
+    if ((s = radius_check(c, tr, te, thr, self_base, classes)) != KNN_OK) return s;
+    if (classes && (C < 1 || C > 16384)) return fail(c, KNN_EINVAL, "num_classes=%d outside [1, 16384]", C);
+    if (d_correct && !d_query_labels) return fail(c, KNN_EINVAL, "radius count: correct needs the query labels");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const int64_t nq = te->n;
+    if (d_correct) HIP_OR_FAIL(c, hipMemsetAsync(d_correct, 0, sizeof(int64_t), st));
+    if (nq == 0) {
+        if (d_offsets) HIP_OR_FAIL(c, hipMemsetAsync(d_offsets, 0, sizeof(int64_t), st));
+        HIP_OR_FAIL(c, hipStreamSynchronize(st));
+        return KNN_OK;
+    }
+    if (!d_count && !classes && !d_offsets)
+        return fail(c, KNN_EINVAL, "radius count: count, class_counts, pred, correct and offsets are all NULL");
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    RadiusTileArgs a = radius_args(c, tr, te, thr, self_base, classes ? C : 0);
+    const bool pass_votes = classes && knn_radius_pass_votes(C, a.nseg);
+    a.classes = classes ? 1 : 0;
+    a.class_counts = d_class_counts;
+    if (classes && !pass_votes) {
+        // the pass adds into the class counts (and k_radius_argmax reads them): the caller's, or workspace
+        if (!a.class_counts) {
+            HIP_OR_FAIL(c, c->rd_cc.ensure(sizeof(int32_t) * (size_t)nq * (size_t)C));
+            a.class_counts = c->rd_cc.as<int32_t>();
+        }
+        HIP_OR_FAIL(c, hipMemsetAsync(a.class_counts, 0, sizeof(int32_t) * (size_t)nq * (size_t)C, st));
+    } else if (pass_votes) {
+        a.pred = d_pred; a.qlabels = d_query_labels; a.outlier = outlier_label;
+        a.correct = reinterpret_cast<unsigned long long*>(d_correct);
+    }
+    // one segment: its counts are the counts
+    if (a.nseg == 1 && d_count) {
+        a.seg_count = d_count;
+    } else {
+        c->rd_key.valid = false;
+        HIP_OR_FAIL(c, c->rd_segcnt.ensure(sizeof(int32_t) * (size_t)nq * a.nseg));
+        a.seg_count = c->rd_segcnt.as<int32_t>();
+    }
+    stage_begin(c, st, "radius_count");
+    HIP_OR_FAIL(c, knn_launch_radius_tile(a, c->metric, false, st));
+    stage_end(c, st);
+    if (d_offsets || (a.nseg > 1 && d_count)) {
+        stage_begin(c, st, "radius_scan");
+        HIP_OR_FAIL(c, knn_launch_radius_scan(a.seg_count, a.nseg, nq, d_count, d_offsets, st));
+        stage_end(c, st);
+    }
+    if (classes && !pass_votes && (d_pred || d_correct)) {
+        stage_begin(c, st, "radius_argmax");
+        HIP_OR_FAIL(c, knn_launch_radius_argmax(a.class_counts, nq, C, outlier_label, d_query_labels, d_pred,
+                                                reinterpret_cast<unsigned long long*>(d_correct), st));
+        stage_end(c, st);
+    }
+    if ((s = finish_call(c, st)) == KNN_OK && a.seg_count == c->rd_segcnt.as<int32_t>()) c->rd_key = radius_key(c, a);
+    return s;
+}
+
+knn_status knn_radius_fill_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, float thr,
+                                  int64_t self_base, const int64_t* d_offsets, int32_t* d_idx, float* d_dist,
+                                  void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    reset_stats(c);
+    knn_status s;
+    if ((s = radius_check(c, tr, te, thr, self_base, false)) != KNN_OK) return s;
+    if (te->n == 0) return KNN_OK;
+    // (d_idx may be NULL only when the lists are empty, which the host cannot know: refuse)
+    if (!d_offsets || !d_idx) return fail(c, KNN_EINVAL, "radius fill: d_offsets / d_idx is NULL");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const int64_t nq = te->n;
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    RadiusTileArgs a = radius_args(c, tr, te, thr, self_base, 0);
+    a.offsets = d_offsets; a.idx = d_idx; a.dist = d_dist;
+    a.base = d_offsets;
+    if (a.nseg > 1) {
+        // where each train segment's part of a query's list starts: the segments' own counts --
+        // those the count call of this very pass left in workspace, else counted again (the count
+        // call may have run with other segments) -- prefixed from the caller's offsets
+        const bool counted = c->rd_key.same(radius_key(c, a));
+        c->rd_key.valid = false;
+        HIP_OR_FAIL(c, c->rd_segcnt.ensure(sizeof(int32_t) * (size_t)nq * a.nseg));
+        HIP_OR_FAIL(c, c->rd_base.ensure(sizeof(int64_t) * (size_t)nq * a.nseg));
+        a.seg_count = c->rd_segcnt.as<int32_t>();
+        if (!counted) {
+            stage_begin(c, st, "radius_count");
+            HIP_OR_FAIL(c, knn_launch_radius_tile(a, c->metric, false, st));
+            stage_end(c, st);
+        }
+        stage_begin(c, st, "radius_scan");
+        HIP_OR_FAIL(c, knn_launch_radius_bases(a.seg_count, a.nseg, nq, d_offsets, c->rd_base.as<int64_t>(), st));
+        stage_end(c, st);
+        a.base = c->rd_base.as<int64_t>();
+    }
+    stage_begin(c, st, "radius_fill");
+    HIP_OR_FAIL(c, knn_launch_radius_tile(a, c->metric, true, st));
+    stage_end(c, st);
+    if ((s = finish_call(c, st)) == KNN_OK && a.nseg > 1) c->rd_key = radius_key(c, a);
+    return s;
+}
+
+knn_status knn_radius_vote_device(knn_ctx* c, int64_t nq, int64_t n_train, const int64_t* d_offsets,
+                                  const int32_t* d_idx, const float* d_dist, const int32_t* d_train_labels, int32_t C,
+                                  int32_t weights, int32_t outlier_label, const int32_t* d_query_labels,
+                                  int32_t* d_pred, int64_t* d_correct, float* d_scores, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    reset_stats(c);
+    knn_status s;
+    if (nq < 0 || n_train < 0 || n_train > 0x7fffffffLL || C < 1 || C > 16384)
+        return fail(c, KNN_EINVAL, "radius vote: bad nq=%lld n_train=%lld C=%d", (long long)nq, (long long)n_train, C);
+    if ((s = weights_check(c, "radius vote", weights)) != KNN_OK) return s;
+    if (nq > 0 && !d_pred && !d_correct && !d_scores)
+        return fail(c, KNN_EINVAL, "radius vote: pred, correct and scores are all NULL");
+    if (d_correct && !d_query_labels) return fail(c, KNN_EINVAL, "radius vote: correct needs the query labels");
+    // (d_idx / d_dist may be NULL when every list is empty, which the host cannot know: refuse)
+    if (nq > 0 && (!d_offsets || !d_idx || !d_train_labels || (!d_dist && weights != KNN_W_UNIFORM)))
+        return fail(c, KNN_EINVAL, "radius vote: d_offsets / d_idx / d_dist / d_train_labels is NULL");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (d_correct) HIP_OR_FAIL(c, hipMemsetAsync(d_correct, 0, sizeof(int64_t), st));
+    if (nq == 0) {
+        HIP_OR_FAIL(c, hipStreamSynchronize(st));
+        return KNN_OK;
+    }
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    RadiusVoteArgs v{};
+    v.offsets = d_offsets; v.idx = d_idx; v.dist = d_dist; v.nq = nq; v.n_train = n_train;
+    v.labels = d_train_labels; v.C = C; v.weights = kernel_weights(c, weights); v.outlier = outlier_label;
+    v.qlabels = d_query_labels; v.pred = d_pred; v.correct = reinterpret_cast<unsigned long long*>(d_correct);
+    v.scores = d_scores;
+    if (!v.scores) {
+        HIP_OR_FAIL(c, c->rd_scores.ensure(sizeof(float) * (size_t)nq * (size_t)C));
+        v.scores = c->rd_scores.as<float>();
+    }
+    v.status = c->ctrl.as<int32_t>();
+    stage_begin(c, st, "radius_vote");
+    HIP_OR_FAIL(c, hipMemsetAsync(v.scores, 0, sizeof(float) * (size_t)nq * (size_t)C, st));
+    HIP_OR_FAIL(c, knn_launch_radius_vote(v, st));
+    stage_end(c, st);
+    return finish_call(c, st);
+}
+
+knn_status knn_radius_regress_device(knn_ctx* c, int64_t nq, int64_t n_train, const int64_t* d_offsets,
+                                     const int32_t* d_idx, const float* d_dist, const float* d_train_targets,
+                                     int32_t weights, float* d_pred, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    reset_stats(c);
+    knn_status s;
+    if (nq < 0 || n_train < 0 || n_train > 0x7fffffffLL)
+        return fail(c, KNN_EINVAL, "radius regression: bad nq=%lld n_train=%lld", (long long)nq, (long long)n_train);
+    if ((s = weights_check(c, "radius regression", weights)) != KNN_OK) return s;
+    if (nq == 0) return KNN_OK;
+    if (!d_pred) return fail(c, KNN_EINVAL, "radius regression: pred is NULL");
+    if (!d_offsets || !d_idx || !d_train_targets || (!d_dist && weights != KNN_W_UNIFORM))
+        return fail(c, KNN_EINVAL, "radius regression: d_offsets / d_idx / d_dist / d_train_targets is NULL");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    RadiusVoteArgs v{};
+    v.offsets = d_offsets; v.idx = d_idx; v.dist = d_dist; v.nq = nq; v.n_train = n_train;
+    v.weights = kernel_weights(c, weights);
+    v.targets = d_train_targets; v.pred_f = d_pred;
+    v.status = c->ctrl.as<int32_t>();
+    stage_begin(c, st, "radius_regress");
+    HIP_OR_FAIL(c, knn_launch_radius_regress(v, st));
+    stage_end(c, st);
+    return finish_call(c, st);
+}
+
+}  // extern "C"
+
 extern "C" {
 
 knn_status knn_predict(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t k, int32_t C,
@@ -1957,6 +2247,7 @@ int32_t knn_get_metric(const knn_ctx* c) { return c ? c->metric : KNN_METRIC_SQE
 knn_status knn_set_generation(knn_ctx* c, uint64_t generation) {
     if (!c) return KNN_EINVAL;
     c->generation = generation;
+    c->rd_key.valid = false;
     return KNN_OK;
 }
 

@@ -2,6 +2,7 @@
 //
 //   knn_cli train.arff test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]]
 //           [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress]
+//           [--radius=R [--outlier=L]]
 //
 // Same positional arguments as ./main (main.cpp:114-122; k parsed with strtol) plus the
 // optional worker count of ./multi-thread (multi-thread.cpp:135-143), here the number of
@@ -22,6 +23,12 @@
 // --regress: k-NN regression (KNN_regress_sweep / KNN_regress_sweep_loo): the last attribute is a
 // numeric target, read as a float.  Composes with --sweep[=loo], --weights= and --metric=; prints
 // the regressor's line per k (or the one line for K) with RMSE = sqrt(sse / n) and MAE = sae / n.
+// --radius=R [--outlier=L]: the radius classifier (KNN_radius / KNN_radius_loo): the vote of the
+// train rows within distance R, label L (default -1) where there is none.  K stays positional and
+// is not used.  Composes with --metric=, --weights= and --sweep=loo (leave-one-out); prints the
+// radius classifier's line with the accuracy (an outlier counts as wrong unless L is the row's
+// label) and the number of rows with no neighbour.  With --regress, with plain --sweep, or with an
+// R that is not a number >= 0, it prints a usage error and exits 1.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -40,11 +47,15 @@ static int run(int argc, char* argv[]) {
     int n = 0;
     bool sweep = false, loo = false, regress = false;
     int weights = 0;  // knn_weight
+    const char* radius_arg = nullptr;
+    int outlier = -1;
     for (int i = 0; i < argc; i++) {
         if (!std::strncmp(argv[i], "--shard=", 8)) setenv("KNN_AMD_SHARD", argv[i] + 8, 1);
         else if (!std::strcmp(argv[i], "--sweep")) sweep = true;
         else if (!std::strcmp(argv[i], "--sweep=loo")) sweep = loo = true;
         else if (!std::strcmp(argv[i], "--regress")) regress = true;
+        else if (!std::strncmp(argv[i], "--radius=", 9)) radius_arg = argv[i] + 9;
+        else if (!std::strncmp(argv[i], "--outlier=", 10)) outlier = (int)std::strtol(argv[i] + 10, NULL, 10);
         else if (!std::strcmp(argv[i], "--weights=uniform")) weights = 0;
         else if (!std::strcmp(argv[i], "--weights=distance")) weights = 1;
         else if (!std::strcmp(argv[i], "--weights=sqdist")) weights = 2;
@@ -62,11 +73,22 @@ static int run(int argc, char* argv[]) {
     }
     argc = n;
     if (argc != 4 && argc != 5) {
-        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress]"
+        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress] [--radius=R [--outlier=L]]"
                   << std::endl;
         std::exit(0);
     }
     int k = (int)std::strtol(argv[3], NULL, 10);
+    float radius = 0.0f;
+    if (radius_arg) {
+        char* end = nullptr;
+        radius = std::strtof(radius_arg, &end);
+        const bool number = end != radius_arg && *end == '\0' && radius >= 0.0f;  // (NaN fails >=)
+        if (!number || regress || (sweep && !loo)) {
+            std::cerr << "usage: --radius=R needs a number R >= 0 and does not combine with --regress or plain --sweep"
+                      << std::endl;
+            std::exit(1);
+        }
+    }
     if (argc == 5) setenv("KNN_AMD_DEVICES", argv[4], 1);
 
     ArffParser parserTrain(argv[1]);
@@ -76,6 +98,28 @@ static int run(int argc, char* argv[]) {
     knn_amd_init();
 
     struct timespec start, end;
+    if (radius_arg) {
+        long outliers = 0;
+        clock_gettime(CLOCK_MONOTONIC_RAW, &start);
+        int* pred = loo ? KNN_radius_loo(train, radius, weights, outlier, &outliers)
+                        : KNN_radius(train, test, radius, weights, outlier, &outliers);
+        clock_gettime(CLOCK_MONOTONIC_RAW, &end);
+        uint64_t diff = (1000000000L * (end.tv_sec - start.tv_sec) + end.tv_nsec - start.tv_nsec) / 1e6;
+        const long nq = test->num_instances();
+        const int last = test->num_attributes() - 1;
+        int ok = 0;  // (no confusion matrix: an outlier label is no class)
+        for (long q = 0; q < nq; q++) ok += pred[q] == (int)(int32)(*test->get_instance((int)q)->get(last));
+        printf("The radius-%g classifier for %lu test instances on %lu train instances required %llu ms CPU time. Accuracy was %.4f, %ld outliers\n",
+               (double)radius, (unsigned long)nq, (unsigned long)train->num_instances(), (long long unsigned int)diff,
+               ok / (float)nq, outliers);
+        if (const char* p = std::getenv("KNN_CLI_PRED_OUT")) {  // test hook: dump predictions
+            FILE* f = std::fopen(p, "w");
+            for (long q = 0; q < nq; q++) std::fprintf(f, "%d\n", pred[q]);
+            std::fclose(f);
+        }
+        std::free(pred);
+        return 0;
+    }
     if (regress) {
         std::vector<double> sse((size_t)(k > 0 ? k : 1)), sae((size_t)(k > 0 ? k : 1));
         clock_gettime(CLOCK_MONOTONIC_RAW, &start);

@@ -9,6 +9,8 @@
 #define KNN_STATUS_GEMM_UNSAFE 4   // a row norm is too large for the GEMM certificate
 #define KNN_STATUS_UNSORTED 8      // k_merge_vote: a source list read was not ascending by (dist, idx)
 #define KNN_STATUS_BAD_DIST 16     // k_vote_weighted: a caller-supplied distance is NaN or negative
+#define KNN_STATUS_BAD_OFFSETS 32  // radius fill / vote: the CSR offsets do not belong to this call
+#define KNN_STATUS_BAD_INDEX 64    // radius vote / regression: a list index is outside [0, n_train)
 
 // candidate-list capacity per query on the GEMM path (entries = 64 * CAPW)
 #define KNN_RESCORE_CAPW 32
@@ -223,6 +225,55 @@ enum { METRIC_SQEUCLIDEAN = 0, METRIC_MANHATTAN = 1, METRIC_CHEBYSHEV = 2 };
 hipError_t knn_metric_units(int metric, int k, int elem, int d, int C, int* queries_per_unit, int* units_per_cu);
 // fills dc / stride / vote_lds / n_qblocks and launches n_qblocks * nseg blocks
 hipError_t knn_launch_metric_tile(DirectTileArgs a, int metric, hipStream_t st);
+
+// Radius neighbours (knn_radius.hip; knn_amd.h "Radius neighbours").  k_radius_tile<M, E, FILL>:
+// k_metric_tile's block shape, tile staging and geometry (knn_direct_tile_geom) for all three
+// metrics, 8 queries per wave for every shape, the selection replaced by D <= thr.
+#define KNN_RADIUS_QW 8
+// class counts up to this many live in the count pass's per-wave LDS block [8][Cpad] (16 KiB a
+// block at the limit, beside the tiles); above it they are integer atomics on class_counts
+#define KNN_RADIUS_LDS_MAX_C 64
+struct RadiusTileArgs {
+    const void* train; const int32_t* labels; int64_t nt; int ld_t;
+    const void* test; int ld_q; int64_t nq;
+    int d; int C; int elem;
+    int64_t seg_len; int nseg; int n_qblocks;
+    int dc; int stride;        // set by the launcher (knn_direct_tile_geom)
+    float thr; int64_t self_base;  // self_base >= 0: train row self_base + q is no neighbour of q
+    // count pass.  classes != 0: a class output is asked (the launcher turns it into 1: LDS counts,
+    // 2: global atomics, and sets fuse_vote when the pass votes itself: LDS counts and nseg == 1)
+    int classes; int fuse_vote;
+    int32_t* seg_count;        // [nseg][nq]
+    int32_t* class_counts;     // [nq][C]; optional with fuse_vote, else needed and zeroed by the caller
+    int32_t* pred; const int32_t* qlabels; unsigned long long* correct; int32_t outlier;  // fuse_vote only
+    // fill pass: base [nseg][nq] where a (segment, query) part starts (offsets itself when nseg == 1)
+    const int64_t* base; const int64_t* offsets;
+    int32_t* idx; float* dist;  // dist optional
+    int32_t* status;
+};
+hipError_t knn_radius_units(int metric, int elem, int d, int C, int* queries_per_unit, int* units_per_cu);
+hipError_t knn_launch_radius_tile(RadiusTileArgs a, int metric, bool fill, hipStream_t st);
+// whether the count pass writes pred / correct itself (no k_radius_argmax behind it)
+bool knn_radius_pass_votes(int C, int nseg);
+// count (optional, may alias seg_count when nseg == 1) and the int64 exclusive scan offsets [nq + 1] (optional)
+hipError_t knn_launch_radius_scan(const int32_t* seg_count, int nseg, int64_t nq, int32_t* count, int64_t* offsets,
+                                  hipStream_t st);
+hipError_t knn_launch_radius_bases(const int32_t* seg_count, int nseg, int64_t nq, const int64_t* offsets, int64_t* base,
+                                   hipStream_t st);
+hipError_t knn_launch_radius_argmax(const int32_t* class_counts, int64_t nq, int C, int32_t outlier,
+                                    const int32_t* qlabels, int32_t* pred, unsigned long long* correct, hipStream_t st);
+// k_radius_vote / k_radius_regress on CSR lists: segment q is [offsets[q], offsets[q + 1]) of idx /
+// dist (dist optional for the uniform kind); weights: KNN_VOTE_W_*.  scores [nq][C] is needed and
+// zeroed by the caller; pred / correct (needs qlabels) are optional.  Regression: targets, pred_f.
+struct RadiusVoteArgs {
+    const int64_t* offsets; const int32_t* idx; const float* dist; int64_t nq; int64_t n_train;
+    const int32_t* labels; int C; int weights; int32_t outlier;
+    const int32_t* qlabels; int32_t* pred; unsigned long long* correct; float* scores;
+    const float* targets; float* pred_f;
+    int32_t* status;
+};
+hipError_t knn_launch_radius_vote(const RadiusVoteArgs& a, hipStream_t st);
+hipError_t knn_launch_radius_regress(const RadiusVoteArgs& a, hipStream_t st);
 
 struct GenerateArgs {
     void* out; int32_t* labels; int64_t row0; int64_t n; int d; int ld;
