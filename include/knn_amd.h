@@ -521,8 +521,11 @@ knn_status knn_regress_sweep(knn_ctx* ctx, const knn_dataset* train, const knn_d
  *              pred = (float)(N / Dn), the weights and the zero rule as above.  An empty segment
  *              predicts NaN (as sklearn does) and is not an error.  There are no error sums.
  *
- * knn_radius_count_device: one distance pass (k_radius_tile, whatever the context's algo: algo
- *   chooses among top-k forms only) under the context's metric, one synchronisation.  d_count,
+ * knn_radius_count_device: one distance pass under the context's metric, one synchronisation.  The
+ *   pass has two forms with the same results, bit for bit: the direct form (k_radius_tile, every
+ *   metric and shape) and an MFMA-filtered form (k_radius_gemm: squared Euclidean, d = 64, 128 or
+ *   256), which brackets each distance on the bf16 MFMA and computes the direct form's D only for
+ *   the rows whose bracket holds thr.  knn_radius_policy says which a call takes.  d_count,
  *   d_class_counts, d_pred, d_correct and d_offsets are each optional, but not all may be NULL;
  *   train->labels may be NULL when none of d_class_counts / d_pred / d_correct is asked.
  * knn_radius_fill_device: the pass again, storing the lists.  The caller read offsets[nq] from a
@@ -538,11 +541,21 @@ knn_status knn_regress_sweep(knn_ctx* ctx, const knn_dataset* train, const knn_d
  * nq == 0 returns KNN_OK.  With profile = 1 the stages are named "radius_count", "radius_fill",
  * "radius_vote" and "radius_regress" (and "radius_scan" for the scan of the counts, "radius_argmax"
  * for the vote of a pass that did not vote itself: several train segments, or more than 64 classes);
- * knn_last_stats()[2] is the number of train segments of the pass.
+ * knn_last_stats()[2] is the number of train segments of the pass.  The MFMA form adds the stages
+ * "radius_norms" and "radius_operands" in front (its train-side operands are kept across calls under
+ * KNN_OPT_CACHE_TRAIN[_DEVICE], knn_last_stats()[8]); knn_last_stats()[13] is the form that ran: 0
+ * direct, 1 MFMA, 2 direct because a row norm is NaN, inf or >= 2^125 (the bracket does not hold
+ * there; not an error), and [14], under profile = 2, the pairs the MFMA form evaluated exactly.
+ * knn_radius_vote_device / knn_radius_regress_device run no distance pass and leave [13] and [14] as
+ * the last count or fill call set them.
+ * knn_radius_policy: the form (0 direct, 1 MFMA) of a radius pass of n_query queries against n_train
+ *   rows on a context of that metric and algo; no GPU call.  Direct for Manhattan / Chebyshev, for
+ *   d outside {64, 128, 256}, an empty set, and under KNN_ALGO_DIRECT / KNN_ALGO_DIRECT_SCAN; MFMA
+ *   at any size under KNN_ALGO_GEMM_BF16; under KNN_ALGO_AUTO and the other GEMM algos MFMA from a floor of train
+ *   rows (>= 16384) and a floor of queries.  KNN_EINVAL for an unknown metric, dtype or algo.
  * Not here: host-buffer entry points, a multi-rank driver (counts and class counts add over train
  * shards, CSR lists concatenate by shard), several thresholds in one pass, distance-sorted
- * segments, regression error sums, and an MFMA-filtered pass for high d -- the radius pass is the
- * direct form at every shape.
+ * segments, regression error sums, and an int8 operand class for the MFMA form.
  */
 knn_status knn_radius_count_device(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test, float thr,
                                    int32_t num_classes, int64_t self_base, int32_t outlier_label,
@@ -551,6 +564,8 @@ knn_status knn_radius_count_device(knn_ctx* ctx, const knn_dataset* train, const
 knn_status knn_radius_fill_device(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test, float thr,
                                   int64_t self_base, const int64_t* d_offsets, int32_t* d_idx, float* d_dist,
                                   void* hip_stream);
+int32_t knn_radius_policy(int32_t metric, int32_t dtype, int32_t d, int64_t n_train, int64_t n_query, int32_t algo,
+                          int32_t* form);
 knn_status knn_radius_vote_device(knn_ctx* ctx, int64_t nq, int64_t n_train, const int64_t* d_offsets,
                                   const int32_t* d_idx, const float* d_dist, const int32_t* d_train_labels,
                                   int32_t num_classes, int32_t weights, int32_t outlier_label,
@@ -578,8 +593,9 @@ int32_t knn_stage_times(const knn_ctx* ctx, const char** names, float* ms, int32
  * multiplied: 1 int8 (KNN_ALGO_GEMM_I8's form; [3] stays 3, fp32 rows rounded once to a narrow
  * MFMA operand), 0 the data's own type or bf16, [12] the records the int8 filter parked in LDS
  * for its batched slow path in the last pass (counted under profile = 2 only, like [0]; 0
- * otherwise).  Returns the number written (<= 13); a caller that asks for 11 or 12 gets the
- * first 11 or 12 as before. */
+ * otherwise), [13] the form of a radius pass (0 direct, 1 MFMA, 2 direct because of unsafe norms),
+ * [14] the pairs a radius pass's MFMA form evaluated exactly (profile = 2 only).  Returns the number
+ * written (<= 15); a caller that asks for 11, 12 or 13 gets the first 11, 12 or 13 as before. */
 int32_t knn_last_stats(const knn_ctx* ctx, int64_t* out, int32_t n);
 
 /*

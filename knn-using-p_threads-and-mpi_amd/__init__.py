@@ -58,6 +58,9 @@ FILTER_OPERANDS = {-1: None, 0: "f32", 1: "bf16", 2: "bf16x3 split", 3: "bf16 ro
 # knn_last_stats()[11]: the element the filter multiplied.  Under "bf16 rounded" (fp32 rows rounded
 # once to a narrow MFMA operand, one product per fp32 product) it is "i8" when the int8 form ran
 FILTER_ELEMENTS = {0: "bf16", 1: "i8"}
+# knn_last_stats()[13]: the form of a radius pass ("unsafe": the direct form, because a row norm is
+# NaN, inf or >= 2^125 and the MFMA form's certificate does not hold)
+RADIUS_FORMS = {0: "direct", 1: "mfma", 2: "unsafe"}
 
 
 class KnnError(RuntimeError):
@@ -159,6 +162,7 @@ def load_library(path=LIB_PATH):
         "knn_predict_train_sharded": (I32, [P, P, DS, I64, DS, I32, I32, P, P, P, P]),
         "knn_shard_range": (I32, [I64, I32, I32, ctypes.POINTER(I64), ctypes.POINTER(I64)]),
         "knn_shard_policy": (I32, [I64, I64, I32, I32, I32, I64, ctypes.POINTER(I32)]),
+        "knn_radius_policy": (I32, [I32, I32, I32, I64, I64, I32, ctypes.POINTER(I32)]),
         "knn_exchange_layout": (I32, [I64, I32, I32, I32, P, P, P, P]),
         "knn_alloc_pinned": (I32, [ctypes.c_size_t, ctypes.POINTER(P)]),
         "knn_free_pinned": (None, [P]),
@@ -1029,15 +1033,16 @@ class Context:
         return out
 
     def stats(self):
-        v = (ctypes.c_int64 * 13)()
-        self.lib.knn_last_stats(self.h, v, 13)
+        v = (ctypes.c_int64 * 15)()
+        self.lib.knn_last_stats(self.h, v, 15)
         return {"candidates": v[0], "fallback_queries": v[1], "train_segments": v[2],
                 "filter_operands": FILTER_OPERANDS.get(v[3], v[3]), "rerun_split": bool(v[4]),
                 "fused_norm": bool(v[5]), "h2d_train_bytes": v[6], "h2d_query_bytes": v[7],
                 "train_operands_cached": bool(v[8]), "filter_mfma": v[9],
                 "queries_per_wave": v[10],
                 "filter_element": FILTER_ELEMENTS.get(v[11], v[11]) if v[3] in (1, 2, 3) else None,
-                "parked_passes": v[12]}
+                "parked_passes": v[12], "radius_form": RADIUS_FORMS.get(v[13], v[13]),
+                "radius_exact_pairs": v[14]}
 
 
 def comm_unique_id():
@@ -1080,6 +1085,18 @@ def shard_policy(n_train, n_query, d, dtype, world, hbm_bytes=0):
     if st != KNN_OK:
         raise KnnError(st, "knn_shard_policy")
     return "train" if p.value == 1 else "test"
+
+
+def radius_policy(metric, dtype, d, n_train, n_query, algo="auto"):
+    """knn_radius_policy: "direct" or "mfma", the form a radius pass of n_query queries against
+    n_train rows takes on a context of that metric and algo.  dtype: "f32" or "bf16"."""
+    lib = load_library()
+    f = ctypes.c_int32()
+    st = lib.knn_radius_policy(_metric_kind(metric), KNN_BF16 if dtype == "bf16" else KNN_F32, d, n_train, n_query,
+                               ALGOS[algo] if isinstance(algo, str) else int(algo), ctypes.byref(f))
+    if st != KNN_OK:
+        raise KnnError(st, "knn_radius_policy")
+    return RADIUS_FORMS[f.value]
 
 
 def exchange_layout(nq, k, world, rank):

@@ -6,7 +6,9 @@
 //   DIRECT:  k_exact_scan                                  (fused distance/top-k/vote)
 //   GEMM:    k_row_norms x2 -> k_gemm_filter -> k_rescore -> k_exact_scan(fallback list)
 //   a non-Euclidean metric (knn_set_metric): k_metric_tile (-> k_merge_vote), every shape
-//   radius neighbours (knn_radius_*): k_radius_tile (-> k_radius_scan / k_radius_argmax), every shape
+//   radius neighbours (knn_radius_*): k_radius_tile (-> k_radius_scan / k_radius_argmax), every shape;
+//     squared Euclidean at d = 64 / 128 / 256 above knn_radius_policy's floors: k_row_norms x2 ->
+//     k_tn_rows x2 -> k_radius_gemm (k_radius_tile behind it, gated on unsafe norms)
 // Train-sharded runs use the same pipeline per shard with the vote
 // replaced by a packed (dist, global idx, label) neighbour list, then k_merge_vote.
 #include <hip/hip_runtime.h>
@@ -133,12 +135,22 @@ struct knn_ctx {
     struct RadiusKey {
         const void *train, *test; int64_t nt, nq, self_base; int d, ld_t, ld_q, dtype, metric, nseg; uint32_t thr_bits;
         bool valid;
+        int64_t seg_len;  // (the two forms cut the same number of segments at different rows)
         bool same(const RadiusKey& o) const {
             return valid && o.valid && train == o.train && test == o.test && nt == o.nt && nq == o.nq &&
                    self_base == o.self_base && d == o.d && ld_t == o.ld_t && ld_q == o.ld_q && dtype == o.dtype &&
-                   metric == o.metric && nseg == o.nseg && thr_bits == o.thr_bits;
+                   metric == o.metric && nseg == o.nseg && thr_bits == o.thr_bits && seg_len == o.seg_len;
         }
     } rd_key{};
+    // the MFMA form of the radius pass (k_radius_gemm): train norms, tile statistics and their
+    // maxima, train tile blocks of 64 rows, the train norms' share of the status word; query norms,
+    // statistics and operand rows; the exact-evaluation counter (profile = 2).  Buffers and a cache
+    // key of their own (tprep's rule: the train view, the generation, the upload epoch) -- run_gemm
+    // trusts tnorm / tmax / tblk / tctrl across calls, so the radius pass never writes them.
+    DBuf rm_tnorm, rm_tmax, rm_tsmax, rm_tblk, rm_tctrl, rm_qnorm, rm_qstat, rm_qop, rm_exact;
+    struct { const void* feat; int64_t n; int d, ld, dtype; uint64_t gen, epoch; bool valid; }
+        rmprep{nullptr, 0, 0, 0, 0, 0, 0, false};
+    bool rm_counted = false;  // the last radius pass counted into rm_exact
     DBuf arrive;              // k_direct_rows' fused merge: per query group, segments finished
     bool arrive_clean = false;  // arrive is all zero (the last launch ran to completion)
     // host-buffer calls (knn_predict): cached train upload, two query slots streamed on a copy stream
@@ -159,13 +171,17 @@ struct knn_ctx {
     bool stage_open = false;  // the last stage_begin recorded an event (profile = 3 skips some)
     std::vector<float> stage_ms;
     std::vector<const char*> stage_names;
-    int64_t stats[13] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
+    int64_t stats[15] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
                                                       // operand type, rerun, fused, train / query H2D
                                                       // bytes, train-side filter operands from the cache,
                                                       // MFMA form, queries per wave, [11] the filter's
                                                       // operand element (0: the data's / bf16, 1: int8),
                                                       // [12] records parked by the last pass's filter
-                                                      // (profile = 2 only, like the candidates)
+                                                      // (profile = 2 only, like the candidates),
+                                                      // [13] the radius pass's form (0 direct, 1 MFMA,
+                                                      // 2 direct because of unsafe norms), [14] the
+                                                      // pairs its MFMA form evaluated exactly
+                                                      // (profile = 2 only)
     int64_t rerun_stats[3] = {0, -1, 0};    // segments, operand type, fused of AUTO's gated split re-run
     int num_cus = 256;
 };
@@ -1080,7 +1096,9 @@ void knn_destroy(knn_ctx* c) {
     for (DBuf* b : {&c->tnorm, &c->tnp, &c->qnorm, &c->gthr, &c->cnt, &c->cand,
                     &c->fb_list, &c->ctrl, &c->scratch, &c->split_t, &c->split_q, &c->pad_t, &c->seg_rec, &c->arrive, &c->tmax, &c->tsmax, &c->qstat, &c->tblk, &c->tctrl, &c->cursor, &c->lshare, &c->parkcnt, &c->h_train, &c->h_labels, &c->h_test, &c->h_pred,
                     &c->h_dist, &c->h_idx, &c->sw_dist, &c->sw_idx, &c->sw_pred, &c->sw_qside, &c->sw_acc, &c->sw_scores,
-                    &c->rg_part, &c->rg_zero, &c->rg_targets, &c->rd_segcnt, &c->rd_base, &c->rd_cc, &c->rd_scores})
+                    &c->rg_part, &c->rg_zero, &c->rg_targets, &c->rd_segcnt, &c->rd_base, &c->rd_cc, &c->rd_scores,
+                    &c->rm_tnorm, &c->rm_tmax, &c->rm_tsmax, &c->rm_tblk, &c->rm_tctrl, &c->rm_qnorm, &c->rm_qstat,
+                    &c->rm_qop, &c->rm_exact})
         b->release();
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; i++) {
@@ -1216,8 +1234,17 @@ knn_dataset offset_rows(const knn_dataset& x, int64_t r0, int64_t n) {
 
 void reset_stats(knn_ctx* c) {
     c->stages.clear();
-    for (int i = 0; i < 13; i++) c->stats[i] = 0;
+    for (int i = 0; i < 15; i++) c->stats[i] = 0;
     c->stats[3] = -1;
+}
+// the vote / regression on CSR lists run no distance pass: the form and the exact evaluations of the
+// radius pass that made the lists (stats[13], [14]) stay readable behind them, so a caller of
+// radius_predict_device or radius_regress_device still sees which form its passes took
+void reset_stats_keep_radius(knn_ctx* c) {
+    const int64_t form = c->stats[13], exact = c->stats[14];
+    reset_stats(c);
+    c->stats[13] = form;
+    c->stats[14] = exact;
 }
 
 // Shared pipeline of knn_predict_device / knn_shard_topk_device: the GEMM path runs the
@@ -1863,8 +1890,8 @@ knn_status knn_regress_sweep(knn_ctx* c, const knn_dataset* tr, const knn_datase
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------
-// Radius neighbours (knn_amd.h "Radius neighbours"): k_radius_tile under the context's metric,
-// whatever its algo
+// Radius neighbours (knn_amd.h "Radius neighbours"): k_radius_tile under the context's metric, or
+// k_radius_gemm where radius_policy says so
 // ---------------------------------------------------------------------------------
 namespace {
 
@@ -1891,22 +1918,138 @@ knn_status radius_check(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te
 knn_ctx::RadiusKey radius_key(const knn_ctx* c, const RadiusTileArgs& a) {
     uint32_t tb;
     std::memcpy(&tb, &a.thr, sizeof(tb));
-    return {a.train, a.test, a.nt, a.nq, a.self_base, a.d, a.ld_t, a.ld_q, a.elem, c->metric, a.nseg, tb, true};
+    return {a.train, a.test, a.nt, a.nq, a.self_base, a.d, a.ld_t, a.ld_q, a.elem, c->metric, a.nseg, tb, true,
+            a.seg_len};
 }
 
+// AUTO's floors of the MFMA form (knn_radius_policy): train rows and queries from which
+// k_radius_gemm, operand build included, measured not slower than k_radius_tile (DESIGN.md
+// "Radius neighbours", "Routing").  The row floor is top-k's (choose_algo).  Whole calls at 16,384
+// rows, d = 64, uncached: 256 queries 0.148 ms against the direct form's 0.135 (beyond its 4.1 %
+// spread, in every run), 512 queries 0.142 against 0.143, 1,024 0.143 against 0.170; d = 128 is
+// faster from 1 query on.  Below the floors both forms are bounded by their launches.
+static constexpr int64_t KNN_RADIUS_MFMA_MIN_ROWS = 16384;
+static constexpr int64_t KNN_RADIUS_MFMA_MIN_QUERIES = 512;
+
+// the form of a radius pass: 0 direct (k_radius_tile), 1 MFMA (k_radius_gemm)
+int radius_policy(int metric, int d, int64_t nt, int64_t nq, int algo) {
+    if (metric != KNN_METRIC_SQEUCLIDEAN || !knn_radius_gemm_supported(d)) return 0;
+    if (nt < 1 || nq < 1) return 0;  // (nothing to filter: no operands are built)
+    if (algo == KNN_ALGO_DIRECT || algo == KNN_ALGO_DIRECT_SCAN) return 0;
+    if (algo == KNN_ALGO_GEMM_BF16) return 1;
+    return nt >= KNN_RADIUS_MFMA_MIN_ROWS && nq >= KNN_RADIUS_MFMA_MIN_QUERIES ? 1 : 0;
+}
+
+// form = 1: k_radius_gemm's segments (multiples of 64 rows), which the direct form behind it
+// (unsafe norms) shares, so either leaves the same per-segment counts
 RadiusTileArgs radius_args(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, float thr, int64_t self_base,
-                           int C) {
+                           int C, int form = 0) {
     RadiusTileArgs a{};
     a.train = tr->feat; a.labels = tr->labels; a.nt = tr->n; a.ld_t = tr->ld;
     a.test = te->feat; a.ld_q = te->ld; a.nq = te->n;
     a.d = tr->d; a.C = C; a.elem = tr->dtype;
     a.thr = thr; a.self_base = self_base;
-    a.nseg = c->train_splits > 0 ? std::min(32, c->train_splits)
-                                 : choose_radius_segments(c, tr->n, te->n, tr->d, C, tr->dtype);
-    a.seg_len = (tr->n + a.nseg - 1) / a.nseg;
+    if (form) {
+        int qb = 32 * KNN_RADIUS_GEMM_NW, occ = 1;
+        if (knn_radius_gemm_units(tr->dtype, tr->d, &qb, &occ) != hipSuccess || occ < 1) occ = 1;
+        a.nseg = c->train_splits > 0
+                     ? std::min(32, c->train_splits)
+                     : fill_segments(tr->n, te->n, (te->n + qb - 1) / qb, (int64_t)occ * c->num_cus, 12.0);
+        a.seg_len = std::max<int64_t>(64, ((tr->n + a.nseg - 1) / a.nseg + 63) / 64 * 64);
+    } else {
+        a.nseg = c->train_splits > 0 ? std::min(32, c->train_splits)
+                                     : choose_radius_segments(c, tr->n, te->n, tr->d, C, tr->dtype);
+        a.seg_len = (tr->n + a.nseg - 1) / a.nseg;
+    }
     a.status = c->ctrl.as<int32_t>();
     c->stats[2] = a.nseg;
+    c->stats[13] = form;
     return a;
+}
+
+// The MFMA form's operands (the fused filter's, by its launchers, in buffers of this form's own)
+// and its arguments from the direct form's.  Train side: norms and tile statistics (k_row_norms),
+// their maxima, tile blocks of 64 rows over the 64-row grid -- kept across calls under
+// KNN_OPT_CACHE_TRAIN[_DEVICE] like run_gemm's (stats[8] says so).  The train norms' share of the
+// status word (KNN_STATUS_GEMM_UNSAFE) is kept with them and copied into this call's, which
+// reset_ctrl left zero; the query norms add theirs.
+knn_status radius_prep(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, const RadiusTileArgs& a,
+                       hipStream_t st, RadiusGemmArgs* g) {
+    const int64_t nt = tr->n, nq = te->n;
+    const int d = tr->d, dtype = tr->dtype;
+    const int64_t tiles = (nt + 63) / 64;
+    const bool own_train = tr->feat == c->h_train.p;
+    const bool may_cache = c->cache_train && (own_train || c->cache_train_device);
+    const uint64_t ep = own_train ? c->train_epoch : 0;
+    auto& rp = c->rmprep;
+    const bool hit = may_cache && rp.valid && rp.feat == tr->feat && rp.n == nt && rp.d == d && rp.ld == tr->ld &&
+                     rp.dtype == dtype && rp.gen == c->generation && rp.epoch == ep;
+    rp.valid = false;
+    HIP_OR_FAIL(c, c->rm_tctrl.ensure(4 * sizeof(int32_t)));
+    HIP_OR_FAIL(c, c->rm_tsmax.ensure(sizeof(float4)));
+    HIP_OR_FAIL(c, c->rm_qnorm.ensure(sizeof(float) * nq));
+    HIP_OR_FAIL(c, c->rm_qstat.ensure(sizeof(float2) * (nq + 1)));
+    HIP_OR_FAIL(c, c->rm_qop.ensure(sizeof(uint16_t) * (size_t)d * nq));
+    if (!hit) {
+        HIP_OR_FAIL(c, c->rm_tnorm.ensure(sizeof(float) * (tiles * 64)));
+        HIP_OR_FAIL(c, c->rm_tmax.ensure(sizeof(float4) * (tiles + 1)));
+        HIP_OR_FAIL(c, c->rm_tblk.ensure(knn_radius_gemm_tile_bytes(d) * (size_t)tiles));
+    }
+    stage_begin(c, st, "radius_norms");
+    if (!hit) {
+        HIP_OR_FAIL(c, hipMemsetAsync(c->rm_tctrl.p, 0, 4 * sizeof(int32_t), st));
+        HIP_OR_FAIL(c, knn_launch_row_norms(tr->feat, dtype, nt, tr->ld, d, c->rm_tnorm.as<float>(),
+                                            c->rm_tctrl.as<int32_t>(), nullptr, nullptr, 0.0f, st,
+                                            c->rm_tmax.as<float4>()));
+        HIP_OR_FAIL(c, knn_launch_tile_stat_max(c->rm_tmax.as<float4>(), tiles, c->rm_tsmax.as<float4>(), st));
+    }
+    HIP_OR_FAIL(c, hipMemcpyAsync(c->ctrl.p, c->rm_tctrl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    HIP_OR_FAIL(c, knn_launch_row_norms(te->feat, dtype, nq, te->ld, d, c->rm_qnorm.as<float>(), c->ctrl.as<int32_t>(),
+                                        nullptr, nullptr, 0.0f, st, nullptr, nullptr, c->rm_qstat.as<float2>(), -2.0f));
+    stage_end(c, st);
+    stage_begin(c, st, "radius_operands");
+    if (!hit)
+        HIP_OR_FAIL(c, knn_launch_tn_rows(tr->feat, dtype, tiles * 64, nt, tr->ld, d, c->rm_tnorm.as<float>(), 1.0f,
+                                          c->rm_tblk.p, c->rm_tmax.as<float4>(), 64, st));
+    HIP_OR_FAIL(c, knn_launch_tn_rows(te->feat, dtype, nq, nq, te->ld, d, nullptr, -2.0f, c->rm_qop.p, nullptr, 0, st));
+    stage_end(c, st);
+    c->stats[8] = hit ? 1 : 0;
+    if (may_cache) rp = {tr->feat, nt, d, tr->ld, dtype, c->generation, ep, true};
+
+    RadiusGemmArgs r{};
+    r.tblk = c->rm_tblk.p; r.qop = c->rm_qop.p; r.qnorm = c->rm_qnorm.as<float>();
+    r.qstat = c->rm_qstat.as<float2>(); r.tsmax = c->rm_tsmax.as<float4>();
+    r.train = a.train; r.labels = a.labels; r.nt = nt; r.ld_t = a.ld_t;
+    r.test = a.test; r.ld_q = a.ld_q; r.nq = nq;
+    r.d = d; r.C = a.C; r.elem = dtype;
+    r.seg_len = a.seg_len; r.nseg = a.nseg;
+    r.thr = a.thr; r.self_base = a.self_base;
+    certificate_fused(d, dtype == KNN_F32, &r.coef, &r.eta);
+    r.status = a.status;
+    c->rm_counted = false;
+    if (c->profile == 2) {
+        HIP_OR_FAIL(c, c->rm_exact.ensure(sizeof(unsigned long long)));
+        HIP_OR_FAIL(c, hipMemsetAsync(c->rm_exact.p, 0, sizeof(unsigned long long), st));
+        r.exact_cnt = c->rm_exact.as<unsigned long long>();
+        c->rm_counted = true;
+    }
+    *g = r;
+    return KNN_OK;
+}
+
+// a radius call's last step: the synchronisation, then which form ran (stats[13]) and, under
+// profile = 2, the pairs the MFMA form evaluated exactly (stats[14])
+knn_status radius_finish(knn_ctx* c, hipStream_t st, int form) {
+    const knn_status s = finish_call(c, st);
+    if (!form) return s;
+    if (s != KNN_OK && s != KNN_EINVAL && s != KNN_ERANGE) c->rmprep.valid = false;  // a HIP failure: the operands may be partial
+    if (s == KNN_OK || s == KNN_EINVAL) {
+        if (c->ctrl_host[0] & KNN_STATUS_GEMM_UNSAFE) c->stats[13] = 2;
+        unsigned long long n = 0;
+        if (c->rm_counted && hipMemcpy(&n, c->rm_exact.p, sizeof(n), hipMemcpyDeviceToHost) == hipSuccess)
+            c->stats[14] = (int64_t)n;
+    }
+    return s;
 }
 
 knn_status weights_check(knn_ctx* c, const char* what, int32_t weights) {
@@ -1946,8 +2089,16 @@ knn_status knn_radius_count_device(knn_ctx* c, const knn_dataset* tr, const knn_
     if (!d_count && !classes && !d_offsets)
         return fail(c, KNN_EINVAL, "radius count: count, class_counts, pred, correct and offsets are all NULL");
     HIP_OR_FAIL(c, reset_ctrl(c, st));
-    RadiusTileArgs a = radius_args(c, tr, te, thr, self_base, classes ? C : 0);
-    const bool pass_votes = classes && knn_radius_pass_votes(C, a.nseg);
+    const int form = radius_policy(c->metric, tr->d, tr->n, nq, c->algo);
+    RadiusTileArgs a = radius_args(c, tr, te, thr, self_base, classes ? C : 0, form);
+    RadiusGemmArgs g{};
+    if (form) {
+        if ((s = radius_prep(c, tr, te, a, st, &g)) != KNN_OK) return s;
+        a.gate = a.status;
+    }
+    // (the MFMA form never votes itself: its members add into class_counts, and so does the gated
+    // direct pass behind it, which is handed no pred / correct)
+    const bool pass_votes = !form && classes && knn_radius_pass_votes(C, a.nseg);
     a.classes = classes ? 1 : 0;
     a.class_counts = d_class_counts;
     if (classes && !pass_votes) {
@@ -1970,6 +2121,10 @@ knn_status knn_radius_count_device(knn_ctx* c, const knn_dataset* tr, const knn_
         a.seg_count = c->rd_segcnt.as<int32_t>();
     }
     stage_begin(c, st, "radius_count");
+    if (form) {
+        g.classes = a.classes; g.class_counts = a.class_counts; g.seg_count = a.seg_count;
+        HIP_OR_FAIL(c, knn_launch_radius_gemm(g, false, st));
+    }
     HIP_OR_FAIL(c, knn_launch_radius_tile(a, c->metric, false, st));
     stage_end(c, st);
     if (d_offsets || (a.nseg > 1 && d_count)) {
@@ -1983,7 +2138,8 @@ knn_status knn_radius_count_device(knn_ctx* c, const knn_dataset* tr, const knn_
                                                 reinterpret_cast<unsigned long long*>(d_correct), st));
         stage_end(c, st);
     }
-    if ((s = finish_call(c, st)) == KNN_OK && a.seg_count == c->rd_segcnt.as<int32_t>()) c->rd_key = radius_key(c, a);
+    if ((s = radius_finish(c, st, form)) == KNN_OK && a.seg_count == c->rd_segcnt.as<int32_t>())
+        c->rd_key = radius_key(c, a);
     return s;
 }
 
@@ -2002,7 +2158,13 @@ knn_status knn_radius_fill_device(knn_ctx* c, const knn_dataset* tr, const knn_d
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     const int64_t nq = te->n;
     HIP_OR_FAIL(c, reset_ctrl(c, st));
-    RadiusTileArgs a = radius_args(c, tr, te, thr, self_base, 0);
+    const int form = radius_policy(c->metric, tr->d, tr->n, nq, c->algo);
+    RadiusTileArgs a = radius_args(c, tr, te, thr, self_base, 0, form);
+    RadiusGemmArgs g{};
+    if (form) {
+        if ((s = radius_prep(c, tr, te, a, st, &g)) != KNN_OK) return s;
+        a.gate = a.status;
+    }
     a.offsets = d_offsets; a.idx = d_idx; a.dist = d_dist;
     a.base = d_offsets;
     if (a.nseg > 1) {
@@ -2016,6 +2178,10 @@ knn_status knn_radius_fill_device(knn_ctx* c, const knn_dataset* tr, const knn_d
         a.seg_count = c->rd_segcnt.as<int32_t>();
         if (!counted) {
             stage_begin(c, st, "radius_count");
+            if (form) {
+                g.seg_count = a.seg_count;
+                HIP_OR_FAIL(c, knn_launch_radius_gemm(g, false, st));
+            }
             HIP_OR_FAIL(c, knn_launch_radius_tile(a, c->metric, false, st));
             stage_end(c, st);
         }
@@ -2025,10 +2191,23 @@ knn_status knn_radius_fill_device(knn_ctx* c, const knn_dataset* tr, const knn_d
         a.base = c->rd_base.as<int64_t>();
     }
     stage_begin(c, st, "radius_fill");
+    if (form) {
+        g.base = a.base; g.offsets = a.offsets; g.idx = a.idx; g.dist = a.dist;
+        HIP_OR_FAIL(c, knn_launch_radius_gemm(g, true, st));
+    }
     HIP_OR_FAIL(c, knn_launch_radius_tile(a, c->metric, true, st));
     stage_end(c, st);
-    if ((s = finish_call(c, st)) == KNN_OK && a.nseg > 1) c->rd_key = radius_key(c, a);
+    if ((s = radius_finish(c, st, form)) == KNN_OK && a.nseg > 1) c->rd_key = radius_key(c, a);
     return s;
+}
+
+int32_t knn_radius_policy(int32_t metric, int32_t dtype, int32_t d, int64_t n_train, int64_t n_query, int32_t algo,
+                          int32_t* form) {
+    if (!form || d <= 0 || n_train < 0 || n_query < 0 || (dtype != KNN_F32 && dtype != KNN_BF16) ||
+        metric < KNN_METRIC_SQEUCLIDEAN || metric > KNN_METRIC_CHEBYSHEV || algo < KNN_ALGO_AUTO || algo > KNN_ALGO_GEMM_I8)
+        return KNN_EINVAL;
+    *form = radius_policy(metric, d, n_train, n_query, algo);
+    return KNN_OK;
 }
 
 knn_status knn_radius_vote_device(knn_ctx* c, int64_t nq, int64_t n_train, const int64_t* d_offsets,
@@ -2037,7 +2216,7 @@ knn_status knn_radius_vote_device(knn_ctx* c, int64_t nq, int64_t n_train, const
                                   int32_t* d_pred, int64_t* d_correct, float* d_scores, void* hip_stream) {
     if (!c) return KNN_EINVAL;
     c->err.clear();
-    reset_stats(c);
+    reset_stats_keep_radius(c);
     knn_status s;
     if (nq < 0 || n_train < 0 || n_train > 0x7fffffffLL || C < 1 || C > 16384)
         return fail(c, KNN_EINVAL, "radius vote: bad nq=%lld n_train=%lld C=%d", (long long)nq, (long long)n_train, C);
@@ -2078,7 +2257,7 @@ knn_status knn_radius_regress_device(knn_ctx* c, int64_t nq, int64_t n_train, co
                                      int32_t weights, float* d_pred, void* hip_stream) {
     if (!c) return KNN_EINVAL;
     c->err.clear();
-    reset_stats(c);
+    reset_stats_keep_radius(c);
     knn_status s;
     if (nq < 0 || n_train < 0 || n_train > 0x7fffffffLL)
         return fail(c, KNN_EINVAL, "radius regression: bad nq=%lld n_train=%lld", (long long)nq, (long long)n_train);
@@ -2278,7 +2457,7 @@ int32_t knn_stage_times(const knn_ctx* c, const char** names, float* ms, int32_t
 
 int32_t knn_last_stats(const knn_ctx* c, int64_t* out, int32_t n) {
     if (!c || !out) return 0;
-    int32_t m = std::min(n, 13);
+    int32_t m = std::min(n, 15);
     for (int32_t i = 0; i < m; i++) out[i] = c->stats[i];
     return m;
 }

@@ -250,6 +250,9 @@ struct RadiusTileArgs {
     const int64_t* base; const int64_t* offsets;
     int32_t* idx; float* dist;  // dist optional
     int32_t* status;
+    // optional: a status word; the kernel runs only when it says KNN_STATUS_GEMM_UNSAFE (the pass
+    // behind k_radius_gemm, which returns at once in that case)
+    const int32_t* gate;
 };
 hipError_t knn_radius_units(int metric, int elem, int d, int C, int* queries_per_unit, int* units_per_cu);
 hipError_t knn_launch_radius_tile(RadiusTileArgs a, int metric, bool fill, hipStream_t st);
@@ -274,6 +277,37 @@ struct RadiusVoteArgs {
 };
 hipError_t knn_launch_radius_vote(const RadiusVoteArgs& a, hipStream_t st);
 hipError_t knn_launch_radius_regress(const RadiusVoteArgs& a, hipStream_t st);
+
+// The MFMA-filtered form of the radius pass (knn_radius_gemm.hip): k_radius_gemm<RB, E, FILL>,
+// squared Euclidean, d in {64, 128, 256}.  8 waves a block, 32 queries a wave; train segments are
+// multiples of 64 rows.  tblk: the fused filter's train tile blocks of 64 rows (knn_launch_tn_rows
+// with bn = 64 over the 64-row grid), qop / qnorm / qstat its query operand, tsmax the maxima of the
+// tile statistics; train / test the caller's rows (the exact distance of the band reads them).
+#define KNN_RADIUS_GEMM_NW 8
+struct RadiusGemmArgs {
+    const void* tblk; const void* qop; const float* qnorm; const float2* qstat; const float4* tsmax;
+    const void* train; const int32_t* labels; int64_t nt; int ld_t;
+    const void* test; int ld_q; int64_t nq;
+    int d; int C; int elem;
+    int64_t seg_len; int nseg; int n_qblocks;  // n_qblocks: set by the launcher
+    float thr; int64_t self_base;
+    float coef; float eta;     // certificate_fused
+    // count pass.  classes != 0: members add into class_counts [nq][C] (needed then, zeroed by the
+    // caller) and every label of the train set is range-checked
+    int classes;
+    int32_t* seg_count;        // [nseg][nq]
+    int32_t* class_counts;
+    // fill pass: as RadiusTileArgs
+    const int64_t* base; const int64_t* offsets;
+    int32_t* idx; float* dist;
+    int32_t* status;           // a set KNN_STATUS_GEMM_UNSAFE bit skips the pass
+    unsigned long long* exact_cnt;  // optional (profile = 2): += the pairs given the exact evaluation
+};
+bool knn_radius_gemm_supported(int d);
+// bytes of one 64-row tile block of the train operand
+size_t knn_radius_gemm_tile_bytes(int d);
+hipError_t knn_radius_gemm_units(int elem, int d, int* queries_per_unit, int* units_per_cu);
+hipError_t knn_launch_radius_gemm(RadiusGemmArgs a, bool fill, hipStream_t st);
 
 struct GenerateArgs {
     void* out; int32_t* labels; int64_t row0; int64_t n; int d; int ld;

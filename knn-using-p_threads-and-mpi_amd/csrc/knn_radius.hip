@@ -84,6 +84,8 @@ __device__ __forceinline__ int lanes_below(u64 m) {
 template <int M, typename E, bool FILL>
 __global__ __launch_bounds__(64 * DT_NW, 4) void k_radius_tile(RadiusTileArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // (the pass behind k_radius_gemm: only when a norm made the certificate unsafe)
+    if (a.gate && !(*a.gate & KNN_STATUS_GEMM_UNSAFE)) return;
     constexpr int NT = 64 * DT_NW;
     constexpr int QW = KNN_RADIUS_QW;
     const int lane = lane_id();
