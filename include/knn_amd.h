@@ -594,9 +594,37 @@ int32_t knn_stage_times(const knn_ctx* ctx, const char** names, float* ms, int32
  * MFMA operand), 0 the data's own type or bf16, [12] the records the int8 filter parked in LDS
  * for its batched slow path in the last pass (counted under profile = 2 only, like [0]; 0
  * otherwise), [13] the form of a radius pass (0 direct, 1 MFMA, 2 direct because of unsafe norms),
- * [14] the pairs a radius pass's MFMA form evaluated exactly (profile = 2 only).  Returns the number
- * written (<= 15); a caller that asks for 11, 12 or 13 gets the first 11, 12 or 13 as before. */
+ * [14] the pairs a radius pass's MFMA form evaluated exactly (profile = 2 only), [15] the operand
+ * width of the last filter pass in features (the rows the MFMA multiplied: d padded with zero
+ * columns, knn_filter_policy's operand_width; 0 when no filter ran), [16] the chunks the filter
+ * cut an operand row into (1 for k_gemm_fused and k_gemm_filter, operand width / 128 for
+ * k_gemm_wide; 0 when no filter ran).
+ * Returns the number written (<= 17); a caller that asks for 11, 12, 13 or 15 gets the first 11,
+ * 12, 13 or 15 as before. */
 int32_t knn_last_stats(const knn_ctx* ctx, int64_t* out, int32_t n);
+
+/*
+ * knn_filter_policy: which form a top-k pass of n_query queries of d features against n_train
+ * rows of that dtype takes at this k on a context created with `algo` -- the default squared
+ * Euclidean metric, no train_splits, no test hooks; no GPU call.
+ *   *form: 0 direct (k_direct_tile / k_exact_scan: no filter), 1 fused (k_gemm_fused), 2 filter
+ *   (the non-fused k_gemm_filter), 3 wide (k_gemm_wide: the K-chunked filter of rows wider than
+ *   256 features).
+ *   *operand_width: the filter's operand row width in features (0 for the direct form).  The
+ *   bf16 operand classes -- fp32 rows rounded to bf16 (KNN_ALGO_GEMM_BF16, AUTO, and
+ *   KNN_ALGO_GEMM_I8 outside its own shapes) and bf16 data -- pad a row with zero columns: any
+ *   d <= 256 to the smallest of 64, 128, 256 that holds it, 256 < d <= 4096 to the next multiple
+ *   of 128 (the wide kernel's chunk).  The fp32 and split classes (KNN_ALGO_GEMM on fp32 data,
+ *   KNN_ALGO_GEMM_SPLIT) multiply the caller's rows and exist at d = 32, 64, 128 only; the int8
+ *   operands at d = 128 only.
+ * Rules: KNN_ALGO_DIRECT / KNN_ALGO_DIRECT_SCAN are direct; k > 128, k > n_train and d > 4096 are
+ * direct; a forced KNN_ALGO_GEMM_BF16 context (and KNN_ALGO_GEMM on bf16 data) takes the filter at
+ * any d <= 4096 and any size; KNN_ALGO_AUTO takes it from d >= 32 and n_train >= 8192 when the
+ * call has >= 10^9 pairs, and at d = 64, 128, 256 from n_train >= 16384 at any query count.
+ * KNN_EINVAL for an unknown dtype or algo, d < 1, k < 1, a negative count or a NULL pointer.
+ */
+int32_t knn_filter_policy(int32_t dtype, int32_t d, int32_t k, int64_t n_train, int64_t n_query, int32_t algo,
+                          int32_t* form, int32_t* operand_width);
 
 /*
  * Synthetic generator, device side: fills rows [row0, row0+n) of a

@@ -163,6 +163,7 @@ def load_library(path=LIB_PATH):
         "knn_shard_range": (I32, [I64, I32, I32, ctypes.POINTER(I64), ctypes.POINTER(I64)]),
         "knn_shard_policy": (I32, [I64, I64, I32, I32, I32, I64, ctypes.POINTER(I32)]),
         "knn_radius_policy": (I32, [I32, I32, I32, I64, I64, I32, ctypes.POINTER(I32)]),
+        "knn_filter_policy": (I32, [I32, I32, I32, I64, I64, I32, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
         "knn_exchange_layout": (I32, [I64, I32, I32, I32, P, P, P, P]),
         "knn_alloc_pinned": (I32, [ctypes.c_size_t, ctypes.POINTER(P)]),
         "knn_free_pinned": (None, [P]),
@@ -1033,8 +1034,8 @@ class Context:
         return out
 
     def stats(self):
-        v = (ctypes.c_int64 * 15)()
-        self.lib.knn_last_stats(self.h, v, 15)
+        v = (ctypes.c_int64 * 17)()
+        self.lib.knn_last_stats(self.h, v, 17)
         return {"candidates": v[0], "fallback_queries": v[1], "train_segments": v[2],
                 "filter_operands": FILTER_OPERANDS.get(v[3], v[3]), "rerun_split": bool(v[4]),
                 "fused_norm": bool(v[5]), "h2d_train_bytes": v[6], "h2d_query_bytes": v[7],
@@ -1042,7 +1043,7 @@ class Context:
                 "queries_per_wave": v[10],
                 "filter_element": FILTER_ELEMENTS.get(v[11], v[11]) if v[3] in (1, 2, 3) else None,
                 "parked_passes": v[12], "radius_form": RADIUS_FORMS.get(v[13], v[13]),
-                "radius_exact_pairs": v[14]}
+                "radius_exact_pairs": v[14], "filter_width": v[15], "filter_chunks": v[16]}
 
 
 def comm_unique_id():
@@ -1097,6 +1098,23 @@ def radius_policy(metric, dtype, d, n_train, n_query, algo="auto"):
     if st != KNN_OK:
         raise KnnError(st, "knn_radius_policy")
     return RADIUS_FORMS[f.value]
+
+
+FILTER_FORMS = {0: "direct", 1: "fused", 2: "filter", 3: "wide"}
+
+
+def filter_policy(dtype, d, k, n_train, n_query, algo="auto"):
+    """knn_filter_policy: (form, operand_width) of a top-k pass of n_query queries of d features
+    against n_train rows at this k on a context of that algo (squared Euclidean, no train_splits).
+    form: "direct", "fused" (k_gemm_fused), "filter" (k_gemm_filter) or "wide"; operand_width: the
+    filter's operand row width in features, 0 for "direct".  dtype: "f32" or "bf16"."""
+    lib = load_library()
+    f, w = ctypes.c_int32(), ctypes.c_int32()
+    st = lib.knn_filter_policy(KNN_BF16 if dtype == "bf16" else KNN_F32, d, k, n_train, n_query,
+                               ALGOS[algo] if isinstance(algo, str) else int(algo), ctypes.byref(f), ctypes.byref(w))
+    if st != KNN_OK:
+        raise KnnError(st, "knn_filter_policy")
+    return FILTER_FORMS[f.value], w.value
 
 
 def exchange_layout(nq, k, world, rank):

@@ -171,7 +171,7 @@ struct knn_ctx {
     bool stage_open = false;  // the last stage_begin recorded an event (profile = 3 skips some)
     std::vector<float> stage_ms;
     std::vector<const char*> stage_names;
-    int64_t stats[15] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
+    int64_t stats[17] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
                                                       // operand type, rerun, fused, train / query H2D
                                                       // bytes, train-side filter operands from the cache,
                                                       // MFMA form, queries per wave, [11] the filter's
@@ -182,7 +182,7 @@ struct knn_ctx {
                                                       // 2 direct because of unsafe norms), [14] the
                                                       // pairs its MFMA form evaluated exactly
                                                       // (profile = 2 only)
-    int64_t rerun_stats[3] = {0, -1, 0};    // segments, operand type, fused of AUTO's gated split re-run
+    int64_t rerun_stats[4] = {0, -1, 0, 0};  // segments, operand type, fused, operand width of AUTO's gated split re-run
     int num_cus = 256;
 };
 
@@ -285,24 +285,51 @@ int filter_elem(int algo, int dtype) {
 int filter_row_bytes(int felem, int d) {
     return felem == ELEM_SPLIT ? 4 * d : felem == ELEM_ROUND ? 2 * d : d * elem_size(felem);
 }
+// Operand width of the filter, separate from the caller's row width d.  The bf16 operand classes
+// (rounded fp32 rows, bf16 data) build their own operand rows (k_tn_rows, k_round_rows), so a row of
+// any d <= 256 is padded with zero columns to the next of the filter's tile widths 64 / 128 / 256,
+// and a row of 256 < d <= 4096 to the next multiple of 128, the chunk of the K-chunked kernel
+// (k_gemm_wide, knn_wide_width): zero products add nothing to the MFMA chain, and norms,
+// statistics, the rescore and the fallback keep the true rows.  The fp32 and split classes read
+// the caller's rows (or their [hi | lo] image) at their own width: they keep d.  0: no filter at
+// this width.
+int filter_width(int felem, int d) {
+    if (felem == ELEM_ROUND || felem == ELEM_BF16)
+        return d <= 64 ? 64 : d <= 128 ? 128 : d <= 256 ? 256 : knn_wide_width(d);
+    return d;
+}
+// whether operands of that class and width run k_gemm_wide (chunks of 128 features)
+bool is_wide(int felem, int dp) { return (felem == ELEM_ROUND || felem == ELEM_BF16) && dp > 256; }
+// AUTO's split re-run (predict_enqueue) builds [hi | lo] operands of its own, so it pads like the
+// rounded pass it follows; the split kernel has rows of 4 dp <= 512 bytes.  0: no split form.
+int split_rerun_width(int d, int k) {
+    const int dp = d <= 32 ? 32 : d <= 64 ? 64 : d <= 128 ? 128 : 0;
+    return dp > 0 && knn_gemm_filter_lds(ELEM_SPLIT, 4 * dp, k) <= 160 * 1024 ? dp : 0;
+}
 bool is_gemm(int algo) {
     return algo == KNN_ALGO_GEMM || algo == KNN_ALGO_GEMM_SPLIT || algo == KNN_ALGO_GEMM_BF16 ||
            algo == KNN_ALGO_GEMM_I8;
 }
 
-int choose_algo(const knn_ctx* c, int64_t nt, int64_t nq, int d, int k, int dtype) {
+// ctx_algo / metric: the context's (knn_filter_policy asks without one)
+int choose_algo(int ctx_algo, int metric, int64_t nt, int64_t nq, int d, int k, int dtype) {
     // a non-Euclidean metric has the direct form only (k_metric_tile), whatever the shape
-    if (c->metric != KNN_METRIC_SQEUCLIDEAN) return KNN_ALGO_DIRECT;
-    if (c->algo == KNN_ALGO_DIRECT || c->algo == KNN_ALGO_DIRECT_SCAN) return c->algo;
-    // the LDS-DMA filter stages whole rows: a row must be one of its tile widths
-    // (128, 256 or 512 bytes: fp32 d = 32/64/128 (fp32 or split), bf16 d = 64/128/256)
+    if (metric != KNN_METRIC_SQEUCLIDEAN) return KNN_ALGO_DIRECT;
+    if (ctx_algo == KNN_ALGO_DIRECT || ctx_algo == KNN_ALGO_DIRECT_SCAN) return ctx_algo;
+    // the LDS-DMA filter stages whole operand rows: a row must be one of its tile widths
+    // (128, 256 or 512 bytes: fp32 d = 32/64/128 (fp32 or split); the bf16 operands, which the
+    // library builds itself, any d <= 256 padded to 64/128/256 and any d <= 4096 in chunks of
+    // 128 -- filter_width)
     auto gemm_ok = [&](int algo) {
-        const int fe = filter_elem(algo, dtype), rb = filter_row_bytes(fe, d);
+        const int fe = filter_elem(algo, dtype), dp = filter_width(fe, d);
+        if (dp <= 0) return false;
+        if (is_wide(fe, dp)) return k <= 128 && k <= nt && knn_wide_plan(k).lds <= 160 * 1024;  // k_gemm_wide
+        const int rb = filter_row_bytes(fe, dp);
         return knn_gemm_filter_supported(fe, rb) && k <= 128 && k <= nt &&
                knn_gemm_filter_lds(fe, rb, k) <= 160 * 1024;
     };
-    if (is_gemm(c->algo))
-        return gemm_ok(c->algo) ? c->algo : KNN_ALGO_DIRECT;
+    if (is_gemm(ctx_algo))
+        return gemm_ok(ctx_algo) ? ctx_algo : KNN_ALGO_DIRECT;
     // AUTO: the direct form wins at low d (3 VALU ops per dim, no rescore) and on small jobs;
     // above that the rounded bf16 filter (one MFMA per 16 features), re-run as split when
     // its wider certificate overflows the candidate lists (predict_core).  For the fused
@@ -312,7 +339,11 @@ int choose_algo(const knn_ctx* c, int64_t nt, int64_t nq, int d, int k, int dtyp
     // 1000 1.38 -> 0.35, 1M x 500 8.72 -> 1.07; d = 64, k = 32: 50k x 200 0.61 -> 0.37, 100k x
     // 2000 2.51 -> 0.49; 20k x 150 0.29 either way; at 10k rows the two are equal (0.21-0.26)
     // and the direct form wins at d = 64, k = 32 (0.25 vs 0.31; profiles/r06_studies/r06au).
-    // Other widths keep the 10^9-pair rule.
+    // Other widths keep the 10^9-pair rule: a padded row pays its operand width's MFMA work and
+    // the direct form the true d's, so the rule that holds at 64/128/256 on 10^9 pairs is kept for
+    // the widths between them and beyond (DESIGN.md "Any row width").  At the rule's edge, 32,768 x
+    // 32,768, k = 10, same box, direct -> filter: d = 96 (padded to 128) 10.09 -> 0.93 ms, d = 768
+    // (k_gemm_wide) 125.2 -> 4.63 ms (profiles/wide_rows.json): no floor raised for either class.
     const double pairs = (double)nt * (double)nq;
     if (d >= 32 && nt >= 8192 && (pairs >= 1e9 || (knn_fused_supported(d) && nt >= 16384))) {
         // fp32 rows at d = 128, k <= 32: the int8 operand class (half
@@ -325,6 +356,9 @@ int choose_algo(const knn_ctx* c, int64_t nt, int64_t nq, int d, int k, int dtyp
         if (gemm_ok(KNN_ALGO_GEMM)) return KNN_ALGO_GEMM;
     }
     return KNN_ALGO_DIRECT;
+}
+int choose_algo(const knn_ctx* c, int64_t nt, int64_t nq, int d, int k, int dtype) {
+    return choose_algo(c->algo, c->metric, nt, nq, d, k, dtype);
 }
 
 // per-stage times of the drained stream (profile mode)
@@ -602,7 +636,7 @@ int max_splits(int64_t nt, int k, int cap, int smax = 8) {
 }
 
 int choose_splits(const knn_ctx* c, int64_t n_qtiles, int64_t nt, int dtype, int rb, int k, int cap,
-                  bool fused = false, int d = 0, const FilterPlan* fplan = nullptr, int smax = 8) {
+                  bool fused = false, int d = 0, const FilterPlan* fplan = nullptr, int smax = 8, bool wide = false) {
     if (c->train_splits > 0) return std::min(8, c->train_splits);
     // More segments shrink the partial last wave of blocks (measured on config A:
     // S=3 224 ms, S=5 217 ms, S=8 216 ms), but each segment must fit its rows in its
@@ -611,7 +645,8 @@ int choose_splits(const knn_ctx* c, int64_t n_qtiles, int64_t nt, int dtype, int
     // tile; the slice gets a 1.5x margin.  Overflowing queries still finish exactly,
     // on the slow full-scan fallback.
     int occ = 1;
-    const hipError_t oe = fused ? knn_fused_occupancy(d, *fplan, &occ) : knn_gemm_filter_occupancy(dtype, rb, k, &occ);
+    const hipError_t oe = fused ? knn_fused_occupancy(d, *fplan, &occ)
+                        : wide ? knn_wide_occupancy(k, &occ) : knn_gemm_filter_occupancy(dtype, rb, k, &occ);
     if (oe != hipSuccess || occ < 1) occ = 1;
     const int64_t slots = (int64_t)occ * c->num_cus;
     int best = 1;
@@ -642,7 +677,12 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     const int d = tr->d;
     const int dtype = tr->dtype;
     const int felem = filter_elem(algo, dtype);  // the filter's operand type
-    const int rb = filter_row_bytes(felem, d);
+    // the operand rows' width (filter_width: d padded with zero columns for the bf16 operands).
+    // Norms, statistics, the rescore and the fallback below keep the caller's rows and d.
+    const int dp = felem == ELEM_SPLIT && gate ? split_rerun_width(d, k) : filter_width(felem, d);
+    const bool wide = is_wide(felem, dp);  // k_gemm_wide: rows in chunks of 128 features
+    if (dp < d) return fail(c, KNN_EINVAL, "no filter operands at d=%d", d);  // (choose_algo never sends one)
+    const int rb = filter_row_bytes(felem, dp);
     const int kelem = felem == ELEM_ROUND ? ELEM_BF16 : felem;  // ELEM_ROUND runs the bf16 kernel
     // Small query sets (round 6): when the base list's pieces would leave CUs idle (256-query
     // tiles x max_splits pieces under 80 % of the CUs -- a 3,125-query call on A's rows ran 13
@@ -663,8 +703,11 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
                      : (size_t)nq * per_q * 2 <= ws_lim ? 2 : 1;
     const int cap = 64 * KNN_RESCORE_CAPW * capmul;
     const int smax = capmul == 8 ? 32 : capmul > 1 ? 16 : 8;
-    HIP_OR_FAIL(c, c->tnorm.ensure(sizeof(float) * (nt + 64)));
-    HIP_OR_FAIL(c, c->tnp.ensure(sizeof(float) * (nt + 64)));
+    // (k_row_norms writes +inf into rows [nt, nt + 64); the wide filter's 256-row groups read up to
+    // 255 rows past nt: the rest of that range is filled below)
+    const int wgr = knn_wide_group_rows();
+    HIP_OR_FAIL(c, c->tnorm.ensure(sizeof(float) * (nt + 64 + wgr)));
+    HIP_OR_FAIL(c, c->tnp.ensure(sizeof(float) * (nt + 64 + wgr)));
     HIP_OR_FAIL(c, c->qnorm.ensure(sizeof(float) * nq));
     HIP_OR_FAIL(c, c->gthr.ensure(sizeof(uint32_t) * nq));
     HIP_OR_FAIL(c, c->cnt.ensure(sizeof(int32_t) * nq * 64));  // [subs * nseg][nq], subs * nseg <= 64
@@ -749,16 +792,18 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     }
     const bool i8 = i8s > 0.0f;
     const FilterPlan fplan = i8 ? iplan
-                           : knn_fused_supported(d) ? knn_fused_plan(d, k, nq, c->num_cus, c->fforce, max_splits(nt, k, 64 * KNN_RESCORE_CAPW)) : FilterPlan{};
-    const bool fused = (felem == ELEM_ROUND || felem == ELEM_BF16) && knn_fused_supported(d) && fplan.nw > 0;
+                           : knn_fused_supported(dp) ? knn_fused_plan(dp, k, nq, c->num_cus, c->fforce, max_splits(nt, k, 64 * KNN_RESCORE_CAPW)) : FilterPlan{};
+    const bool fused = (felem == ELEM_ROUND || felem == ELEM_BF16) && knn_fused_supported(dp) && fplan.nw > 0;
+    // (the certificates take dp: their coefficient grows with the width, so the one for dp >= d
+    // holds for a chain whose columns past d add exact zeros)
     float coef, eta;
     if (fused) {
-        certificate_fused(d, felem == ELEM_ROUND, &coef, &eta);
+        certificate_fused(dp, felem == ELEM_ROUND, &coef, &eta);
         HIP_OR_FAIL(c, c->tmax.ensure(sizeof(float4) * ((nt + 63) / 64 + 1)));
         HIP_OR_FAIL(c, c->tsmax.ensure(sizeof(float4)));
         HIP_OR_FAIL(c, c->qstat.ensure(sizeof(float2) * (nq + 1)));
     } else {
-        certificate(d, felem, &coef, &eta);
+        certificate(dp, felem, &coef, &eta);
     }
     // train-side operands of the fused filter: norms + tile statistics (k_row_norms) and the
     // tile blocks (k_tn_rows), reused from an earlier call on the same train view when the
@@ -773,6 +818,11 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     const bool prep_hit = fused && !gate && may_cache && tp.valid && tp.feat == tr->feat && tp.n == nt &&
                           tp.d == d && tp.ld == tr->ld && tp.dtype == dtype && tp.bn == bn_f && tp.i8 == (i8 ? 1 : 0) &&
                           tp.gen == c->generation && tp.epoch == (own_train ? c->train_epoch : 0);
+    // (A non-fused or wide pass leaves tprep alone although it overwrites tnorm / tnp: a later hit
+    // reads the tile blocks (tblk, the norms in their headers), tctrl and tsmax only -- the fused
+    // kernel takes no norm from tnorm / tnp, and k_tn_rows reads tnorm / tmax only on a miss -- and
+    // none of those three is written outside the fused branch and the int8 guard, which clears
+    // tprep itself.)
     if (fused && !gate) {
         HIP_OR_FAIL(c, c->tctrl.ensure(4 * sizeof(int32_t)));
         tp.valid = false;  // (set again below once this call's train pass is enqueued)
@@ -802,6 +852,10 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     HIP_OR_FAIL(c, knn_launch_row_norms(te->feat, dtype, nq, te->ld, d, c->qnorm.as<float>(),
                                         c->ctrl.as<int32_t>(), nullptr, nullptr, 0.0f, st, nullptr, gate,
                                         fused ? c->qstat.as<float2>() : nullptr, -2.0f, i8s));
+    if (wide) {
+        HIP_OR_FAIL(c, knn_launch_fill_u32(c->tnorm.as<uint32_t>() + nt + 64, wgr, 0x7f800000u, gate, st));  // +inf
+        HIP_OR_FAIL(c, knn_launch_fill_u32(c->tnp.as<uint32_t>() + nt + 64, wgr, 0x7f800000u, gate, st));
+    }
     stage_end(c, st);
     // (a norm >= 2^125 sets GEMM_UNSAFE in the status word: the filter then skips and the
     // rescore sends every query to the exact fallback scan -- decided on the device)
@@ -810,8 +864,9 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     stage_end(c, st);
 
     // filter operands: the rows themselves, or their bf16 [hi | lo] split (2d elements per row);
-    // train operand rows always cover the 64-row tile grid (ntp rows)
-    const int64_t ntp = (nt + 63) / 64 * 64;
+    // train operand rows always cover the 64-row tile grid (ntp rows; the wide filter's grid of
+    // 256-row groups)
+    const int64_t ntp = wide ? (nt + wgr - 1) / wgr * wgr : (nt + 63) / 64 * 64;
     const void* ftrain = tr->feat;
     const void* ftest = te->feat;
     int fld_t = tr->ld, fld_q = te->ld;
@@ -823,8 +878,8 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
         const int64_t ntf = ntp + 256;  // (256 pad rows: a piece's scan may run up to 224 rows past
                                         //  its own -- seven 32-row tiles of an octet, k_gemm_fused)
         // (int8 class: rows of d bytes, the header's bn words the integer norm terms, k_i8_rows)
-        const size_t tb = (size_t)bn_f * (i8 ? 1 : 2) * d + 4 * bn_f + 16;
-        HIP_OR_FAIL(c, c->split_q.ensure(sizeof(uint16_t) * (size_t)d * nq));
+        const size_t tb = (size_t)bn_f * (i8 ? 1 : 2) * dp + 4 * bn_f + 16;
+        HIP_OR_FAIL(c, c->split_q.ensure(sizeof(uint16_t) * (size_t)dp * nq));
         stage_begin(c, st, "aug");
         if (!prep_hit) {
             HIP_OR_FAIL(c, c->tblk.ensure(tb * (size_t)(ntf / bn_f)));
@@ -832,41 +887,54 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
                 HIP_OR_FAIL(c, knn_launch_i8_rows((const float*)tr->feat, ntf, nt, tr->ld, d, c->tnorm.as<float>(), i8s,
                                                   c->tblk.p, c->tmax.as<float4>(), bn_f, st));
             else
-                HIP_OR_FAIL(c, knn_launch_tn_rows(tr->feat, dtype, ntf, nt, tr->ld, d, c->tnorm.as<float>(), 1.0f,
+                HIP_OR_FAIL(c, knn_launch_tn_rows(tr->feat, dtype, ntf, nt, tr->ld, d, dp, c->tnorm.as<float>(), 1.0f,
                                                   c->tblk.p, c->tmax.as<float4>(), bn_f, st, nullptr));
         }
         if (i8)
             HIP_OR_FAIL(c, knn_launch_i8_rows((const float*)te->feat, nq, nq, te->ld, d, nullptr, i8s, c->split_q.p,
                                               nullptr, 0, st));
         else
-            HIP_OR_FAIL(c, knn_launch_tn_rows(te->feat, dtype, nq, nq, te->ld, d, nullptr, -2.0f, c->split_q.p, nullptr,
-                                              0, st, nullptr));
+            HIP_OR_FAIL(c, knn_launch_tn_rows(te->feat, dtype, nq, nq, te->ld, d, dp, nullptr, -2.0f, c->split_q.p,
+                                              nullptr, 0, st, nullptr));
         stage_end(c, st);
         ftrain = c->tblk.p; ftest = c->split_q.p;
-        fld_t = fld_q = d;
+        fld_t = fld_q = dp;
         c->stats[8] = prep_hit ? 1 : 0;
         if (may_cache)
             tp = {tr->feat, nt, d, tr->ld, dtype, bn_f, c->generation, own_train ? c->train_epoch : 0, true, i8 ? 1 : 0};
     } else if (felem == ELEM_SPLIT) {
-        HIP_OR_FAIL(c, c->split_t.ensure(sizeof(uint16_t) * 2 * d * ntp));
-        HIP_OR_FAIL(c, c->split_q.ensure(sizeof(uint16_t) * 2 * d * nq));
+        HIP_OR_FAIL(c, c->split_t.ensure(sizeof(uint16_t) * 2 * (size_t)dp * ntp));
+        HIP_OR_FAIL(c, c->split_q.ensure(sizeof(uint16_t) * 2 * (size_t)dp * nq));
         stage_begin(c, st, gate ? "split_rerun" : "split");
-        HIP_OR_FAIL(c, hipMemsetAsync(c->split_t.as<uint16_t>() + 2 * d * nt, 0, sizeof(uint16_t) * 2 * d * (ntp - nt), st));
-        HIP_OR_FAIL(c, knn_launch_split_rows((const float*)tr->feat, nt, tr->ld, d, c->split_t.as<uint16_t>(), st, gate));
-        HIP_OR_FAIL(c, knn_launch_split_rows((const float*)te->feat, nq, te->ld, d, c->split_q.as<uint16_t>(), st, gate));
+        HIP_OR_FAIL(c, hipMemsetAsync(c->split_t.as<uint16_t>() + 2 * (size_t)dp * nt, 0, sizeof(uint16_t) * 2 * (size_t)dp * (ntp - nt), st));
+        HIP_OR_FAIL(c, knn_launch_split_rows((const float*)tr->feat, nt, tr->ld, d, dp, c->split_t.as<uint16_t>(), st, gate));
+        HIP_OR_FAIL(c, knn_launch_split_rows((const float*)te->feat, nq, te->ld, d, dp, c->split_q.as<uint16_t>(), st, gate));
         stage_end(c, st);
         ftrain = c->split_t.p; ftest = c->split_q.p;
-        fld_t = fld_q = 2 * d;
+        fld_t = fld_q = 2 * dp;
     } else if (felem == ELEM_ROUND) {
-        HIP_OR_FAIL(c, c->split_t.ensure(sizeof(uint16_t) * d * ntp));
-        HIP_OR_FAIL(c, c->split_q.ensure(sizeof(uint16_t) * d * nq));
+        HIP_OR_FAIL(c, c->split_t.ensure(sizeof(uint16_t) * (size_t)dp * ntp));
+        HIP_OR_FAIL(c, c->split_q.ensure(sizeof(uint16_t) * (size_t)dp * nq));
         stage_begin(c, st, gate ? "round_rerun" : "round");
-        HIP_OR_FAIL(c, hipMemsetAsync(c->split_t.as<uint16_t>() + d * nt, 0, sizeof(uint16_t) * d * (ntp - nt), st));
-        HIP_OR_FAIL(c, knn_launch_round_rows((const float*)tr->feat, nt, tr->ld, d, c->split_t.as<uint16_t>(), st, gate));
-        HIP_OR_FAIL(c, knn_launch_round_rows((const float*)te->feat, nq, te->ld, d, c->split_q.as<uint16_t>(), st, gate));
+        HIP_OR_FAIL(c, hipMemsetAsync(c->split_t.as<uint16_t>() + (size_t)dp * nt, 0, sizeof(uint16_t) * (size_t)dp * (ntp - nt), st));
+        HIP_OR_FAIL(c, knn_launch_round_rows((const float*)tr->feat, nt, tr->ld, d, dp, c->split_t.as<uint16_t>(), st, gate));
+        HIP_OR_FAIL(c, knn_launch_round_rows((const float*)te->feat, nq, te->ld, d, dp, c->split_q.as<uint16_t>(), st, gate));
         stage_end(c, st);
         ftrain = c->split_t.p; ftest = c->split_q.p;
-        fld_t = fld_q = d;
+        fld_t = fld_q = dp;
+    } else if (felem == ELEM_BF16 && (dp != d || wide)) {
+        // bf16 data narrower than its operand width with no fused kernel at this k, or wide rows
+        // (packed operands on the grid of row groups): [dp] rows with zero columns past d
+        // (k_tn_rows' query form; scale 1 keeps the bits), the train rows on the tile grid with
+        // zero pad rows
+        HIP_OR_FAIL(c, c->split_t.ensure(sizeof(uint16_t) * (size_t)dp * ntp));
+        HIP_OR_FAIL(c, c->split_q.ensure(sizeof(uint16_t) * (size_t)dp * nq));
+        stage_begin(c, st, gate ? "round_rerun" : "round");
+        HIP_OR_FAIL(c, knn_launch_tn_rows(tr->feat, dtype, ntp, nt, tr->ld, d, dp, nullptr, 1.0f, c->split_t.p, nullptr, 0, st, gate));
+        HIP_OR_FAIL(c, knn_launch_tn_rows(te->feat, dtype, nq, nq, te->ld, d, dp, nullptr, 1.0f, c->split_q.p, nullptr, 0, st, gate));
+        stage_end(c, st);
+        ftrain = c->split_t.p; ftest = c->split_q.p;
+        fld_t = fld_q = dp;
     } else if (nt % 64) {
         // the caller's rows, copied onto the 64-row tile grid: every tile the filter copies
         // into LDS is whole (one DMA form, knn_kernels.hip), the pad rows never pass (+inf norms).
@@ -889,7 +957,7 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
         ftrain = c->pad_t.p;
     }
 
-    const FilterPlan plan = fused ? fplan : knn_gemm_filter_plan(kelem, rb, k);
+    const FilterPlan plan = fused ? fplan : wide ? knn_wide_plan(k) : knn_gemm_filter_plan(kelem, rb, k);
     const bool shared = fused && knn_fused_list_share_width(plan) > 0;
     const int64_t n_qtiles = (nq + plan.bm - 1) / plan.bm;
     GemmFilterArgs g{};
@@ -903,19 +971,19 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     // 2.02 against 1.84 ms, r06bi)
     if (fused && c->train_splits <= 0 && capmul == 1) {
         int occ = 1;
-        if (knn_fused_occupancy(d, plan, &occ) != hipSuccess || occ < 1) occ = 1;
+        if (knn_fused_occupancy(dp, plan, &occ) != hipSuccess || occ < 1) occ = 1;
         int nb = 1;
         knn_fused_schedule(g, occ * c->num_cus, &nb);
         if (nb <= max_splits(nt, k, cap, smax)) nseg = nb;
     }
     if (nseg == 0) {
-        nseg = choose_splits(c, n_qtiles, nt, kelem, rb, k, cap, fused, d, &plan, smax);
+        nseg = choose_splits(c, n_qtiles, nt, kelem, rb, k, cap, fused, dp, &plan, smax, wide);
         g.g2 = -1;  // segment schedule
     }
     int64_t seg_len = (nt + nseg - 1) / nseg;
-    seg_len = (seg_len + 63) / 64 * 64;
+    seg_len = wide ? (seg_len + wgr - 1) / wgr * wgr : (seg_len + 63) / 64 * 64;
     g.train = ftrain; g.nt = nt; g.ld_t = fld_t;
-    g.test = ftest; g.nq = nq; g.ld_q = fld_q; g.d = d;
+    g.test = ftest; g.nq = nq; g.ld_q = fld_q; g.d = dp;  // (the operand rows' width)
     g.tnorm = c->tnorm.as<float>(); g.tnp = c->tnp.as<float>(); g.qnorm = c->qnorm.as<float>();
     g.tnmax = c->ctrl.as<uint32_t>() + 2;
     g.k = k; g.seg_len = seg_len; g.nseg = nseg;
@@ -941,7 +1009,7 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
     // its 2- and 4-GPU shares; B's and C's grids take segments or several rounds; the 32-query
     // instantiations compile no pacing code).  The two uses of c->cursor exclude each other
     // (segments: g2 < 0).
-    if (fused && g.g2 > 0 && g.p1_blocks == 0 && plan.qg == 2 && plan.kr > 0 && d == 128) {
+    if (fused && g.g2 > 0 && g.p1_blocks == 0 && plan.qg == 2 && plan.kr > 0 && dp == 128) {
         HIP_OR_FAIL(c, c->cursor.ensure(sizeof(int32_t) * 16));
         HIP_OR_FAIL(c, hipMemsetAsync(c->cursor.p, 0, sizeof(int32_t) * 16, st));
         g.pace = c->cursor.as<int32_t>();
@@ -973,6 +1041,7 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
         HIP_OR_FAIL(c, hipMemsetAsync(c->cnt.p, 0, sizeof(int32_t) * subs * nseg * nq, st));
     stage_begin(c, st, gate ? "gemm_filter_rerun" : "gemm_filter");
     if (fused) HIP_OR_FAIL(c, knn_launch_fused(g, plan, st));
+    else if (wide) HIP_OR_FAIL(c, knn_launch_wide(g, st));
     else HIP_OR_FAIL(c, knn_launch_gemm_filter(g, kelem, rb, st));
     stage_end(c, st);
 
@@ -1006,11 +1075,14 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
         c->stats[9] = fused ? 32 : 0;
         c->stats[10] = fused ? 32 * plan.qg : 0;
         c->stats[11] = i8 ? 1 : 0;
+        c->stats[15] = dp;
+        c->stats[16] = wide ? dp / 128 : 1;
         if (i8) c->i8_pass_nq = nq;
     } else {
         c->rerun_stats[0] = nseg;
         c->rerun_stats[1] = felem;
         c->rerun_stats[2] = fused;
+        c->rerun_stats[3] = dp;
     }
     return KNN_OK;
 }
@@ -1173,7 +1245,10 @@ knn_status predict_enqueue(knn_ctx* c, const knn_dataset* tr, const knn_dataset*
         // filter (every output is rewritten).  The decision is made on the device
         // (k_rerun_decide): the split stages are enqueued behind a gate, so a call ends in a
         // single stream synchronisation either way.
-        const bool adaptive = c->algo == KNN_ALGO_AUTO && filter_elem(algo, tr->dtype) == ELEM_ROUND;
+        // (where the split form exists at the padded width: rows of at most 128 features; elsewhere
+        // the overflowing queries go to the exact fallback list)
+        const bool adaptive = c->algo == KNN_ALGO_AUTO && filter_elem(algo, tr->dtype) == ELEM_ROUND &&
+                              split_rerun_width(tr->d, k) > 0;
         if ((s = run_gemm(c, tr, te, k, C, out, st, algo, nullptr)) != KNN_OK) return s;
         if (adaptive) {
             const int64_t limit = std::max<int64_t>(256, te->n / 16);
@@ -1213,6 +1288,7 @@ void pass_stats(knn_ctx* c, const int32_t* ctrl, bool gemm) {
         c->stats[3] = c->rerun_stats[1];
         c->stats[5] = c->rerun_stats[2];
         c->stats[11] = 0;
+        c->stats[15] = c->rerun_stats[3];
     }
 }
 
@@ -1234,7 +1310,7 @@ knn_dataset offset_rows(const knn_dataset& x, int64_t r0, int64_t n) {
 
 void reset_stats(knn_ctx* c) {
     c->stages.clear();
-    for (int i = 0; i < 15; i++) c->stats[i] = 0;
+    for (int i = 0; i < 17; i++) c->stats[i] = 0;
     c->stats[3] = -1;
 }
 // the vote / regression on CSR lists run no distance pass: the form and the exact evaluations of the
@@ -2009,9 +2085,9 @@ knn_status radius_prep(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te,
     stage_end(c, st);
     stage_begin(c, st, "radius_operands");
     if (!hit)
-        HIP_OR_FAIL(c, knn_launch_tn_rows(tr->feat, dtype, tiles * 64, nt, tr->ld, d, c->rm_tnorm.as<float>(), 1.0f,
+        HIP_OR_FAIL(c, knn_launch_tn_rows(tr->feat, dtype, tiles * 64, nt, tr->ld, d, d, c->rm_tnorm.as<float>(), 1.0f,
                                           c->rm_tblk.p, c->rm_tmax.as<float4>(), 64, st));
-    HIP_OR_FAIL(c, knn_launch_tn_rows(te->feat, dtype, nq, nq, te->ld, d, nullptr, -2.0f, c->rm_qop.p, nullptr, 0, st));
+    HIP_OR_FAIL(c, knn_launch_tn_rows(te->feat, dtype, nq, nq, te->ld, d, d, nullptr, -2.0f, c->rm_qop.p, nullptr, 0, st));
     stage_end(c, st);
     c->stats[8] = hit ? 1 : 0;
     if (may_cache) rp = {tr->feat, nt, d, tr->ld, dtype, c->generation, ep, true};
@@ -2207,6 +2283,26 @@ int32_t knn_radius_policy(int32_t metric, int32_t dtype, int32_t d, int64_t n_tr
         metric < KNN_METRIC_SQEUCLIDEAN || metric > KNN_METRIC_CHEBYSHEV || algo < KNN_ALGO_AUTO || algo > KNN_ALGO_GEMM_I8)
         return KNN_EINVAL;
     *form = radius_policy(metric, d, n_train, n_query, algo);
+    return KNN_OK;
+}
+
+int32_t knn_filter_policy(int32_t dtype, int32_t d, int32_t k, int64_t n_train, int64_t n_query, int32_t algo,
+                          int32_t* form, int32_t* operand_width) {
+    if (!form || !operand_width || d <= 0 || k < 1 || n_train < 0 || n_query < 0 ||
+        (dtype != KNN_F32 && dtype != KNN_BF16) || algo < KNN_ALGO_AUTO || algo > KNN_ALGO_GEMM_I8)
+        return KNN_EINVAL;
+    *form = 0;
+    *operand_width = 0;
+    const int a = choose_algo(algo, KNN_METRIC_SQEUCLIDEAN, n_train, n_query, d, k, dtype);
+    if (!is_gemm(a)) return KNN_OK;
+    // run_gemm's choice between the fused kernel and k_gemm_filter: the bf16 operand classes run
+    // fused wherever knn_fused_plan has a shape for (width, k) -- that does not depend on the
+    // device or the query count, which only pick among the shapes
+    const int fe = filter_elem(a, dtype), dp = filter_width(fe, d);
+    const bool fused = (fe == ELEM_ROUND || fe == ELEM_BF16) && knn_fused_supported(dp) &&
+                       knn_fused_plan(dp, k, n_query, 256, FusedForce{}, 1).nw > 0;
+    *form = is_wide(fe, dp) ? 3 : fused ? 1 : 2;
+    *operand_width = dp;
     return KNN_OK;
 }
 
@@ -2457,7 +2553,7 @@ int32_t knn_stage_times(const knn_ctx* c, const char** names, float* ms, int32_t
 
 int32_t knn_last_stats(const knn_ctx* c, int64_t* out, int32_t n) {
     if (!c || !out) return 0;
-    int32_t m = std::min(n, 15);
+    int32_t m = std::min(n, 17);
     for (int32_t i = 0; i < m; i++) out[i] = c->stats[i];
     return m;
 }

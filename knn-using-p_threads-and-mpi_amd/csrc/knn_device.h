@@ -197,6 +197,35 @@ __device__ __forceinline__ float4 load4(const bf16_t* p) {
                        __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
 }
 
+// One quad of a bf16 filter operand row (k_tn_rows, k_round_rows, and their host view
+// knn_debug_operand_rows): columns c .. c+3 of the operand, rn(scale * x) of the caller's row of
+// d elements and zero bits from column d on.  A quad inside the row is one load; the row's last
+// partial quad is read by element, so nothing at column d or beyond is touched.
+__host__ __device__ __forceinline__ uint32_t operand_rne(float x) {
+    const uint32_t b = __builtin_bit_cast(uint32_t, x);
+    return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
+}
+__host__ __device__ __forceinline__ float operand_widen(float v) { return v; }
+__host__ __device__ __forceinline__ float operand_widen(bf16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
+template <typename E>
+__host__ __device__ __forceinline__ uint2 operand_quad(const E* row, int c, int d, float scale) {
+    if (c >= d) return make_uint2(0u, 0u);
+    float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (c + 4 <= d) {
+        const float4 q = load4(row + c);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else
+#endif
+    {
+        for (int t = 0; t < 4; t++)
+            if (c + t < d) v[t] = operand_widen(row[c + t]);
+    }
+    uint32_t o[4];
+    for (int t = 0; t < 4; t++) o[t] = c + t < d ? operand_rne(scale * v[t]) : 0u;  // (zero bits whatever scale's sign)
+    return make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
+}
+
 // ---------------------------------------------------------------------------------
 // The int8 filter operand class (fp32 data, KNN_ALGO_GEMM_I8; DESIGN.md "int8 filter operands").
 // One symmetric scale per train set, s = max|t| / 127; a row element x becomes the integer

@@ -39,35 +39,37 @@ static constexpr bool FUSED_PARK_DEFAULT = true;
 
 // ---------------------------------------------------------------------------------
 // k_tn_rows<E>: operand rows of the filter (no augmented columns).
-//   queries (norms == NULL): [n][d] bf16 = rn(scale * x)
-//   train: blocks of bn rows, [bn][d] bf16 = rn(x) | bn fp32 norms | {max tn, max |t - rt|,
+//   queries (norms == NULL): [n][dp] bf16 = rn(scale * x)
+//   train: blocks of bn rows, [bn][dp] bf16 = rn(x) | bn fp32 norms | {max tn, max |t - rt|,
 //   max |rt|, 0} of the enclosing 64-row tile (k_row_norms) -- the image one tile's LDS-DMA
 //   copies, header included.  Rows n_valid .. n-1 (padding past the tile grid): zero features
 //   and norm 0x1.fep127, so y = tn - 2 q.t never passes a fast test.  n % bn == 0.
+// d: the caller's row width; dp >= d (dp % 4 == 0): the operand's.  Columns d .. dp-1 are zero
+// bits (a zero product adds nothing to the MFMA chain); no load touches column d or beyond --
+// whole quads inside the row are one load, the row's last partial quad is read by element (the
+// caller's buffer may end at (n - 1) ld + d elements, and a view's pad columns hold anything).
 // ---------------------------------------------------------------------------------
 template <typename E>
 __global__ __launch_bounds__(256) void k_tn_rows(const E* __restrict__ x, int64_t n, int64_t n_valid, int ld, int d,
-                                                 const float* __restrict__ norms, float scale,
+                                                 int dp, const float* __restrict__ norms, float scale,
                                                  unsigned char* __restrict__ out, const float4* __restrict__ tstat,
                                                  int bn, const int32_t* __restrict__ gate) {
     if (gate && *gate == 0) return;
-    const int per_row = d >> 2;
+    const int per_row = dp >> 2;
     auto quad = [&](int64_t r, int c) -> uint2 {
         if (r >= n_valid) return make_uint2(0u, 0u);
-        const float4 v = load4(x + r * ld + c);
-        return make_uint2(bf16_rne(scale * v.x) | (bf16_rne(scale * v.y) << 16),
-                          bf16_rne(scale * v.z) | (bf16_rne(scale * v.w) << 16));
+        return operand_quad(x + r * ld, c, d, scale);
     };
     if (!norms) {
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n * per_row; i += (int64_t)gridDim.x * 256) {
             const int64_t r = i / per_row;
             const int c = (int)(i - r * per_row) * 4;
-            *reinterpret_cast<uint2*>(out + (r * d + c) * 2) = quad(r, c);
+            *reinterpret_cast<uint2*>(out + (r * dp + c) * 2) = quad(r, c);
         }
         return;
     }
     const int64_t per_tile = (int64_t)bn * per_row + bn + 1;
-    const int64_t tb = (int64_t)bn * d * 2 + 4 * bn + 16;
+    const int64_t tb = (int64_t)bn * dp * 2 + 4 * bn + 16;
     const int64_t nvt = (n_valid + 63) >> 6;  // 64-row tiles with statistics
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (n / bn) * per_tile; i += (int64_t)gridDim.x * 256) {
         const int64_t T = i / per_tile;
@@ -77,34 +79,51 @@ __global__ __launch_bounds__(256) void k_tn_rows(const E* __restrict__ x, int64_
         if (l < (int64_t)bn * per_row) {
             const int rr = (int)(l / per_row);
             const int c = (int)(l - (int64_t)rr * per_row) * 4;
-            *reinterpret_cast<uint2*>(blk + ((int64_t)rr * d + c) * 2) = quad(r0 + rr, c);
+            *reinterpret_cast<uint2*>(blk + ((int64_t)rr * dp + c) * 2) = quad(r0 + rr, c);
         } else if (l < (int64_t)bn * per_row + bn) {
             const int rr = (int)(l - (int64_t)bn * per_row);
             const int64_t r = r0 + rr;
-            *reinterpret_cast<float*>(blk + (int64_t)bn * d * 2 + 4 * rr) = r < n_valid ? norms[r] : 0x1.fep127f;
+            *reinterpret_cast<float*>(blk + (int64_t)bn * dp * 2 + 4 * rr) = r < n_valid ? norms[r] : 0x1.fep127f;
         } else {
             const int64_t t64 = r0 >> 6;
-            *reinterpret_cast<float4*>(blk + (int64_t)bn * d * 2 + 4 * bn) =
+            *reinterpret_cast<float4*>(blk + (int64_t)bn * dp * 2 + 4 * bn) =
                 t64 < nvt ? tstat[t64] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
     }
 }
 
-hipError_t knn_launch_tn_rows(const void* x, int elem, int64_t n, int64_t n_valid, int ld, int d, const float* norms,
-                              float scale, void* out, const float4* tstat, int bn, hipStream_t st,
+hipError_t knn_launch_tn_rows(const void* x, int elem, int64_t n, int64_t n_valid, int ld, int d, int dp,
+                              const float* norms, float scale, void* out, const float4* tstat, int bn, hipStream_t st,
                               const int32_t* gate) {
     if (n <= 0) return hipSuccess;
-    if (d % 4 || ld % 4 || (norms && (bn <= 0 || n % bn))) return hipErrorInvalidValue;
-    const int64_t total = norms ? (n / bn) * ((int64_t)bn * (d / 4) + bn + 1) : n * (d / 4);
+    if (d < 1 || dp < d || dp % 4 || ld % 4 || (norms && (bn <= 0 || n % bn))) return hipErrorInvalidValue;
+    const int64_t total = norms ? (n / bn) * ((int64_t)bn * (dp / 4) + bn + 1) : n * (dp / 4);
     const dim3 grid(gated_grid(elementwise_grid(total), gate));
     if (elem == ELEM_BF16)
-        hipLaunchKernelGGL(k_tn_rows<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, n, n_valid, ld, d, norms, scale,
-                           (unsigned char*)out, tstat, bn, gate);
+        hipLaunchKernelGGL(k_tn_rows<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, n, n_valid, ld, d, dp, norms,
+                           scale, (unsigned char*)out, tstat, bn, gate);
     else
-        hipLaunchKernelGGL(k_tn_rows<float>, grid, dim3(256), 0, st, (const float*)x, n, n_valid, ld, d, norms, scale,
-                           (unsigned char*)out, tstat, bn, gate);
+        hipLaunchKernelGGL(k_tn_rows<float>, grid, dim3(256), 0, st, (const float*)x, n, n_valid, ld, d, dp, norms,
+                           scale, (unsigned char*)out, tstat, bn, gate);
     KNN_LAUNCH_CHECK();
     return hipSuccess;
+}
+
+// Host view of the operand rows (no GPU call; tests/test_filter_width_cpu.py): out [n][dp] bf16 =
+// the rows k_tn_rows' query form and k_round_rows (scale 1) write for x [n][ld] of d elements --
+// operand_quad as the kernels run it, but for the load: on the host every quad takes the per-element
+// branch, on the device a whole quad inside the row is one load4.  elem: ELEM_F32 or ELEM_BF16.
+extern "C" int knn_debug_operand_rows(const void* x, int elem, long long n, int ld, int d, int dp, float scale,
+                                      uint16_t* out) {
+    if (!x || !out || n < 0 || d < 1 || dp < d || dp % 4 || ld < d || (elem != ELEM_F32 && elem != ELEM_BF16)) return -1;
+    for (long long r = 0; r < n; r++)
+        for (int c = 0; c < dp; c += 4) {
+            const uint2 q = elem == ELEM_BF16 ? operand_quad((const bf16_t*)x + r * ld, c, d, scale)
+                                              : operand_quad((const float*)x + r * ld, c, d, scale);
+            uint16_t* o = out + r * dp + c;
+            o[0] = (uint16_t)q.x; o[1] = (uint16_t)(q.x >> 16); o[2] = (uint16_t)q.y; o[3] = (uint16_t)(q.y >> 16);
+        }
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------

@@ -347,10 +347,13 @@ FilterPlan knn_gemm_filter_plan(int elem, int row_bytes, int k);
 hipError_t knn_launch_gemm_filter(const GemmFilterArgs& a, int elem, int row_bytes, hipStream_t st);
 size_t knn_gemm_filter_lds(int elem, int row_bytes, int k);
 hipError_t knn_gemm_filter_occupancy(int elem, int row_bytes, int k, int* blocks_per_cu);
-// fp32 rows [n][ld] (d % 4 == 0) -> bf16 rows [n][2d]: hi = rn(x), lo = rn(x - hi)
-hipError_t knn_launch_split_rows(const float* x, int64_t n, int ld, int d, uint16_t* out, hipStream_t st,
+// fp32 rows [n][ld] of d elements -> bf16 rows [n][2 dp]: hi = rn(x), lo = rn(x - hi), each half
+// dp >= d elements wide (dp % 4 == 0) with zero bits in columns d .. dp-1
+hipError_t knn_launch_split_rows(const float* x, int64_t n, int ld, int d, int dp, uint16_t* out, hipStream_t st,
                                  const int32_t* gate = nullptr);
-hipError_t knn_launch_round_rows(const float* x, int64_t n, int ld, int d, uint16_t* out, hipStream_t st,
+// fp32 rows [n][ld] of d elements -> bf16 rows [n][dp] rn(x), dp >= d, dp % 4 == 0: columns d .. dp-1
+// are zero bits, and no load touches column d or beyond
+hipError_t knn_launch_round_rows(const float* x, int64_t n, int ld, int d, int dp, uint16_t* out, hipStream_t st,
                                  const int32_t* gate = nullptr);
 hipError_t knn_launch_fill_u32(uint32_t* p, int64_t n, uint32_t v, const int32_t* gate, hipStream_t st);
 // host_mapped[0..n) = ctrl[0..n) (a mapped pinned host buffer), then ctrl[0..n) = 0
@@ -393,11 +396,22 @@ int knn_fused_list_share_width(const FilterPlan& f);
 int knn_fused_schedule(GemmFilterArgs& a, int slots, int* nseg);
 // f: the plan run_gemm sized the grid and operands with (knn_fused_plan)
 hipError_t knn_launch_fused(const GemmFilterArgs& a, const FilterPlan& f, hipStream_t st);
-// the fused filter's operands: x -> queries [n][d] bf16 rn(scale x) (norms == NULL),
-// or train blocks of bn rows [bn][d] bf16 | bn fp32 norms | tstat of the enclosing 64-row tile
-hipError_t knn_launch_tn_rows(const void* x, int elem, int64_t n, int64_t n_valid, int ld, int d, const float* norms,
-                              float scale, void* out, const float4* tstat, int bn, hipStream_t st,
+// the fused filter's operands: x -> queries [n][dp] bf16 rn(scale x) (norms == NULL),
+// or train blocks of bn rows [bn][dp] bf16 | bn fp32 norms | tstat of the enclosing 64-row tile.
+// d: the caller's row width, dp >= d (dp % 4 == 0) the operand's: columns d .. dp-1 are zero bits
+hipError_t knn_launch_tn_rows(const void* x, int elem, int64_t n, int64_t n_valid, int ld, int d, int dp,
+                              const float* norms, float scale, void* out, const float4* tstat, int bn, hipStream_t st,
                               const int32_t* gate = nullptr);
+// K-chunked filter for wide rows (knn_wide.hip, k_gemm_wide): bf16 operand rows of dp = d rounded up
+// to a multiple of 128 features, 256 < d <= 4096, cut into chunks of 128; k_gemm_filter's
+// protocol (GemmFilterArgs with d = ld_t = ld_q = dp, CandRec / cnt / gthr), k <= 128.
+// knn_wide_width: dp, or 0 when the kernel does not take d.  The train operand covers the grid of
+// knn_wide_group_rows()-row groups with zero rows, tnorm / tnp with +inf; seg_len is a multiple of it.
+int knn_wide_width(int d);
+int knn_wide_group_rows();
+FilterPlan knn_wide_plan(int k);
+hipError_t knn_wide_occupancy(int k, int* blocks_per_cu);
+hipError_t knn_launch_wide(const GemmFilterArgs& a, hipStream_t st);
 // the int8 operand class (fp32 x, scale s; knn_i8_quant): queries [n][d] int8 (norms == NULL), or
 // train blocks of bn rows [bn][d] int8 | bn int32 -knn_i8_norm_q(tn, s2) | tstat of the enclosing
 // 64-row tile; pad rows: zero features and -2^30

@@ -769,48 +769,56 @@ __global__ __launch_bounds__(256) void k_row_norms(const E* __restrict__ x, int6
 }
 
 // ---------------------------------------------------------------------------------
-// k_split_rows: fp32 rows -> bf16 [hi | lo] rows for the split filter (ELEM_SPLIT).
+// k_split_rows: fp32 rows of d elements -> bf16 [hi | lo] rows of 2 dp elements for the split
+// filter (ELEM_SPLIT), dp >= d.
 // hi = rn(x); x - hi is exact in fp32 (Sterbenz: hi is within 2^-8 |x| of x, or 0 when
 // |x| < 2^-134); lo = rn(x - hi).  |x - hi - lo| <= 2^-16 |x| + 2^-134.  One thread per
-// 4 elements (coalesced float4 in, two 8-byte bf16 quads out).
+// 4 elements (coalesced float4 in, two 8-byte bf16 quads out).  Columns d .. dp-1 of both halves
+// are zero bits; a row's last partial quad is read by element (no load touches column d or beyond).
 // ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_split_rows(const float* __restrict__ x, int64_t n, int ld, int d,
+__global__ __launch_bounds__(256) void k_split_rows(const float* __restrict__ x, int64_t n, int ld, int d, int dp,
                                                     bf16_t* __restrict__ out, const int32_t* __restrict__ gate) {
     if (gate && *gate == 0) return;
-    const int per_row = d >> 2;
+    const int per_row = dp >> 2;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n * per_row; i += (int64_t)gridDim.x * 256) {
     const int64_t r = i / per_row;
     const int c = (int)(i - r * per_row) * 4;
-    const float4 v = *reinterpret_cast<const float4*>(x + r * ld + c);
-    const float e[4] = {v.x, v.y, v.z, v.w};
+    float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (c + 4 <= d) {
+        const float4 v = *reinterpret_cast<const float4*>(x + r * ld + c);
+        e[0] = v.x; e[1] = v.y; e[2] = v.z; e[3] = v.w;
+    } else {
+        for (int t = 0; t < 3; t++)
+            if (c + t < d) e[t] = x[r * ld + c + t];
+    }
     uint32_t hi[4], lo[4];
 #pragma unroll
     for (int t = 0; t < 4; t++) {
-        hi[t] = bf16_rne(e[t]);
-        lo[t] = bf16_rne(e[t] - __uint_as_float(hi[t] << 16));
+        hi[t] = c + t < d ? bf16_rne(e[t]) : 0u;
+        lo[t] = c + t < d ? bf16_rne(e[t] - __uint_as_float(hi[t] << 16)) : 0u;
     }
-    bf16_t* o = out + r * (int64_t)(2 * d) + c;
+    bf16_t* o = out + r * (int64_t)(2 * dp) + c;
     *reinterpret_cast<uint2*>(o) = make_uint2(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16));
-    *reinterpret_cast<uint2*>(o + d) = make_uint2(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16));
+    *reinterpret_cast<uint2*>(o + dp) = make_uint2(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16));
     }
 }
 
 // ---------------------------------------------------------------------------------
-// k_round_rows: fp32 rows -> bf16 rows rn(x) for the rounded filter (ELEM_ROUND, d
-// elements per row): |x - rn(x)| <= 2^-8 |x| + 2^-134.  The filter runs the bf16 kernel
+// k_round_rows: fp32 rows of d elements -> bf16 rows rn(x) of dp >= d elements for the rounded
+// filter (ELEM_ROUND): |x - rn(x)| <= 2^-8 |x| + 2^-134.  The filter runs the bf16 kernel
 // on them; the certificate (knn_capi.cpp) carries the rounding.  One thread per 4
-// elements (coalesced float4 in, one 8-byte bf16 quad out).
+// elements (coalesced float4 in, one 8-byte bf16 quad out).  Columns d .. dp-1 are zero bits;
+// a row's last partial quad is read by element, so no load touches column d or beyond.
 // ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_round_rows(const float* __restrict__ x, int64_t n, int ld, int d,
+__global__ __launch_bounds__(256) void k_round_rows(const float* __restrict__ x, int64_t n, int ld, int d, int dp,
                                                     bf16_t* __restrict__ out, const int32_t* __restrict__ gate) {
     if (gate && *gate == 0) return;
-    const int per_row = d >> 2;
+    const int per_row = dp >> 2;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n * per_row; i += (int64_t)gridDim.x * 256) {
         const int64_t r = i / per_row;
         const int c = (int)(i - r * per_row) * 4;
-        const float4 v = *reinterpret_cast<const float4*>(x + r * ld + c);
-        *reinterpret_cast<uint2*>(out + r * (int64_t)d + c) =
-            make_uint2(bf16_rne(v.x) | (bf16_rne(v.y) << 16), bf16_rne(v.z) | (bf16_rne(v.w) << 16));
+        const uint2 o = operand_quad(x + r * ld, c, d, 1.0f);
+        *reinterpret_cast<uint2*>(out + r * (int64_t)dp + c) = o;
     }
 }
 
@@ -2541,22 +2549,22 @@ hipError_t knn_launch_vote_sweep(const VoteSweepArgs& a, hipStream_t st) {
     }
 }
 
-hipError_t knn_launch_split_rows(const float* x, int64_t n, int ld, int d, uint16_t* out, hipStream_t st,
+hipError_t knn_launch_split_rows(const float* x, int64_t n, int ld, int d, int dp, uint16_t* out, hipStream_t st,
                                  const int32_t* gate) {
-    const int64_t total = n * (d / 4);
+    if (d < 1 || dp < d || dp % 4 || ld % 4) return hipErrorInvalidValue;
+    const int64_t total = n * (dp / 4);
     if (total <= 0) return hipSuccess;
-    if (d % 4 || ld % 4) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_split_rows, dim3(gated_grid(elementwise_grid(total), gate)), dim3(256), 0, st, x, n, ld, d, out, gate);
+    hipLaunchKernelGGL(k_split_rows, dim3(gated_grid(elementwise_grid(total), gate)), dim3(256), 0, st, x, n, ld, d, dp, out, gate);
     KNN_LAUNCH_CHECK();
     return hipSuccess;
 }
 
-hipError_t knn_launch_round_rows(const float* x, int64_t n, int ld, int d, uint16_t* out, hipStream_t st,
+hipError_t knn_launch_round_rows(const float* x, int64_t n, int ld, int d, int dp, uint16_t* out, hipStream_t st,
                                  const int32_t* gate) {
-    const int64_t total = n * (d / 4);
+    if (d < 1 || dp < d || dp % 4 || ld % 4) return hipErrorInvalidValue;
+    const int64_t total = n * (dp / 4);
     if (total <= 0) return hipSuccess;
-    if (d % 4 || ld % 4) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_round_rows, dim3(gated_grid(elementwise_grid(total), gate)), dim3(256), 0, st, x, n, ld, d, out, gate);
+    hipLaunchKernelGGL(k_round_rows, dim3(gated_grid(elementwise_grid(total), gate)), dim3(256), 0, st, x, n, ld, d, dp, out, gate);
     KNN_LAUNCH_CHECK();
     return hipSuccess;
 }
