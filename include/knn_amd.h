@@ -554,8 +554,8 @@ knn_status knn_regress_sweep(knn_ctx* ctx, const knn_dataset* train, const knn_d
  *   at any size under KNN_ALGO_GEMM_BF16; under KNN_ALGO_AUTO and the other GEMM algos MFMA from a floor of train
  *   rows (>= 16384) and a floor of queries.  KNN_EINVAL for an unknown metric, dtype or algo.
  * Not here: host-buffer entry points, a multi-rank driver (counts and class counts add over train
- * shards, CSR lists concatenate by shard), several thresholds in one pass, distance-sorted
- * segments, regression error sums, and an int8 operand class for the MFMA form.
+ * shards, CSR lists concatenate by shard), distance-sorted segments (several thresholds in one
+ * pass: "Radius sweep" below), regression error sums, and an int8 operand class for the MFMA form.
  */
 knn_status knn_radius_count_device(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test, float thr,
                                    int32_t num_classes, int64_t self_base, int32_t outlier_label,
@@ -574,6 +574,66 @@ knn_status knn_radius_vote_device(knn_ctx* ctx, int64_t nq, int64_t n_train, con
 knn_status knn_radius_regress_device(knn_ctx* ctx, int64_t nq, int64_t n_train, const int64_t* d_offsets,
                                      const int32_t* d_idx, const float* d_dist, const float* d_train_targets,
                                      int32_t weights, float* d_pred, void* hip_stream);
+
+/*
+ * Radius sweep: "which r?" in one distance pass, as knn_sweep_device answers "which k?".  The
+ * distances do not depend on the threshold, so R thresholds cost one pass, not R.
+ *   thresholds  a HOST array thr[0 .. R - 1], 1 <= R <= 32, each a binary32 value in [0, FLT_MAX) in
+ *               the units of "Radius neighbours", NON-DECREASING (equal neighbours are allowed and
+ *               give equal rows).  KNN_EINVAL otherwise, before anything is launched.
+ *   membership  train row t is in query q's neighbourhood at index r iff D(q, t) <= thr[r], D being
+ *               the very bits knn_radius_count_device tests; the self row is excluded under
+ *               self_base; a NaN D is never a member.  Neighbourhoods are nested, so a pair has one
+ *               bucket -- the smallest r with D <= thr[r] -- and every output is a prefix sum over
+ *               buckets.  Row r of every output equals, bit for bit, what the single-threshold entry
+ *               point returns for thr[r] on the same context.
+ *   outputs     row r of an [R][...] output starts at r * ld_out (elements; times num_classes for
+ *               class_counts / scores), with ld_out >= nq the caller's row pitch: a caller may walk
+ *               its queries in blocks and fill column blocks of larger arrays.  Elements outside the
+ *               call's nq columns are not written.
+ * knn_radius_sweep_count_device: one distance pass under the context's metric, then
+ *   k_radius_sweep_finish.  The pass has the two forms of the single-threshold pass, with the same
+ *   results bit for bit, and takes the one knn_radius_policy states for the call's shape: the
+ *   direct form (k_radius_sweep_tile) or the MFMA-filtered form (k_radius_sweep_gemm: the bracket
+ *   [L, U] of a pair decides its bucket where no threshold lies inside it, and only the other
+ *   pairs get the direct form's D).  knn_last_stats()[13], [14] and [8] read as after
+ *   knn_radius_count_device.  d_count int32 [R][ld_out]; d_class_counts int32 [R][ld_out][num_classes];
+ *   d_pred int32 [R][ld_out], the uniform vote, ties to the smallest label, outlier_label where
+ *   count is 0; d_correct int64 [R] (needs d_query_labels), the queries with pred == label;
+ *   d_outliers int64 [R], the queries with no neighbour.  Each is optional, not all NULL.
+ *   d_correct and d_outliers are ADDED TO, NOT ZEROED, so that the blocks of a query set accumulate:
+ *   THE CALLER ZEROES THEM before the first block.  The pass keeps integer histograms of
+ *   nq * (R + 1) * (1 + num_classes) int32 (num_classes counts as 0 when no class output is asked);
+ *   a call whose histograms exceed the context's workspace budget (the bytes of its GEMM-path
+ *   candidate workspace) is refused with KNN_ERANGE before anything is launched, and the message
+ *   names the largest nq that fits -- split the queries into blocks of at most that many.
+ *   knn_radius_sweep_max_queries says that number for (R, num_classes) without a GPU call
+ *   (num_classes = 0: no class output; 0 for a bad argument).
+ * knn_radius_vote_sweep_device: the weighted vote of every threshold on CSR lists the caller holds,
+ *   from a fill at any threshold >= thr[R - 1].  Row r is knn_radius_vote_device on the sub-list of
+ *   the entries with dist <= thr[r], in list order: the same binary32 weights, the zero rule over
+ *   the SUB-list ("any entry of it has d == 0"), one thread's chain of adds per class in ascending
+ *   list position, ties to the smallest label; an empty sub-list gives outlier_label and a +0 score
+ *   row.  d_dist is needed under every kind of weights (the filter reads it).  d_pred int32
+ *   [R][ld_out], d_correct int64 [R] (ADDED TO: the caller zeroes it), d_scores fp32
+ *   [R][ld_out][num_classes] (this call's nq rows of every r are zeroed here); each optional, not
+ *   all NULL.  The checks of knn_radius_vote_device run on every entry of the lists, whether or not
+ *   it is in a sub-list.
+ * Stages under profile = 1: "radius_sweep", "radius_sweep_finish", "radius_vote_sweep".
+ * Not here: a regression sweep (error sums per r), host-buffer entry points, a swept fill that
+ * returns per-r offsets, the MFMA form at other widths, int8 operands.
+ */
+knn_status knn_radius_sweep_count_device(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test,
+                                         const float* thresholds, int32_t R, int32_t num_classes,
+                                         int64_t self_base, int32_t outlier_label, const int32_t* d_query_labels,
+                                         int64_t ld_out, int32_t* d_count, int32_t* d_class_counts, int32_t* d_pred,
+                                         int64_t* d_correct, int64_t* d_outliers, void* hip_stream);
+int64_t knn_radius_sweep_max_queries(const knn_ctx* ctx, int32_t R, int32_t num_classes);
+knn_status knn_radius_vote_sweep_device(knn_ctx* ctx, int64_t nq, int64_t n_train, const int64_t* d_offsets,
+                                        const int32_t* d_idx, const float* d_dist, const int32_t* d_train_labels,
+                                        int32_t num_classes, int32_t weights, const float* thresholds, int32_t R,
+                                        int32_t outlier_label, const int32_t* d_query_labels, int64_t ld_out,
+                                        int32_t* d_pred, int64_t* d_correct, float* d_scores, void* hip_stream);
 
 /* Per-stage device times (ms) of the last predict call when opts.profile >= 1.
  * names: optional array of n const char* to receive stage names. Returns the

@@ -201,6 +201,13 @@ int* KNN_radius(ArffData* train, ArffData* test, float radius, int weights, int 
                 long* outliers = nullptr);
 // Leave-one-out on the train set: row i voted by the other rows within the radius.
 int* KNN_radius_loo(ArffData* train, float radius, int weights, int outlier_label, long* outliers = nullptr);
+// The radius classifier of n_radii <= 32 non-decreasing radii from one distance pass (knn_amd.h
+// "Radius sweep").  Returns malloc'd int[n_radii][n_test], row r = KNN_radius at radii[r], caller
+// frees; outliers (optional) receives n_radii counts of rows with no neighbour.
+int* KNN_radius_sweep(ArffData* train, ArffData* test, const float* radii, int n_radii, int weights,
+                      int outlier_label, long* outliers = nullptr);
+int* KNN_radius_sweep_loo(ArffData* train, const float* radii, int n_radii, int weights, int outlier_label,
+                          long* outliers = nullptr);
 // main.cpp:87 -- calloc'd int[C*C], C = dataset->num_classes(), row = true class.
 int* computeConfusionMatrix(int* predictions, ArffData* dataset);
 // main.cpp:102

@@ -142,6 +142,9 @@ def load_library(path=LIB_PATH):
         "knn_radius_fill_device": (I32, [P, DS, DS, F, I64, P, P, P, P]),
         "knn_radius_vote_device": (I32, [P, I64, I64, P, P, P, P, I32, I32, I32, P, P, P, P, P]),
         "knn_radius_regress_device": (I32, [P, I64, I64, P, P, P, P, I32, P, P]),
+        "knn_radius_sweep_count_device": (I32, [P, DS, DS, P, I32, I32, I64, I32, P, I64, P, P, P, P, P, P]),
+        "knn_radius_sweep_max_queries": (I64, [P, I32, I32]),
+        "knn_radius_vote_sweep_device": (I32, [P, I64, I64, P, P, P, P, I32, I32, P, I32, I32, P, I64, P, P, P, P]),
         "knn_arff_copy_targets": (I32, [P, P, I32, P]),
         "knn_stage_times": (I32, [P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(F), I32]),
         "knn_last_stats": (I32, [P, ctypes.POINTER(I64), I32]),
@@ -933,6 +936,148 @@ class Context:
                                           outlier_label, query_labels=labels, self_base=0, scores=scores,
                                           stream=stream, d=d)
 
+    # radius sweep (knn_amd.h "Radius sweep")
+    def _thresholds(self, radii, thresholds):
+        """The binary32 thresholds of a sweep: exactly one of radii= (each float32(r) * float32(r)
+        under the Euclidean metric, float32(r) otherwise) and thresholds= (passed as they are).
+        The library checks their number, range and order."""
+        if (radii is None) == (thresholds is None):
+            raise KnnError(KNN_EINVAL, "give exactly one of radii= and thresholds=")
+        if thresholds is not None:
+            return np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+        r = np.asarray(radii, dtype=np.float32).reshape(-1)
+        if (r < 0).any():
+            raise KnnError(KNN_EINVAL, f"radii must be >= 0, got {radii}")
+        with np.errstate(over="ignore"):
+            return np.ascontiguousarray(r * r if self.metric == "euclidean" else r)
+
+    def radius_sweep_device(self, train, labels, test, radii=None, thresholds=None, num_classes=None,
+                            query_labels=None, self_base=None, outlier_label=-1, class_counts=False, query_block=None,
+                            stream=None, d=None):
+        """The counts and the uniform vote of every one of R <= 32 non-decreasing radii from one
+        distance pass (knn_radius_sweep_count_device).  Returns (count int32 [R][nq], pred int32
+        [R][nq] or None without labels, correct int64 [R] or None without query_labels, outliers
+        int64 [R] = the queries with no neighbour[, class_counts int32 [R][nq][C] with
+        class_counts=True]); row r is radius_count_device at radii[r].  The queries are walked in
+        blocks of query_block, or of the most the library's workspace takes; every block writes
+        its columns of the outputs and adds into correct / outliers."""
+        import torch
+        thr = self._thresholds(radii, thresholds)
+        R = int(thr.size)
+        tr, te = self._datasets_arg(train, labels, test, d)
+        dev = test.device
+        nq = te.n
+        voting = labels is not None
+        if (voting or class_counts) and (labels is None or num_classes is None):
+            raise KnnError(KNN_EINVAL, "class outputs need labels and num_classes")
+        if query_labels is not None:
+            if not voting:
+                raise KnnError(KNN_EINVAL, "query_labels need labels and num_classes")
+            _check_tensor(query_labels, "query_labels", torch.int32, nq)
+        C = num_classes if voting else 0
+        rows = max(R, 1)
+        count = torch.empty((rows, nq), dtype=torch.int32, device=dev)
+        pred = torch.empty((rows, nq), dtype=torch.int32, device=dev) if voting else None
+        correct = torch.zeros(rows, dtype=torch.int64, device=dev) if query_labels is not None else None
+        outliers = torch.zeros(rows, dtype=torch.int64, device=dev)
+        cc = torch.empty((rows, nq, num_classes), dtype=torch.int32, device=dev) if class_counts else None
+        if query_block is None:
+            query_block = int(self.lib.knn_radius_sweep_max_queries(self.h, R, C)) if 1 <= R <= 32 else max(nq, 1)
+        if query_block < 1:
+            raise KnnError(KNN_EINVAL, f"query_block must be >= 1, got {query_block}")
+        st = self._stream(stream, test)
+        thr_p = thr.ctypes.data_as(ctypes.c_void_p)
+        q0 = 0
+        while True:  # (nq = 0: one call, for the library's checks)
+            n = min(query_block, nq - q0)
+            # (an empty tensor has no address)
+            tq = knn_dataset((te.feat or 0) + q0 * te.ld * (2 if te.dtype == KNN_BF16 else 4), None, n, te.d, te.ld,
+                             te.dtype)
+            self._check(self.lib.knn_radius_sweep_count_device(
+                self.h, ctypes.byref(tr), ctypes.byref(tq), thr_p, R, C,
+                -1 if self_base is None else self_base + q0, outlier_label,
+                None if query_labels is None or nq == 0 else query_labels.data_ptr() + 4 * q0, nq,
+                count.data_ptr() + 4 * q0, None if cc is None else cc.data_ptr() + 4 * q0 * num_classes,
+                None if pred is None else pred.data_ptr() + 4 * q0, _opt_ptr(correct) if nq else None,
+                outliers.data_ptr(), st))
+            q0 += n
+            if q0 >= nq:
+                break
+        out = (count, pred, correct, outliers)
+        return out + (cc,) if class_counts else out
+
+    def radius_sweep_loo_device(self, train, labels, radii=None, thresholds=None, num_classes=None,
+                                outlier_label=-1, class_counts=False, query_block=None, stream=None, d=None):
+        """Leave-one-out for every radius: every train row voted on by the other rows within each
+        radius and scored against its own label (radius_sweep_device with self_base=0)."""
+        return self.radius_sweep_device(train, labels, train, radii, thresholds, num_classes, query_labels=labels,
+                                        self_base=0, outlier_label=outlier_label, class_counts=class_counts,
+                                        query_block=query_block, stream=stream, d=d)
+
+    def radius_vote_sweep_device(self, offsets, idx, dist, train_labels, num_classes, radii=None, thresholds=None,
+                                 weights="uniform", outlier_label=-1, query_labels=None, scores=True, stream=None):
+        """The weighted vote of every radius on CSR lists the caller holds, filled at any threshold
+        >= the last one (knn_radius_vote_sweep_device): row r is radius_vote_device on the entries
+        with dist <= thresholds[r].  Returns (pred int32 [R][nq], correct int64 [R] or None, scores
+        float32 [R][nq][C] or None)."""
+        import torch
+        self._on_device(idx)
+        thr = self._thresholds(radii, thresholds)
+        R = int(thr.size)
+        nq = offsets.numel() - 1
+        _check_tensor(offsets, "offsets", torch.int64, 1)
+        _check_tensor(idx, "idx", torch.int32)
+        if dist is None:
+            raise KnnError(KNN_EINVAL, "the vote sweep reads the distances under every kind of weights")
+        _check_tensor(dist, "dist", torch.float32, idx.numel())
+        _check_tensor(train_labels, "train_labels", torch.int32)
+        rows = max(R, 1)
+        pred = torch.empty((rows, nq), dtype=torch.int32, device=idx.device)
+        sc = torch.empty((rows, nq, num_classes), dtype=torch.float32, device=idx.device) if scores else None
+        correct = None
+        if query_labels is not None:
+            _check_tensor(query_labels, "query_labels", torch.int32, nq)
+            correct = torch.zeros(rows, dtype=torch.int64, device=idx.device)
+        self._check(self.lib.knn_radius_vote_sweep_device(
+            self.h, nq, train_labels.numel(), offsets.data_ptr(), idx.data_ptr(), dist.data_ptr(),
+            train_labels.data_ptr(), num_classes, _weight_kind(weights), thr.ctypes.data_as(ctypes.c_void_p), R,
+            outlier_label, _opt_ptr(query_labels), nq, pred.data_ptr(), _opt_ptr(correct), _opt_ptr(sc),
+            self._stream(stream, idx)))
+        return pred, correct, sc
+
+    def radius_sweep_predict_device(self, train, labels, test, radii=None, thresholds=None, num_classes=None,
+                                    weights="uniform", outlier_label=-1, query_labels=None, self_base=None,
+                                    scores=True, stream=None, d=None):
+        """radius_predict_device for every radius: returns (pred int32 [R][nq], scores float32
+        [R][nq][C] or None, count int32 [R][nq]); with query_labels a fourth element, correct int64
+        [R].  "uniform" takes the count sweep alone (no lists; the scores are the class counts as
+        floats); the weighted kinds build the lists once, at the last threshold, and run the vote
+        sweep on them."""
+        import torch
+        thr = self._thresholds(radii, thresholds)
+        if _weight_kind(weights) == WEIGHTS["uniform"]:
+            out = self.radius_sweep_device(train, labels, test, None, thr, num_classes, query_labels, self_base,
+                                           outlier_label, class_counts=bool(scores), stream=stream, d=d)
+            count, pred, correct = out[0], out[1], out[2]
+            sc = out[4].to(torch.float32) if scores else None
+        else:
+            if not 1 <= thr.size <= 32:
+                raise KnnError(KNN_EINVAL, f"{thr.size} thresholds outside [1, 32]")
+            top = float(thr[-1])
+            off, idx, dist = self.radius_neighbors_device(train, test, threshold=top, self_base=self_base,
+                                                          stream=stream, d=d)
+            pred, correct, sc = self.radius_vote_sweep_device(off, idx, dist, labels, num_classes, None, thr, weights,
+                                                              outlier_label, query_labels, scores, stream)
+            # count[r][q]: the entries of q's list within thr[r]
+            nq = off.numel() - 1
+            seg = torch.repeat_interleave(torch.arange(nq, device=idx.device), (off[1:] - off[:-1]))
+            t = torch.from_numpy(thr).to(idx.device)
+            count = torch.zeros((thr.size, nq), dtype=torch.int32, device=idx.device)
+            if idx.numel():
+                inside = (dist[None, :] <= t[:, None]).to(torch.int32)
+                count.index_add_(1, seg, inside)
+        return (pred, sc, count) if query_labels is None else (pred, sc, count, correct)
+
     def radius_regress_device(self, train, targets, test, radius=None, threshold=None, weights="uniform",
                               self_base=None, stream=None, d=None):
         """RadiusNeighborsRegressor.predict: the weighted mean of the targets of the train rows
@@ -1305,6 +1450,15 @@ def best_k(correct):
     if c.ndim != 1 or c.size == 0:
         raise KnnError(KNN_EINVAL, "correct must be a non-empty 1-D array")
     return int(np.argmax(c)) + 1  # argmax returns the first maximum
+
+
+def best_radius(correct):
+    """The index r a radius sweep's correct counts choose: the smallest index among those with the
+    most correct (the radii are non-decreasing, so it is the smallest such radius)."""
+    c = correct.cpu().numpy() if hasattr(correct, "cpu") else np.asarray(correct)
+    if c.ndim != 1 or c.size == 0:
+        raise KnnError(KNN_EINVAL, "correct must be a non-empty 1-D array")
+    return int(np.argmax(c))  # argmax returns the first maximum
 
 
 def best_k_error(err):

@@ -981,6 +981,113 @@ int* KNN_radius_loo(ArffData* train, float radius, int weights, int outlier_labe
     return radius_on_device0(train, train, radius, weights, outlier_label, true, outliers);
 }
 
+// the radius classifier of R non-decreasing radii on the first device (knn_amd.h "Radius sweep"),
+// staged as radius_on_device0.  Uniform: the count sweep alone, the queries in blocks of what the
+// library's workspace takes.  Weighted: count and fill once at the largest radius, the vote sweep
+// on those lists, and a count sweep for the rows with no neighbour.
+static int* radius_sweep_on_device0(ArffData* train, ArffData* test, const float* radii, int R, int weights,
+                                    int outlier_label, bool loo, long* outliers) {
+    const KnnFlatView& tr = train->flat();
+    const KnnFlatView& te = test->flat();
+    if (R < 1 || R > 32 || !radii) throwf("KNN_radius_sweep: %d radii outside [1, 32]", R);
+    for (int r = 0; r < R; r++)
+        if (!(radii[r] >= 0.0f) || (r && radii[r] < radii[r - 1]))
+            throwf("KNN_radius_sweep: the radii must be >= 0 and non-decreasing");
+    if (tr.d != te.d) throwf("KNN_radius_sweep: train has %d features, test has %d", tr.d, te.d);
+    const int64_t nq = te.n;
+    const int C = (int)train->num_classes();
+    int* pred = (int*)std::malloc(sizeof(int) * (size_t)R * (size_t)(nq > 0 ? nq : 1));
+    if (!pred) throwf("KNN_radius_sweep: out of memory");
+    std::vector<int64_t> out((size_t)R, 0);
+    std::string why;
+    knn_status s = KNN_OK;
+    try {
+        std::vector<knn_ctx*>& cs = contexts();
+        knn_ctx* c = cs[0];
+        std::lock_guard<std::mutex> busy(*devices().busy[0]);
+        // the reported distance is squared under the Euclidean metric (one binary32 product)
+        std::vector<float> thr((size_t)R);
+        for (int r = 0; r < R; r++) thr[r] = knn_get_metric(c) == KNN_METRIC_SQEUCLIDEAN ? radii[r] * radii[r] : radii[r];
+        const int dev = knn_ctx_device(c);
+        hipStream_t st = (hipStream_t)knn_ctx_stream(c);
+        knn_dataset htr{tr.feat.data(), tr.labels.data(), tr.n, tr.d, tr.ld, KNN_F32}, dtr{}, dte{};
+        s = knn_set_generation(c, tr.uid);
+        if (s == KNN_OK) s = knn_ctx_train_device(c, &htr, &dtr);
+        DevMem dq(dev, loo ? 0 : sizeof(float) * (size_t)te.ld * (size_t)nq);
+        DevMem dpred(dev, sizeof(int32_t) * (size_t)R * (size_t)nq), dout(dev, sizeof(int64_t) * (size_t)R);
+        if (s == KNN_OK && (!dq.p || !dpred.p || !dout.p)) throwf("KNN_radius_sweep: device allocation failed");
+        if (s == KNN_OK) {
+            if (loo) {
+                dte = dtr;
+                dte.labels = nullptr;
+            } else {
+                if (hipMemcpyAsync(dq.p, te.feat.data(), sizeof(float) * (size_t)te.ld * (size_t)nq, hipMemcpyHostToDevice,
+                                   st) != hipSuccess)
+                    throwf("KNN_radius_sweep: upload failed");
+                dte = knn_dataset{dq.p, nullptr, nq, te.d, te.ld, KNN_F32};
+            }
+            if (hipMemsetAsync(dout.p, 0, sizeof(int64_t) * (size_t)R, st) != hipSuccess)
+                throwf("KNN_radius_sweep: memset failed");
+            const bool uniform = weights == KNN_W_UNIFORM;
+            // the count sweep, block by block: pred and outliers (uniform), or outliers alone
+            const int64_t block = std::max<int64_t>(1, knn_radius_sweep_max_queries(c, R, uniform ? C : 0));
+            for (int64_t q0 = 0; s == KNN_OK && q0 < nq; q0 += block) {
+                knn_dataset tq = dte;
+                tq.feat = (const char*)dte.feat + sizeof(float) * (size_t)dte.ld * (size_t)q0;
+                tq.n = std::min(block, nq - q0);
+                s = knn_radius_sweep_count_device(c, &dtr, &tq, thr.data(), R, uniform ? C : 0, loo ? q0 : -1,
+                                                  outlier_label, nullptr, nq, nullptr, nullptr,
+                                                  uniform ? (int32_t*)dpred.p + q0 : nullptr, nullptr, (int64_t*)dout.p,
+                                                  st);
+            }
+            if (s == KNN_OK && !uniform) {
+                const int64_t self_base = loo ? 0 : -1;
+                DevMem doff(dev, sizeof(int64_t) * (size_t)(nq + 1));
+                if (!doff.p) throwf("KNN_radius_sweep: device allocation failed");
+                s = knn_radius_count_device(c, &dtr, &dte, thr[R - 1], 0, self_base, outlier_label, nullptr, nullptr,
+                                            nullptr, nullptr, nullptr, (int64_t*)doff.p, st);
+                int64_t total = 0;
+                if (s == KNN_OK && nq > 0 &&
+                    hipMemcpy(&total, (int64_t*)doff.p + nq, sizeof(total), hipMemcpyDeviceToHost) != hipSuccess)
+                    throwf("KNN_radius_sweep: download failed");
+                DevMem didx(dev, sizeof(int32_t) * (size_t)total), ddist(dev, sizeof(float) * (size_t)total);
+                if (s == KNN_OK && (!didx.p || !ddist.p)) throwf("KNN_radius_sweep: device allocation failed");
+                if (s == KNN_OK)
+                    s = knn_radius_fill_device(c, &dtr, &dte, thr[R - 1], self_base, (const int64_t*)doff.p,
+                                               (int32_t*)didx.p, (float*)ddist.p, st);
+                if (s == KNN_OK)
+                    s = knn_radius_vote_sweep_device(c, nq, tr.n, (const int64_t*)doff.p, (const int32_t*)didx.p,
+                                                     (const float*)ddist.p, dtr.labels, C, weights, thr.data(), R,
+                                                     outlier_label, nullptr, nq, (int32_t*)dpred.p, nullptr, nullptr, st);
+            }
+            if (s == KNN_OK && nq > 0 &&
+                (hipMemcpy(pred, dpred.p, sizeof(int32_t) * (size_t)R * (size_t)nq, hipMemcpyDeviceToHost) != hipSuccess ||
+                 hipMemcpy(out.data(), dout.p, sizeof(int64_t) * (size_t)R, hipMemcpyDeviceToHost) != hipSuccess))
+                throwf("KNN_radius_sweep: download failed");
+        }
+        if (s != KNN_OK) why = knn_last_error(c);
+    } catch (...) {
+        std::free(pred);
+        throw;
+    }
+    if (s != KNN_OK) {
+        std::free(pred);
+        throwf("KNN_radius_sweep: %s (status %d)", why.c_str(), (int)s);
+    }
+    for (int r = 0; outliers && r < R; r++) outliers[r] = (long)out[(size_t)r];
+    return pred;
+}
+
+int* KNN_radius_sweep(ArffData* train, ArffData* test, const float* radii, int n_radii, int weights, int outlier_label,
+                      long* outliers) {
+    return radius_sweep_on_device0(train, test, radii, n_radii, weights, outlier_label, false, outliers);
+}
+
+int* KNN_radius_sweep_loo(ArffData* train, const float* radii, int n_radii, int weights, int outlier_label,
+                          long* outliers) {
+    return radius_sweep_on_device0(train, train, radii, n_radii, weights, outlier_label, true, outliers);
+}
+
 void* KNN(void* params) {
     arguments* a = static_cast<arguments*>(params);
     predict_range(a->train, a->test, a->k, a->start, a->end, predictions + a->start);

@@ -129,6 +129,8 @@ struct knn_ctx {
     // a segmented pass; class counts [nq][C] / scores [nq][C] the caller did not ask for but the
     // vote needs
     DBuf rd_segcnt, rd_base, rd_cc, rd_scores;
+    // the radius sweep's bucket histograms: hist [nq][R + 1] | chist [nq][R + 1][C], int32
+    DBuf rd_sweep;
     // the pass rd_segcnt's counts came from: a fill whose pass has the same key takes them as they
     // are instead of counting again.  (Rows rewritten in place in between are caught where stale
     // counts would matter: the fill checks every (segment, query) count against its own.)
@@ -223,7 +225,7 @@ knn_status fail(knn_ctx* c, knn_status s, const char* fmt, ...) {
 // 3.44 -> 3.56 ms per step, A 22.58 -> 22.73 (scripts/event_overhead.py, profiles/r04n).
 static bool hot_stage(const char* n) {
     static const char* const hot[] = {"gemm_filter", "rescore", "direct_tile", "metric_tile", "exact_scan", "merge_vote",
-                                      "exchange", "radius_count", "radius_fill"};
+                                      "exchange", "radius_count", "radius_fill", "radius_sweep"};
     for (const char* h : hot)
         if (!strcmp(n, h)) return true;
     return false;
@@ -2372,6 +2374,177 @@ knn_status knn_radius_regress_device(knn_ctx* c, int64_t nq, int64_t n_train, co
     v.status = c->ctrl.as<int32_t>();
     stage_begin(c, st, "radius_regress");
     HIP_OR_FAIL(c, knn_launch_radius_regress(v, st));
+    stage_end(c, st);
+    return finish_call(c, st);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// Radius sweep (knn_amd.h "Radius sweep"): R thresholds in one distance pass
+// (k_radius_sweep_tile -> k_radius_sweep_finish), and the vote of every threshold on held lists
+// (k_radius_vote_sweep)
+// ---------------------------------------------------------------------------------
+namespace {
+
+// 1 <= R <= 32 thresholds, each in [0, FLT_MAX), non-decreasing
+knn_status sweep_thresholds_check(knn_ctx* c, const char* what, const float* thr, int32_t R) {
+    if (R < 1 || R > KNN_RADIUS_SWEEP_MAX_R)
+        return fail(c, KNN_EINVAL, "%s: R=%d thresholds outside [1, %d]", what, R, KNN_RADIUS_SWEEP_MAX_R);
+    if (!thr) return fail(c, KNN_EINVAL, "%s: thresholds is NULL", what);
+    for (int r = 0; r < R; r++) {
+        if (!(thr[r] >= 0.0f && thr[r] < FLT_MAX))
+            return fail(c, KNN_EINVAL, "%s: threshold %d must be in [0, FLT_MAX)", what, r);
+        if (r && thr[r] < thr[r - 1])
+            return fail(c, KNN_EINVAL, "%s: thresholds %d and %d descend (the list must be non-decreasing)", what,
+                        r - 1, r);
+    }
+    return KNN_OK;
+}
+
+// the bytes of workspace one call may take: what ws_queries queries of the GEMM path's candidate
+// workspace take (a quarter of the free HBM at knn_create)
+size_t workspace_budget(const knn_ctx* c) {
+    return (size_t)std::max<int64_t>(1, c->ws_queries) * (12 * 64 * (size_t)KNN_RESCORE_CAPW + 64);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t knn_radius_sweep_max_queries(const knn_ctx* c, int32_t R, int32_t C) {
+    if (!c || R < 1 || R > KNN_RADIUS_SWEEP_MAX_R || C < 0 || C > 16384) return 0;
+    return (int64_t)(workspace_budget(c) / ((size_t)(R + 1) * (size_t)(1 + C) * sizeof(int32_t)));
+}
+
+knn_status knn_radius_sweep_count_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te,
+                                         const float* thresholds, int32_t R, int32_t C, int64_t self_base,
+                                         int32_t outlier_label, const int32_t* d_query_labels, int64_t ld_out,
+                                         int32_t* d_count, int32_t* d_class_counts, int32_t* d_pred,
+                                         int64_t* d_correct, int64_t* d_outliers, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    reset_stats(c);
+    const bool classes = d_class_counts || d_pred || d_correct;
+    knn_status s;
+    if ((s = sweep_thresholds_check(c, "radius sweep", thresholds, R)) != KNN_OK) return s;
+    if ((s = radius_check(c, tr, te, thresholds[R - 1], self_base, classes)) != KNN_OK) return s;
+    if (classes && (C < 1 || C > 16384)) return fail(c, KNN_EINVAL, "num_classes=%d outside [1, 16384]", C);
+    if (d_correct && !d_query_labels) return fail(c, KNN_EINVAL, "radius sweep: correct needs the query labels");
+    const int64_t nq = te->n;
+    if (ld_out < nq) return fail(c, KNN_EINVAL, "radius sweep: ld_out=%lld < nq=%lld", (long long)ld_out, (long long)nq);
+    if (!d_count && !classes && !d_outliers)
+        return fail(c, KNN_EINVAL, "radius sweep: count, class_counts, pred, correct and outliers are all NULL");
+    if (nq == 0) return KNN_OK;
+    // hist [nq][R + 1] | chist [nq][R + 1][C]
+    const size_t per_q = (size_t)(R + 1) * (size_t)(1 + (classes ? C : 0)) * sizeof(int32_t);
+    const int64_t fit = knn_radius_sweep_max_queries(c, R, classes ? C : 0);
+    if (nq > fit)
+        return fail(c, KNN_ERANGE,
+                    "radius sweep: the histograms of nq=%lld queries (R=%d, num_classes=%d) exceed the workspace "
+                    "budget; at most nq=%lld queries fit in one call",
+                    (long long)nq, R, classes ? C : 0, (long long)fit);
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    HIP_OR_FAIL(c, c->rd_sweep.ensure(per_q * (size_t)nq));
+
+    // the form a single-threshold pass of this shape takes (knn_radius_policy), with its segments
+    const int form = radius_policy(c->metric, tr->d, tr->n, nq, c->algo);
+    const RadiusTileArgs ta = radius_args(c, tr, te, thresholds[R - 1], self_base, classes ? C : 0, form);
+    RadiusSweepArgs a{};
+    a.train = tr->feat; a.labels = tr->labels; a.nt = tr->n; a.ld_t = tr->ld;
+    a.test = te->feat; a.ld_q = te->ld; a.nq = nq;
+    a.d = tr->d; a.C = classes ? C : 0; a.elem = tr->dtype;
+    a.self_base = self_base;
+    a.classes = classes ? 1 : 0; a.R = R;
+    std::copy(thresholds, thresholds + R, a.thr);
+    a.nseg = ta.nseg; a.seg_len = ta.seg_len;
+    a.hist = c->rd_sweep.as<int32_t>();
+    a.chist = classes ? a.hist + (size_t)nq * (R + 1) : nullptr;
+    a.status = c->ctrl.as<int32_t>();
+    RadiusSweepGemmArgs g{};
+    if (form) {
+        // k_radius_gemm's operands (radius_prep: cached like a single-threshold pass's) and certificate
+        RadiusGemmArgs r{};
+        if ((s = radius_prep(c, tr, te, ta, st, &r)) != KNN_OK) return s;
+        g.tblk = r.tblk; g.qop = r.qop; g.qnorm = r.qnorm; g.qstat = r.qstat; g.tsmax = r.tsmax;
+        g.train = r.train; g.labels = r.labels; g.nt = r.nt; g.ld_t = r.ld_t;
+        g.test = r.test; g.ld_q = r.ld_q; g.nq = r.nq;
+        g.d = r.d; g.C = a.C; g.elem = r.elem;
+        g.seg_len = r.seg_len; g.nseg = r.nseg;
+        g.self_base = self_base; g.coef = r.coef; g.eta = r.eta;
+        g.classes = a.classes; g.R = R;
+        g.hist = a.hist; g.chist = a.chist; g.status = r.status; g.exact_cnt = r.exact_cnt;
+        std::copy(thresholds, thresholds + R, g.thr);
+        a.gate = a.status;
+    }
+
+    stage_begin(c, st, "radius_sweep");
+    HIP_OR_FAIL(c, hipMemsetAsync(c->rd_sweep.p, 0, per_q * (size_t)nq, st));
+    if (form) HIP_OR_FAIL(c, knn_launch_radius_sweep_gemm(g, st));
+    HIP_OR_FAIL(c, knn_launch_radius_sweep_tile(a, c->metric, st));
+    stage_end(c, st);
+
+    RadiusSweepFinishArgs f{};
+    f.hist = a.hist; f.chist = a.chist; f.nq = nq; f.R = R; f.C = a.C; f.classes = a.classes;
+    f.ld_out = ld_out; f.outlier = outlier_label; f.qlabels = d_query_labels;
+    f.count = d_count; f.class_counts = d_class_counts; f.pred = d_pred;
+    f.correct = reinterpret_cast<unsigned long long*>(d_correct);
+    f.outliers = reinterpret_cast<unsigned long long*>(d_outliers);
+    stage_begin(c, st, "radius_sweep_finish");
+    HIP_OR_FAIL(c, knn_launch_radius_sweep_finish(f, st));
+    stage_end(c, st);
+    return radius_finish(c, st, form);
+}
+
+knn_status knn_radius_vote_sweep_device(knn_ctx* c, int64_t nq, int64_t n_train, const int64_t* d_offsets,
+                                        const int32_t* d_idx, const float* d_dist, const int32_t* d_train_labels,
+                                        int32_t C, int32_t weights, const float* thresholds, int32_t R,
+                                        int32_t outlier_label, const int32_t* d_query_labels, int64_t ld_out,
+                                        int32_t* d_pred, int64_t* d_correct, float* d_scores, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    reset_stats_keep_radius(c);
+    knn_status s;
+    if (nq < 0 || n_train < 0 || n_train > 0x7fffffffLL || C < 1 || C > 16384)
+        return fail(c, KNN_EINVAL, "radius vote sweep: bad nq=%lld n_train=%lld C=%d", (long long)nq,
+                    (long long)n_train, C);
+    if ((s = weights_check(c, "radius vote sweep", weights)) != KNN_OK) return s;
+    if ((s = sweep_thresholds_check(c, "radius vote sweep", thresholds, R)) != KNN_OK) return s;
+    if (ld_out < nq)
+        return fail(c, KNN_EINVAL, "radius vote sweep: ld_out=%lld < nq=%lld", (long long)ld_out, (long long)nq);
+    if (!d_pred && !d_correct && !d_scores)
+        return fail(c, KNN_EINVAL, "radius vote sweep: pred, correct and scores are all NULL");
+    if (d_correct && !d_query_labels)
+        return fail(c, KNN_EINVAL, "radius vote sweep: correct needs the query labels");
+    if (nq == 0) return KNN_OK;
+    // (the threshold filter reads the distances under every kind of weights)
+    if (!d_offsets || !d_idx || !d_dist || !d_train_labels)
+        return fail(c, KNN_EINVAL, "radius vote sweep: d_offsets / d_idx / d_dist / d_train_labels is NULL");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    RadiusVoteSweepArgs v{};
+    v.offsets = d_offsets; v.idx = d_idx; v.dist = d_dist; v.nq = nq; v.n_train = n_train;
+    v.labels = d_train_labels; v.C = C; v.weights = kernel_weights(c, weights); v.outlier = outlier_label;
+    v.R = R; v.ld_out = ld_out;
+    std::copy(thresholds, thresholds + R, v.thr);
+    v.qlabels = d_query_labels; v.pred = d_pred; v.correct = reinterpret_cast<unsigned long long*>(d_correct);
+    v.scores = d_scores;
+    stage_begin(c, st, "radius_vote_sweep");
+    if (!v.scores) {
+        // (workspace of the caller's pitch: the kernel has one ld_out for pred and scores)
+        HIP_OR_FAIL(c, c->rd_scores.ensure(sizeof(float) * (size_t)R * (size_t)ld_out * (size_t)C));
+        v.scores = c->rd_scores.as<float>();
+        HIP_OR_FAIL(c, hipMemsetAsync(v.scores, 0, sizeof(float) * (size_t)R * (size_t)ld_out * (size_t)C, st));
+    } else {
+        // the caller's [R][ld_out][C]: only this call's nq rows of every r are zeroed
+        HIP_OR_FAIL(c, hipMemset2DAsync(v.scores, sizeof(float) * (size_t)ld_out * (size_t)C, 0,
+                                        sizeof(float) * (size_t)nq * (size_t)C, (size_t)R, st));
+    }
+    v.status = c->ctrl.as<int32_t>();
+    HIP_OR_FAIL(c, knn_launch_radius_vote_sweep(v, st));
     stage_end(c, st);
     return finish_call(c, st);
 }

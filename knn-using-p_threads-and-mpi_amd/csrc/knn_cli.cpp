@@ -2,7 +2,7 @@
 //
 //   knn_cli train.arff test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]]
 //           [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress]
-//           [--radius=R [--outlier=L]]
+//           [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]]
 //
 // Same positional arguments as ./main (main.cpp:114-122; k parsed with strtol) plus the
 // optional worker count of ./multi-thread (multi-thread.cpp:135-143), here the number of
@@ -29,6 +29,11 @@
 // radius classifier's line with the accuracy (an outlier counts as wrong unless L is the row's
 // label) and the number of rows with no neighbour.  With --regress, with plain --sweep, or with an
 // R that is not a number >= 0, it prints a usage error and exits 1.
+// --radii=R1,R2,...: up to 32 radii in one distance pass (KNN_radius_sweep / KNN_radius_sweep_loo):
+// the radius classifier's line once per radius, in ascending order.  Composes like --radius=; with
+// --regress, with --radius=, with plain --sweep, with more than 32 values or a value that is not a
+// number >= 0, it prints a usage error and exits 1.
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -48,6 +53,7 @@ static int run(int argc, char* argv[]) {
     bool sweep = false, loo = false, regress = false;
     int weights = 0;  // knn_weight
     const char* radius_arg = nullptr;
+    const char* radii_arg = nullptr;
     int outlier = -1;
     for (int i = 0; i < argc; i++) {
         if (!std::strncmp(argv[i], "--shard=", 8)) setenv("KNN_AMD_SHARD", argv[i] + 8, 1);
@@ -55,6 +61,7 @@ static int run(int argc, char* argv[]) {
         else if (!std::strcmp(argv[i], "--sweep=loo")) sweep = loo = true;
         else if (!std::strcmp(argv[i], "--regress")) regress = true;
         else if (!std::strncmp(argv[i], "--radius=", 9)) radius_arg = argv[i] + 9;
+        else if (!std::strncmp(argv[i], "--radii=", 8)) radii_arg = argv[i] + 8;
         else if (!std::strncmp(argv[i], "--outlier=", 10)) outlier = (int)std::strtol(argv[i] + 10, NULL, 10);
         else if (!std::strcmp(argv[i], "--weights=uniform")) weights = 0;
         else if (!std::strcmp(argv[i], "--weights=distance")) weights = 1;
@@ -73,7 +80,7 @@ static int run(int argc, char* argv[]) {
     }
     argc = n;
     if (argc != 4 && argc != 5) {
-        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress] [--radius=R [--outlier=L]]"
+        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress] [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]]"
                   << std::endl;
         std::exit(0);
     }
@@ -89,6 +96,25 @@ static int run(int argc, char* argv[]) {
             std::exit(1);
         }
     }
+    std::vector<float> radii;
+    if (radii_arg) {
+        bool ok = !radius_arg && !regress && !(sweep && !loo);
+        for (const char* p = radii_arg; ok;) {
+            char* end = nullptr;
+            const float r = std::strtof(p, &end);
+            ok = end != p && (*end == ',' || *end == '\0') && r >= 0.0f && radii.size() < 32;  // (NaN fails >=)
+            if (ok) radii.push_back(r);
+            if (!ok || *end == '\0') break;
+            p = end + 1;
+        }
+        if (!ok) {
+            std::cerr << "usage: --radii=R1,R2,... needs 1 to 32 numbers >= 0 and does not combine with --radius=, "
+                         "--regress or plain --sweep"
+                      << std::endl;
+            std::exit(1);
+        }
+        std::sort(radii.begin(), radii.end());
+    }
     if (argc == 5) setenv("KNN_AMD_DEVICES", argv[4], 1);
 
     ArffParser parserTrain(argv[1]);
@@ -98,6 +124,35 @@ static int run(int argc, char* argv[]) {
     knn_amd_init();
 
     struct timespec start, end;
+    if (radii_arg) {
+        const int R = (int)radii.size();
+        std::vector<long> outliers((size_t)R, 0);
+        clock_gettime(CLOCK_MONOTONIC_RAW, &start);
+        int* all = loo ? KNN_radius_sweep_loo(train, radii.data(), R, weights, outlier, outliers.data())
+                       : KNN_radius_sweep(train, test, radii.data(), R, weights, outlier, outliers.data());
+        clock_gettime(CLOCK_MONOTONIC_RAW, &end);
+        uint64_t diff = (1000000000L * (end.tv_sec - start.tv_sec) + end.tv_nsec - start.tv_nsec) / 1e6;
+        const long nq = test->num_instances();
+        const int last = test->num_attributes() - 1;
+        for (int r = 0; r < R; r++) {
+            int ok = 0;  // (no confusion matrix: an outlier label is no class)
+            for (long q = 0; q < nq; q++)
+                ok += all[(size_t)r * nq + q] == (int)(int32)(*test->get_instance((int)q)->get(last));
+            printf("The radius-%g classifier for %lu test instances on %lu train instances required %llu ms CPU time. Accuracy was %.4f, %ld outliers\n",
+                   (double)radii[r], (unsigned long)nq, (unsigned long)train->num_instances(),
+                   (long long unsigned int)diff, ok / (float)nq, outliers[r]);
+        }
+        if (const char* p = std::getenv("KNN_CLI_PRED_OUT")) {  // test hook: one line of n predictions per radius
+            FILE* f = std::fopen(p, "w");
+            for (int r = 0; r < R; r++) {
+                for (long q = 0; q < nq; q++) std::fprintf(f, q ? " %d" : "%d", all[(size_t)r * nq + q]);
+                std::fprintf(f, "\n");
+            }
+            std::fclose(f);
+        }
+        std::free(all);
+        return 0;
+    }
     if (radius_arg) {
         long outliers = 0;
         clock_gettime(CLOCK_MONOTONIC_RAW, &start);

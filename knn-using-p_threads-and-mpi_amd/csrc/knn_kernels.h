@@ -309,6 +309,68 @@ size_t knn_radius_gemm_tile_bytes(int d);
 hipError_t knn_radius_gemm_units(int elem, int d, int* queries_per_unit, int* units_per_cu);
 hipError_t knn_launch_radius_gemm(RadiusGemmArgs a, bool fill, hipStream_t st);
 
+// The radius sweep (knn_radius_sweep.hip; knn_amd.h "Radius sweep"): R <= 32 non-decreasing
+// thresholds in one distance pass.  k_radius_sweep_tile<M, E> has k_radius_tile's block shape,
+// geometry and segments; a pair counts into its bucket (the smallest r with D <= thr[r]) of
+// hist [nq][R + 1] and, with classes, of chist [nq][R + 1][C] -- both zeroed by the caller, added
+// to with integer atomics by every train segment.  The thresholds travel by value.
+#define KNN_RADIUS_SWEEP_MAX_R 32
+struct RadiusSweepArgs {
+    const void* train; const int32_t* labels; int64_t nt; int ld_t;
+    const void* test; int ld_q; int64_t nq;
+    int d; int C; int elem;
+    int64_t seg_len; int nseg; int n_qblocks;
+    int dc; int stride;        // set by the launcher (knn_direct_tile_geom)
+    int64_t self_base;
+    int classes; int R;
+    int32_t* hist; int32_t* chist;
+    int32_t* status;
+    // optional: a status word; the kernel runs only when it says KNN_STATUS_GEMM_UNSAFE (the pass
+    // behind k_radius_sweep_gemm, which returns at once in that case)
+    const int32_t* gate;
+    float thr[KNN_RADIUS_SWEEP_MAX_R];  // [R..31]: set by the launcher to thr[R - 1]
+};
+// k_radius_sweep_gemm<RB, E>: the MFMA-filtered form of the sweep pass -- RadiusGemmArgs' operands
+// and certificate (squared Euclidean, d in {64, 128, 256}; segments are multiples of 64 rows), the
+// same histograms.
+struct RadiusSweepGemmArgs {
+    const void* tblk; const void* qop; const float* qnorm; const float2* qstat; const float4* tsmax;
+    const void* train; const int32_t* labels; int64_t nt; int ld_t;
+    const void* test; int ld_q; int64_t nq;
+    int d; int C; int elem;
+    int64_t seg_len; int nseg; int n_qblocks;  // n_qblocks: set by the launcher
+    int64_t self_base;
+    float coef; float eta;     // certificate_fused
+    int classes; int R;
+    int32_t* hist; int32_t* chist;
+    int32_t* status;           // a set KNN_STATUS_GEMM_UNSAFE bit skips the pass
+    unsigned long long* exact_cnt;  // optional (profile = 2): += the pairs given the exact evaluation
+    float thr[KNN_RADIUS_SWEEP_MAX_R];  // [R..31]: set by the launcher to thr[R - 1]
+};
+hipError_t knn_launch_radius_sweep_gemm(RadiusSweepGemmArgs a, hipStream_t st);
+hipError_t knn_launch_radius_sweep_tile(RadiusSweepArgs a, int metric, hipStream_t st);
+// k_radius_sweep_finish: the prefix over buckets.  count / pred [R][ld_out], class_counts
+// [R][ld_out][C] (each optional; the class outputs need classes != 0); correct / outliers [R] are
+// ADDED to.  chist is overwritten with its own prefix.
+struct RadiusSweepFinishArgs {
+    const int32_t* hist; int32_t* chist; int64_t nq; int R; int C; int classes;
+    int64_t ld_out; int32_t outlier; const int32_t* qlabels;
+    int32_t* count; int32_t* class_counts; int32_t* pred;
+    unsigned long long* correct; unsigned long long* outliers;
+};
+hipError_t knn_launch_radius_sweep_finish(const RadiusSweepFinishArgs& a, hipStream_t st);
+// k_radius_vote_sweep: k_radius_vote on the sub-lists dist <= thr[r] of CSR lists (dist needed for
+// every kind).  scores [R][ld_out][C] is needed and zeroed by the caller; pred [R][ld_out] and
+// correct [R] (added to; needs qlabels) are optional.
+struct RadiusVoteSweepArgs {
+    const int64_t* offsets; const int32_t* idx; const float* dist; int64_t nq; int64_t n_train;
+    const int32_t* labels; int C; int weights; int32_t outlier; int R; int64_t ld_out;
+    const int32_t* qlabels; int32_t* pred; unsigned long long* correct; float* scores;
+    int32_t* status;
+    float thr[KNN_RADIUS_SWEEP_MAX_R];
+};
+hipError_t knn_launch_radius_vote_sweep(const RadiusVoteSweepArgs& a, hipStream_t st);
+
 struct GenerateArgs {
     void* out; int32_t* labels; int64_t row0; int64_t n; int d; int ld;
     int bf16_out; int kind; uint64_t seed; uint32_t stream; int C;

@@ -24,35 +24,7 @@
 #include "knn_device.h"
 
 #pragma clang fp contract(off)
-// one feature of metric M: the accumulator after (q_i, t_i)
-template <int M>
-__device__ __forceinline__ float radius_step(float acc, float q, float t) {
-    const float df = q - t;
-    if constexpr (M == METRIC_SQEUCLIDEAN)
-        return acc + df * df;
-    else if constexpr (M == METRIC_MANHATTAN)
-        return acc + __builtin_fabsf(df);
-    else
-        return __builtin_fmaxf(acc, __builtin_fabsf(df));
-}
-
-// Four consecutive query elements as fp32 through the constant address space.  The query rows are
-// wave-uniform operands and are only read, but this kernel stores to global memory inside its tile
-// loop (the lists, the class-count atomics), so the compiler can no longer prove that a plain load
-// of them is not clobbered and emits a vector global_load per query and group (measured: the count
-// pass at 30.6 ms against k_direct_tile's 27.1 on 262,144 x 64 x 16,384).  A constant-address-space
-// load of a uniform address is the s_load_dwordx4 that k_metric_tile gets by itself.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float4 load4q(const float* p) {
-    const f32x4 v = *(const __attribute__((address_space(4))) f32x4*)(uintptr_t)p;
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ float4 load4q(const bf16_t* p) {
-    const u32x2 v = *(const __attribute__((address_space(4))) u32x2*)(uintptr_t)p;
-    return make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xffff0000u),
-                       __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xffff0000u));
-}
+#include "knn_radius_dev.h"  // radius_step<M>, load4q
 
 // set bits of m below this lane
 __device__ __forceinline__ int lanes_below(u64 m) {

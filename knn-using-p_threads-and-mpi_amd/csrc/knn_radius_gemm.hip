@@ -26,38 +26,8 @@
 
 #include "knn_device.h"
 
-// tile image in LDS: the fused filter's (rows padded to RB + 16 bytes, then the header: 64 norms and
-// the tile's statistics), two buffers
-template <int RB>
-struct RadiusGemmTile {
-    static constexpr int STRIDE = RB + 16;           // LDS bytes per tile row
-    static constexpr int SPR = RB / 16;              // 16-byte slots per operand row
-    static constexpr int HDR = 64 * STRIDE;          // LDS offset of the header
-    static constexpr int HS = 64 / 4 + 1;            // header slots: 64 fp32 norms + the statistics
-    static constexpr int NSL = 64 * SPR + HS;        // 16-byte slots of one tile block
-    static constexpr int TILE = HDR + 16 * HS;       // LDS bytes per buffer
-    static constexpr int64_t TB = 64 * (int64_t)RB + 16 * HS;  // bytes of one tile block in the train operand
-};
-
 #pragma clang fp contract(off)
-// D of k_direct_tile / k_radius_tile for one pair, from the caller's rows: acc = acc + (q_i - t_i)
-// (q_i - t_i), i ascending, one rounding per operation (radius_step<SQEUCLIDEAN>, knn_radius.hip)
-template <typename E>
-__device__ __forceinline__ float radius_exact(const E* __restrict__ q, const E* __restrict__ t, int d) {
-    float acc = 0.0f;
-    for (int i = 0; i < d; i += 4) {
-        const float4 a = load4(q + i), b = load4(t + i);
-        float df = a.x - b.x;
-        acc = acc + df * df;
-        df = a.y - b.y;
-        acc = acc + df * df;
-        df = a.z - b.z;
-        acc = acc + df * df;
-        df = a.w - b.w;
-        acc = acc + df * df;
-    }
-    return acc;
-}
+#include "knn_radius_dev.h"  // RadiusGemmTile<RB>, radius_exact<E>
 
 // ---------------------------------------------------------------------------------
 // k_radius_gemm<RB, E, FILL> (RadiusGemmArgs; RB = 2 d operand bytes per row, E the caller's
