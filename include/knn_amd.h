@@ -480,6 +480,65 @@ knn_status knn_regress_sweep(knn_ctx* ctx, const knn_dataset* train, const knn_d
                              double* out_sae);
 
 /*
+ * Local outlier factor: LOF (Breunig et al. 2000; sklearn's LocalOutlierFactor; no reference
+ * counterpart) of every train row for EVERY k in [k_lo, k_hi] from one top-(k_hi + 1) pass, and
+ * novelty scores of queries against the fitted tables.  A row's score reads its NEIGHBOURS' lists,
+ * so the scores are computed after the last pass, over all rows, in two gather rounds.
+ * Let T be the train set of n rows under the context's metric and Kr = k_hi - k_lo + 1.  Limits:
+ * 1 <= k_lo <= k_hi <= 255, anything else is KNN_EINVAL.
+ *   lists      row i's list is the k-sweep's leave-one-out list: the top-(k_hi + 1) list of row i
+ *              against T with row i removed -- the first entry equal to i, or the last entry when
+ *              none is (more than k_hi duplicates sit ahead of i at distance 0).  o_1 .. o_k are its
+ *              first k entries: exactly k neighbours, no tie extension at the k-distance (sklearn's
+ *              selection).
+ *   distance   delta(i, o_j) is binary32: sqrtf(D) of the reported squared distance under the
+ *              Euclidean metric (the correctly rounded sqrtf, as the weighted vote's), D itself
+ *              under Manhattan / Chebyshev.
+ *   k-distance kd_k(i) = delta(i, o_k).
+ *   reach sum  reach = fmaxf(kd_k(o_j), delta(i, o_j)) in binary32;
+ *              S_k(i) = sum over j = 1..k of (double)reach, binary64, ascending j, no tree and no
+ *              reordering.  (A neighbour whose own list has no k-th entry makes S_k(i) NaN.)
+ *   lrd        lrd_k(i) = 1.0 / (S_k(i) / (double)k + 1e-10), binary64, every operation correctly
+ *              rounded and none contracted.  The 1e-10 is sklearn's: rows inside a clump of more
+ *              than k duplicates stay finite.
+ *   LOF        L_k(i) = sum over j = 1..k of lrd_k(o_j), binary64, ascending j;
+ *              LOF_k(i) = (float)(L_k(i) / ((double)k * lrd_k(i))): one rounding to binary32.
+ *   novelty    a query's list is its plain top-k_hi list against T, nothing removed (a query equal
+ *              to a train row keeps that row at delta = 0); kd_k(o_j) and lrd_k(o_j) come from T's
+ *              fitted tables, the query's own lrd_k and LOF_k from the formulas above.
+ *   missing    a prefix that reaches a missing entry (-1; n - 1 < k) gives NaN for that k and
+ *              every larger k, and the call returns KNN_ERANGE (the outputs are written).
+ *   errors     on lists the caller holds, an index outside [0, n) that is not -1, or a non-missing
+ *              distance that is NaN or negative, gives KNN_EINVAL.  k_lof_compact checks every
+ *              entry before any gather: no kernel reads a table with an unchecked index.
+ *   determinism the same inputs give the same bits on every run and through every algorithm
+ *              (direct, MFMA filter, wide rows), however the pass loop cuts the rows.
+ * Outputs: d_kd fp32 [n][Kr] (kd[i][k - k_lo]), d_lrd fp64 [n][Kr], d_lof fp32 [Kr][n] (row
+ *   k - k_lo is LOF_k) are each optional, but not all may be NULL.
+ *
+ * knn_lof_fit_device: the vote-less top-(k_hi + 1) pass of train against itself (context-owned zero
+ *   labels, one class: train->labels is not read), the lists of ALL rows in context workspace or in
+ *   d_dist / d_idx ([n][k_hi + 1], before self-removal: what knn_lof_lists_device takes with
+ *   self_base = 0) when given, then k_lof_compact, k_lof_lrd, k_lof_score on the same stream and
+ *   one synchronisation for the last pass and the kernels.  k_hi + 1 may exceed n (KNN_ERANGE).
+ *   With profile = 1 the three stages are named "lof".
+ * knn_lof_score_device: novelty -- the plain top-k_hi pass of test against train, then d_lof_out
+ *   [Kr][nq] from the fitted d_kd / d_lrd of train (all three needed).
+ * knn_lof_lists_device: the kernels alone on lists [n][stride] the caller holds, the first kin
+ *   entries of a row: kin = k_hi + 1 with self_base = 0 (row i is removed from list i), kin = k_hi
+ *   with self_base < 0 (already removed).  List i belongs to row i of the same n rows the indices
+ *   name; merged train-shard lists qualify.
+ */
+knn_status knn_lof_fit_device(knn_ctx* ctx, const knn_dataset* train, int32_t k_lo, int32_t k_hi, float* d_kd,
+                              double* d_lrd, float* d_lof, float* d_dist, int32_t* d_idx, void* hip_stream);
+knn_status knn_lof_score_device(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test, int32_t k_lo,
+                                int32_t k_hi, const float* d_kd, const double* d_lrd, float* d_lof_out,
+                                void* hip_stream);
+knn_status knn_lof_lists_device(knn_ctx* ctx, int64_t n, int32_t kin, const int32_t* d_idx, const float* d_dist,
+                                int64_t stride, int64_t self_base, int32_t k_lo, int32_t k_hi, float* d_kd,
+                                double* d_lrd, float* d_lof, void* hip_stream);
+
+/*
  * Radius neighbours: "which train rows lie within thr of this query, how many, and what do they
  * vote?" (sklearn's radius_neighbors, RadiusNeighborsClassifier and RadiusNeighborsRegressor; no
  * reference counterpart).  A neighbourhood may hold any number of rows, or none, so the answer is a

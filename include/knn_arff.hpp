@@ -208,6 +208,12 @@ int* KNN_radius_sweep(ArffData* train, ArffData* test, const float* radii, int n
                       int outlier_label, long* outliers = nullptr);
 int* KNN_radius_sweep_loo(ArffData* train, const float* radii, int n_radii, int weights, int outlier_label,
                           long* outliers = nullptr);
+// Local outlier factor (knn_amd.h "Local outlier factor"; sklearn's LocalOutlierFactor): the LOF of
+// every train row for every k in [k_lo, k_hi], 1 <= k_lo <= k_hi <= 255, from one leave-one-out
+// top-(k_hi + 1) pass under the run's metric.  The last attribute is not read.  Returns malloc'd
+// float[(k_hi - k_lo + 1) * n] laid out [k_hi - k_lo + 1][n], row k - k_lo for k, caller frees.
+// Runs on the first device.
+float* KNN_lof(ArffData* train, int k_lo, int k_hi);
 // main.cpp:87 -- calloc'd int[C*C], C = dataset->num_classes(), row = true class.
 int* computeConfusionMatrix(int* predictions, ArffData* dataset);
 // main.cpp:102

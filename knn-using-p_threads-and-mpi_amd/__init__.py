@@ -27,6 +27,10 @@ Names follow the reference (srna99/KNN-using-p_threads-and-MPI):
   -- the prediction for every k <= K from the same lists, under the same weight kinds and metrics,
   with the per-k sums of squared and absolute errors (no reference counterpart; the rules are in
   ``knn_amd.h`` "Regression")
+* ``Context.lof_device / lof_fit_device / lof_lists_device``, ``LofModel.score_device``, ``lof_max``
+  and ``lof_outliers``: the local outlier factor of every train row for every k in [k_lo, k_hi]
+  from one leave-one-out top-k pass, and novelty scores of queries against the fitted tables (no
+  reference counterpart; the rules are in ``knn_amd.h`` "Local outlier factor")
 
 Features are fp32 or bf16.  Host bf16 arrays are numpy ``uint16`` holding bf16 bits
 (``to_bf16_bits`` / ``bf16_bits_to_f32``); device tensors are ``torch.bfloat16``.
@@ -138,6 +142,9 @@ def load_library(path=LIB_PATH):
         "knn_regress_sweep_device": (I32, [P, DS, DS, P, I32, I32, I64, P, P, P, P, P, P, P]),
         "knn_regress_device": (I32, [P, DS, DS, P, I32, I32, P, P, P, P]),
         "knn_regress_sweep": (I32, [P, DS, DS, P, I32, I32, I64, P, P, P, P]),
+        "knn_lof_fit_device": (I32, [P, DS, I32, I32, P, P, P, P, P, P]),
+        "knn_lof_score_device": (I32, [P, DS, DS, I32, I32, P, P, P, P]),
+        "knn_lof_lists_device": (I32, [P, I64, I32, P, P, I64, I64, I32, I32, P, P, P, P]),
         "knn_radius_count_device": (I32, [P, DS, DS, F, I32, I64, I32, P, P, P, P, P, P, P]),
         "knn_radius_fill_device": (I32, [P, DS, DS, F, I64, P, P, P, P]),
         "knn_radius_vote_device": (I32, [P, I64, I64, P, P, P, P, I32, I32, I32, P, P, P, P, P]),
@@ -788,6 +795,81 @@ class Context:
                                                _weight_kind(weights), _self_base(self_base),
                                                _ptr(qt), _ptr(pred_all), _ptr(sse), _ptr(sae)))
         return pred_all, sse, sae
+
+    # local outlier factor (knn_amd.h "Local outlier factor")
+    @staticmethod
+    def _lof_out(out, name, shape, dtype, device):
+        """An optional LOF output: True = allocate, a tensor = use it, False / None = none."""
+        import torch
+        if out is None or out is False:
+            return None
+        if out is True:
+            return torch.empty(shape, dtype=dtype, device=device)
+        return _check_tensor(out, name, dtype, shape[0] * shape[1])
+
+    def lof_fit_device(self, train, k_lo, k_hi=None, lof=False, dist=None, idx=None, stream=None, d=None, kd=None,
+                       lrd=None):
+        """Fit the local outlier factor on the train rows for every k in [k_lo, k_hi] (k_hi=None: the
+        single k = k_lo) from one leave-one-out top-(k_hi + 1) pass (knn_lof_fit_device).  Returns a
+        LofModel holding kd float32 [n][Kr], lrd float64 [n][Kr], the range and the train tensor;
+        with lof=True (or a float32 [Kr][n] tensor) also model.lof, the train rows' own scores.
+        dist / idx (optional, [n][k_hi + 1]) receive the lists before self-removal, which
+        lof_lists_device takes with self_base=0.  A KnnError(KNN_ERANGE) (k_hi > n - 1) is raised
+        after the outputs are written: pass tensors (kd, lrd, lof) to read them."""
+        import torch
+        k_hi = k_lo if k_hi is None else k_hi
+        Kr = max(k_hi - k_lo + 1, 0)
+        self._on_device(train)
+        self._note_train(train)
+        tr = _device_dataset(train, None, d)
+        _outputs(tr.n, k_hi + 1, None, dist, idx)
+        kd = self._lof_out(True if kd is None else kd, "kd", (tr.n, Kr), torch.float32, train.device)
+        lrd = self._lof_out(True if lrd is None else lrd, "lrd", (tr.n, Kr), torch.float64, train.device)
+        lof = self._lof_out(lof, "lof", (Kr, tr.n), torch.float32, train.device)
+        model = LofModel(self, train, d, k_lo, k_hi, kd, lrd, lof)
+        self._check(self.lib.knn_lof_fit_device(
+            self.h, ctypes.byref(tr), k_lo, k_hi, kd.data_ptr(), lrd.data_ptr(), _opt_ptr(lof), _opt_ptr(dist),
+            _opt_ptr(idx), self._stream(stream, train)))
+        return model
+
+    def lof_device(self, train, k_lo, k_hi=None, lof=None, dist=None, idx=None, stream=None, d=None):
+        """The local outlier factor of every train row for every k in [k_lo, k_hi] (k_hi=None: the
+        single k = k_lo): lof float32 [Kr][n], row k - k_lo for k (knn_lof_fit_device with the scores
+        alone).  ``lof_max`` takes the per-row maximum over the range, ``lof_outliers`` the rows
+        above a threshold.  lof, dist, idx as lof_fit_device."""
+        import torch
+        k_hi = k_lo if k_hi is None else k_hi
+        self._on_device(train)
+        self._note_train(train)
+        tr = _device_dataset(train, None, d)
+        _outputs(tr.n, k_hi + 1, None, dist, idx)
+        lof = self._lof_out(True if lof is None else lof, "lof", (max(k_hi - k_lo + 1, 0), tr.n), torch.float32,
+                            train.device)
+        self._check(self.lib.knn_lof_fit_device(
+            self.h, ctypes.byref(tr), k_lo, k_hi, None, None, lof.data_ptr(), _opt_ptr(dist), _opt_ptr(idx),
+            self._stream(stream, train)))
+        return lof
+
+    def lof_lists_device(self, idx, dist, k_lo, k_hi=None, self_base=None, kd=None, lrd=None, lof=True, stream=None):
+        """The LOF kernels alone (knn_lof_lists_device) on lists idx int32 / dist float32 [n][stride]
+        the caller holds, list i belonging to row i of the n rows the indices name: the first
+        k_hi + 1 entries of a row with self_base=0 (row i is removed from its list), the first k_hi
+        with self_base=None (already removed: loo_device's lists).  kd float32 [n][Kr] / lrd float64
+        [n][Kr] (True or a tensor) are filled when asked for.  Returns (lof float32 [Kr][n] or None,
+        kd or None, lrd or None)."""
+        import torch
+        k_hi = k_lo if k_hi is None else k_hi
+        Kr = max(k_hi - k_lo + 1, 0)
+        n, stride, kin, _ = self._lists_arg(idx, dist, k_hi + (0 if self_base is None else 1), self_base)
+        if dist is None:
+            raise KnnError(KNN_EINVAL, "lof: dist is needed")
+        kd = self._lof_out(kd, "kd", (n, Kr), torch.float32, idx.device)
+        lrd = self._lof_out(lrd, "lrd", (n, Kr), torch.float64, idx.device)
+        lof = self._lof_out(lof, "lof", (Kr, n), torch.float32, idx.device)
+        self._check(self.lib.knn_lof_lists_device(
+            self.h, n, kin, idx.data_ptr(), dist.data_ptr(), stride, _self_base(self_base), k_lo, k_hi, _opt_ptr(kd),
+            _opt_ptr(lrd), _opt_ptr(lof), self._stream(stream, idx)))
+        return lof, kd, lrd
 
     # radius neighbours (knn_amd.h "Radius neighbours")
     def _threshold(self, radius, threshold):
@@ -1471,6 +1553,54 @@ def best_k_error(err):
         raise KnnError(KNN_EINVAL, "best_k_error: every entry is NaN")
     at = np.flatnonzero(ok)
     return int(at[np.argmin(e[at])]) + 1  # argmin returns the first minimum
+
+
+class LofModel:
+    """A fitted local outlier factor (Context.lof_fit_device): the train tensor (and the d it was
+    read with), the range [k_lo, k_hi], kd float32 [n][Kr] and lrd float64 [n][Kr] of the train
+    rows, and lof float32 [Kr][n], their own scores, when the fit was asked for them."""
+
+    def __init__(self, ctx, train, d, k_lo, k_hi, kd, lrd, lof=None):
+        self.ctx, self.train, self.d = ctx, train, d
+        self.k_lo, self.k_hi = k_lo, k_hi
+        self.kd, self.lrd, self.lof = kd, lrd, lof
+
+    def score_device(self, test, lof=None, stream=None):
+        """Novelty scores of queries that are not train rows (knn_lof_score_device): lof float32
+        [Kr][nq] from each query's plain top-k_hi list against the train rows and the fitted
+        tables.  A query equal to a train row keeps that row, at distance 0."""
+        import torch
+        c = self.ctx
+        tr, te = c._datasets_arg(self.train, None, test, self.d)
+        Kr = max(self.k_hi - self.k_lo + 1, 0)
+        lof = c._lof_out(True if lof is None else lof, "lof", (Kr, te.n), torch.float32, test.device)
+        c._check(c.lib.knn_lof_score_device(
+            c.h, ctypes.byref(tr), ctypes.byref(te), self.k_lo, self.k_hi, self.kd.data_ptr(), self.lrd.data_ptr(),
+            lof.data_ptr(), c._stream(stream, test)))
+        return lof
+
+
+def lof_max(lof):
+    """The per-row maximum of lof [Kr][n] over the range of k (the LOF paper's rule for choosing
+    MinPts): [n], a tensor for a tensor, else a numpy array.  NaN entries (a k the row has too few
+    neighbours for) are ignored; a row that is NaN for every k stays NaN."""
+    if hasattr(lof, "cpu"):
+        import torch
+        nan = torch.isnan(lof)
+        m = torch.where(nan, torch.full_like(lof, float("-inf")), lof).max(dim=0).values
+        return torch.where(nan.all(dim=0), torch.full_like(m, float("nan")), m)
+    a = np.asarray(lof, np.float32)
+    return np.fmax.reduce(a, axis=0)
+
+
+def lof_outliers(scores, threshold=1.5):
+    """The row indices (ascending, int64) whose score [n] -- a row of lof, or lof_max -- is above
+    threshold; NaN scores are never above it."""
+    if hasattr(scores, "cpu"):
+        import torch
+        return torch.nonzero(scores > threshold).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        return np.flatnonzero(np.asarray(scores) > threshold).astype(np.int64)
 
 
 def _host_targets(t, name, n):

@@ -1088,6 +1088,43 @@ int* KNN_radius_sweep_loo(ArffData* train, const float* radii, int n_radii, int 
     return radius_sweep_on_device0(train, train, radii, n_radii, weights, outlier_label, true, outliers);
 }
 
+// the local outlier factor of the train rows on the first device (knn_amd.h "Local outlier
+// factor"), staged as radius_on_device0: the cached train upload, knn_lof_fit_device on the
+// context's stream, the [Kr][n] scores back
+float* KNN_lof(ArffData* train, int k_lo, int k_hi) {
+    const KnnFlatView& tr = train->flat();
+    if (k_lo < 1 || k_hi > 255 || k_lo > k_hi) throwf("KNN_lof: k_lo=%d, k_hi=%d outside 1 <= k_lo <= k_hi <= 255", k_lo, k_hi);
+    const size_t Kr = (size_t)(k_hi - k_lo + 1), n = (size_t)tr.n;
+    float* lof = (float*)std::malloc(sizeof(float) * Kr * (n > 0 ? n : 1));
+    if (!lof) throwf("KNN_lof: out of memory");
+    std::string why;
+    knn_status s = KNN_OK;
+    try {
+        std::vector<knn_ctx*>& cs = contexts();
+        knn_ctx* c = cs[0];
+        std::lock_guard<std::mutex> busy(*devices().busy[0]);
+        const int dev = knn_ctx_device(c);
+        hipStream_t st = (hipStream_t)knn_ctx_stream(c);
+        knn_dataset htr{tr.feat.data(), tr.labels.data(), tr.n, tr.d, tr.ld, KNN_F32}, dtr{};
+        s = knn_set_generation(c, tr.uid);
+        if (s == KNN_OK) s = knn_ctx_train_device(c, &htr, &dtr);
+        DevMem dlof(dev, sizeof(float) * Kr * n);
+        if (s == KNN_OK && !dlof.p) throwf("KNN_lof: device allocation failed");
+        if (s == KNN_OK) s = knn_lof_fit_device(c, &dtr, k_lo, k_hi, nullptr, nullptr, (float*)dlof.p, nullptr, nullptr, st);
+        if (s == KNN_OK && n > 0 && hipMemcpy(lof, dlof.p, sizeof(float) * Kr * n, hipMemcpyDeviceToHost) != hipSuccess)
+            throwf("KNN_lof: download failed");
+        if (s != KNN_OK) why = knn_last_error(c);
+    } catch (...) {
+        std::free(lof);
+        throw;
+    }
+    if (s != KNN_OK) {
+        std::free(lof);
+        throwf("KNN_lof: %s (status %d)", why.c_str(), (int)s);
+    }
+    return lof;
+}
+
 void* KNN(void* params) {
     arguments* a = static_cast<arguments*>(params);
     predict_range(a->train, a->test, a->k, a->start, a->end, predictions + a->start);

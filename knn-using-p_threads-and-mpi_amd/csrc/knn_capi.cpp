@@ -9,6 +9,8 @@
 //   radius neighbours (knn_radius_*): k_radius_tile (-> k_radius_scan / k_radius_argmax), every shape;
 //     squared Euclidean at d = 64 / 128 / 256 above knn_radius_policy's floors: k_row_norms x2 ->
 //     k_tn_rows x2 -> k_radius_gemm (k_radius_tile behind it, gated on unsafe norms)
+//   local outlier factor (knn_lof_*): the vote-less top-k pass of ALL rows, then k_lof_compact ->
+//     k_lof_lrd -> k_lof_score (two gather rounds over the rows' own tables)
 // Train-sharded runs use the same pipeline per shard with the vote
 // replaced by a packed (dist, global idx, label) neighbour list, then k_merge_vote.
 #include <hip/hip_runtime.h>
@@ -125,6 +127,11 @@ struct knn_ctx {
     // the vote-less pass runs with (the caller has no classes), and the host entry point's device
     // copy of the train targets
     DBuf rg_part, rg_zero, rg_targets;
+    // local outlier factor (knn_lof_*): the top-kin lists of ALL rows (the gathers need every row's
+    // list, so they are not the per-pass sw_idx / sw_dist), the self-removed lists cidx / delta
+    // [n][k_hi], and the tables kd [n][Kr] fp32 / lrd [n][Kr] fp64 the caller did not ask for;
+    // lof_qlrd: the queries' own lrd of a novelty call
+    DBuf lof_idx, lof_dist, lof_cidx, lof_delta, lof_kd, lof_lrd, lof_qlrd;
     // radius neighbours: per-(segment, query) counts [nseg][nq] and list bases [nseg][nq] int64 of
     // a segmented pass; class counts [nq][C] / scores [nq][C] the caller did not ask for but the
     // vote needs
@@ -1172,7 +1179,8 @@ void knn_destroy(knn_ctx* c) {
                     &c->h_dist, &c->h_idx, &c->sw_dist, &c->sw_idx, &c->sw_pred, &c->sw_qside, &c->sw_acc, &c->sw_scores,
                     &c->rg_part, &c->rg_zero, &c->rg_targets, &c->rd_segcnt, &c->rd_base, &c->rd_cc, &c->rd_scores,
                     &c->rm_tnorm, &c->rm_tmax, &c->rm_tsmax, &c->rm_tblk, &c->rm_tctrl, &c->rm_qnorm, &c->rm_qstat,
-                    &c->rm_qop, &c->rm_exact})
+                    &c->rm_qop, &c->rm_exact, &c->lof_idx, &c->lof_dist, &c->lof_cidx, &c->lof_delta, &c->lof_kd,
+                    &c->lof_lrd, &c->lof_qlrd})
         b->release();
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; i++) {
@@ -1491,7 +1499,9 @@ knn_status knn_merge_vote_append(knn_ctx* c, int32_t nsrc, int64_t nq, int32_t k
 // ---------------------------------------------------------------------------------
 namespace {
 
-enum ConsumerKind { VOTE_SWEEP = 0, VOTE_WEIGHTED = 1, REGRESS = 2 };
+// (LOF_SCORES runs its own kernels, lof_enqueue, behind a pass loop of its own: its scores need
+// every row's list; it is a kind here for list_check and its texts)
+enum ConsumerKind { VOTE_SWEEP = 0, VOTE_WEIGHTED = 1, REGRESS = 2, LOF_SCORES = 3 };
 
 // What a call asks of its consumer.  Per query every element is 4 bytes wide (int32 labels and
 // predictions for the class votes, float targets and predictions for regression) and every
@@ -1536,6 +1546,19 @@ const struct {
      "weighted vote: bad nq=%lld kin=%d stride=%lld C=%d", "weighted vote: d_idx / d_dist / d_train_labels is NULL"},
     {"regression", "pred_all, sse and sae are all NULL", "sse / sae need the query targets",
      "regression: bad nq=%lld kin=%d stride=%lld", "regression: d_idx / d_dist / d_train_targets is NULL"},
+    {"lof", "kd, lrd and lof are all NULL", "", "lof: bad n=%lld kin=%d stride=%lld", "lof: d_idx / d_dist is NULL"},
+};
+// the local outlier factor's other texts
+const struct {
+    const char *bad_range, *bad_kin, *bad_self, *no_tables, *bad_index, *bad_dist, *too_few;
+} kLofText = {
+    "lof: k_lo=%d, k_hi=%d outside 1 <= k_lo <= k_hi <= 255",
+    "lof: kin=%d is not k_hi=%d (+ 1 with self_base)",
+    "lof: self_base=%lld must be 0 (row i is list i's own row) or negative (none)",
+    "lof: the fitted kd / lrd tables and the output are needed",
+    "lof: a list index is outside [0, n)",
+    "lof: a neighbour distance is NaN or negative",
+    "lof: a list is shorter than k_hi (fewer than k_hi other rows have a finite distance): NaN from that k on",
 };
 
 // what every entry point of a consumer checks: the kind of weights, the outputs asked for (the
@@ -1644,8 +1667,21 @@ knn_status consumer_enqueue(knn_ctx* c, const ListConsumer& lc, const Lists& L, 
     switch (lc.kind) {
         case VOTE_SWEEP: return vote_sweep_enqueue(c, lc, L, C, labels, self_base, st);
         case VOTE_WEIGHTED: return vote_weighted_enqueue(c, lc, L, C, labels, self_base, st);
-        default: return regress_enqueue(c, lc, L, self_base, st);
+        case REGRESS: return regress_enqueue(c, lc, L, self_base, st);
+        default: return fail(c, KNN_EINVAL, "%s: not a per-pass consumer", kConsumerText[lc.kind].prefix);
     }
+}
+
+// the context-owned all-zero label array of n entries the vote-less passes of callers without
+// classes run with (regression, the local outlier factor)
+knn_status zero_labels(knn_ctx* c, int64_t n, hipStream_t st, const int32_t** out) {
+    const size_t need = sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1);
+    if (need > c->rg_zero.bytes || !c->rg_zero.p) {
+        HIP_OR_FAIL(c, c->rg_zero.ensure(need));
+        HIP_OR_FAIL(c, hipMemsetAsync(c->rg_zero.p, 0, need, st));
+    }
+    *out = c->rg_zero.as<int32_t>();
+    return KNN_OK;
 }
 
 hipError_t zero_accumulators(const ListConsumer& lc, int32_t kmax, hipStream_t st) {
@@ -1709,14 +1745,7 @@ knn_status lists_core(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, 
         HIP_OR_FAIL(c, hipStreamSynchronize(st));
         return KNN_OK;
     }
-    if (regress) {
-        const size_t need = sizeof(int32_t) * (size_t)std::max<int64_t>(tr->n, 1);
-        if (need > c->rg_zero.bytes || !c->rg_zero.p) {
-            HIP_OR_FAIL(c, c->rg_zero.ensure(need));
-            HIP_OR_FAIL(c, hipMemsetAsync(c->rg_zero.p, 0, need, st));
-        }
-        trv.labels = c->rg_zero.as<int32_t>();
-    }
+    if (regress && (s = zero_labels(c, tr->n, st, &trv.labels)) != KNN_OK) return s;
     const int algo = choose_algo(c, tr->n, te->n, tr->d, kin, tr->dtype);
     const bool gemm = is_gemm(algo);
     const int64_t grain = regress ? (int64_t)KNN_REGRESS_CHUNK * KNN_REGRESS_SPAN : 1;
@@ -1963,6 +1992,181 @@ knn_status knn_regress_sweep(knn_ctx* c, const knn_dataset* tr, const knn_datase
     return lists_host(c, tr, te, kmax, 1, self_base,
                       regress_consumer(weights, 0, train_targets, query_targets, out_pred_all, 0, out_sse, out_sae, nullptr,
                                        nullptr));
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// Local outlier factor (knn_amd.h "Local outlier factor"): k_lof_compact, k_lof_lrd, k_lof_score
+// behind the vote-less top-k pass.  A row's score reads its neighbours' lists, so the kernels start
+// after the LAST pass of the loop, over all rows: how the loop cuts the rows cannot change a bit.
+// ---------------------------------------------------------------------------------
+namespace {
+
+struct LofOut {
+    float* kd; double* lrd; float* lof; int64_t lof_stride;
+};
+
+knn_status lof_args_check(knn_ctx* c, int32_t k_lo, int32_t k_hi, int64_t self_base, const void* any_out) {
+    if (k_lo < 1 || k_hi > KNN_LOF_MAX_K || k_lo > k_hi) return fail(c, KNN_EINVAL, kLofText.bad_range, k_lo, k_hi);
+    return list_check(c,
+                      ListConsumer{LOF_SCORES, KNN_W_UNIFORM, 0, nullptr, nullptr, const_cast<void*>(any_out), 0,
+                                   {nullptr, nullptr}, nullptr, nullptr, nullptr},
+                      k_hi, self_base);
+}
+
+// The three kernels on lists in device memory, enqueued on st (no synchronisation).  kd_fit /
+// lrd_fit: the fitted tables of n_table rows (novelty: the lists are queries'); NULL: the lists are
+// the table rows' own, and kd / lrd are computed (into the caller's arrays or workspace).
+knn_status lof_enqueue(knn_ctx* c, const Lists& L, int64_t self_base, int64_t n_table, int k_lo, int k_hi,
+                       const float* kd_fit, const double* lrd_fit, const LofOut& o, hipStream_t st) {
+    const size_t Kr = (size_t)(k_hi - k_lo + 1), nq = (size_t)L.nq;
+    const bool novelty = kd_fit != nullptr;
+    HIP_OR_FAIL(c, c->lof_cidx.ensure(sizeof(int32_t) * nq * (size_t)k_hi));
+    HIP_OR_FAIL(c, c->lof_delta.ensure(sizeof(float) * nq * (size_t)k_hi));
+    float* kd = novelty ? nullptr : o.kd;
+    if (!novelty && !kd) {
+        HIP_OR_FAIL(c, c->lof_kd.ensure(sizeof(float) * nq * Kr));
+        kd = c->lof_kd.as<float>();
+    }
+    LofCompactArgs a{};
+    a.idx = L.idx; a.dist = L.dist; a.stride = L.stride;
+    a.nq = L.nq; a.n_table = n_table; a.kin = L.kin; a.k_lo = k_lo; a.k_hi = k_hi; a.self_base = self_base;
+    a.euclid = c->metric == KNN_METRIC_SQEUCLIDEAN ? 1 : 0;
+    a.check_dist = L.check_dist ? 1 : 0;
+    a.cidx = c->lof_cidx.as<int32_t>(); a.delta = c->lof_delta.as<float>(); a.kd = kd;
+    a.status = c->ctrl.as<int32_t>();
+    stage_begin(c, st, "lof");
+    HIP_OR_FAIL(c, knn_launch_lof_compact(a, st));
+    stage_end(c, st);
+    if (!novelty && !o.lrd && !o.lof) return KNN_OK;
+    double* lrd = novelty ? nullptr : o.lrd;
+    if (!lrd) {
+        DBuf& ws = novelty ? c->lof_qlrd : c->lof_lrd;
+        HIP_OR_FAIL(c, ws.ensure(sizeof(double) * nq * Kr));
+        lrd = ws.as<double>();
+    }
+    LofWalkArgs w{};
+    w.cidx = a.cidx; w.delta = a.delta; w.nq = L.nq; w.k_lo = k_lo; w.k_hi = k_hi;
+    w.kd_table = novelty ? kd_fit : kd; w.lrd_out = lrd;
+    stage_begin(c, st, "lof");
+    HIP_OR_FAIL(c, knn_launch_lof_lrd(w, st));
+    stage_end(c, st);
+    if (!o.lof) return KNN_OK;
+    w.lrd_table = novelty ? lrd_fit : lrd; w.lrd_own = lrd; w.lof = o.lof; w.lof_stride = o.lof_stride;
+    stage_begin(c, st, "lof");
+    HIP_OR_FAIL(c, knn_launch_lof_score(w, st));
+    stage_end(c, st);
+    return KNN_OK;
+}
+
+// finish_call behind the LOF kernels: the status word's texts are this feature's
+knn_status lof_finish(knn_ctx* c, hipStream_t st) {
+    const knn_status s = finish_call(c, st);
+    const int32_t status = c->ctrl_host[0];
+    if (s == KNN_EINVAL && (status & KNN_STATUS_BAD_INDEX)) return fail(c, s, "%s", kLofText.bad_index);
+    if (s == KNN_EINVAL && (status & KNN_STATUS_BAD_DIST)) return fail(c, s, "%s", kLofText.bad_dist);
+    if (s == KNN_ERANGE) return fail(c, s, "%s", kLofText.too_few);
+    return s;
+}
+
+// The vote-less top-kin pass of te against tr (context-owned zero labels, one class, choose_algo as
+// it is; kin may exceed the rows: the lists then end in missing entries) into lists [te->n][kin],
+// then the LOF kernels on ALL rows behind the last pass and one finish_call for both.  Earlier
+// passes of the GEMM path end in their own finish_call, as in lists_core.
+knn_status lof_core(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int kin, int64_t self_base, int k_lo,
+                    int k_hi, const float* kd_fit, const double* lrd_fit, const LofOut& o, float* d_dist, int32_t* d_idx,
+                    hipStream_t st) {
+    knn_status s;
+    if (!tr || !te) return fail(c, KNN_EINVAL, "%s dataset is NULL", tr ? "test" : "train");
+    knn_dataset trv = *tr, tev = *te;
+    trv.labels = static_cast<const int32_t*>(tr->feat);  // (for the checks; the zero array replaces it below)
+    tev.labels = nullptr;
+    QueryOut out{nullptr, nullptr, nullptr, nullptr, kin, 0};
+    if ((s = validate_call(c, &trv, &tev, kin, 1, out, true, false)) != KNN_OK) return s;
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    reset_stats(c);
+    const int64_t nq = tev.n;
+    if (nq == 0) return KNN_OK;
+    if ((s = zero_labels(c, trv.n, st, &trv.labels)) != KNN_OK) return s;
+    if (!d_idx) {
+        HIP_OR_FAIL(c, c->lof_idx.ensure(sizeof(int32_t) * (size_t)nq * kin));
+        d_idx = c->lof_idx.as<int32_t>();
+    }
+    if (!d_dist) {
+        HIP_OR_FAIL(c, c->lof_dist.ensure(sizeof(float) * (size_t)nq * kin));
+        d_dist = c->lof_dist.as<float>();
+    }
+    out.idx = d_idx;
+    out.dist = d_dist;
+    const int algo = choose_algo(c, trv.n, nq, trv.d, kin, trv.dtype);
+    const bool gemm = is_gemm(algo);
+    const int64_t pass = gemm ? std::max<int64_t>(1, c->ws_queries) : nq;
+    for (int64_t q0 = 0; q0 < nq; q0 += pass) {
+        const int64_t n = std::min(pass, nq - q0);
+        const bool last = q0 + n >= nq;
+        const knn_dataset tq = offset_rows(tev, q0, n);
+        s = predict_enqueue(c, &trv, &tq, kin, 1, offset_out(out, q0), st, algo, nullptr);
+        if (s == KNN_OK && last)
+            s = lof_enqueue(c, Lists{d_idx, d_dist, nq, kin, kin, false}, self_base, trv.n, k_lo, k_hi, kd_fit, lrd_fit, o,
+                            st);
+        if (s != KNN_OK || (s = last ? lof_finish(c, st) : finish_call(c, st)) != KNN_OK) {
+            if (s != KNN_EINVAL && s != KNN_ERANGE) c->tprep.valid = c->tpad.valid = false;  // a HIP failure: the operands may be partial
+            return s;
+        }
+        pass_stats(c, c->ctrl_host, gemm);
+    }
+    return KNN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+knn_status knn_lof_fit_device(knn_ctx* c, const knn_dataset* tr, int32_t k_lo, int32_t k_hi, float* d_kd, double* d_lrd,
+                              float* d_lof, float* d_dist, int32_t* d_idx, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    knn_status s;
+    const void* any = d_kd ? (const void*)d_kd : d_lrd ? (const void*)d_lrd : (const void*)d_lof;
+    if ((s = lof_args_check(c, k_lo, k_hi, 0, any)) != KNN_OK) return s;
+    return lof_core(c, tr, tr, k_hi + 1, 0, k_lo, k_hi, nullptr, nullptr, LofOut{d_kd, d_lrd, d_lof, tr ? tr->n : 0}, d_dist,
+                    d_idx, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+knn_status knn_lof_score_device(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t k_lo, int32_t k_hi,
+                                const float* d_kd, const double* d_lrd, float* d_lof_out, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    knn_status s;
+    if ((s = lof_args_check(c, k_lo, k_hi, -1, d_lof_out)) != KNN_OK) return s;
+    if (te && te->n > 0 && (!d_kd || !d_lrd || !d_lof_out)) return fail(c, KNN_EINVAL, "%s", kLofText.no_tables);
+    return lof_core(c, tr, te, k_hi, -1, k_lo, k_hi, d_kd, d_lrd, LofOut{nullptr, nullptr, d_lof_out, te ? te->n : 0},
+                    nullptr, nullptr, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+knn_status knn_lof_lists_device(knn_ctx* c, int64_t n, int32_t kin, const int32_t* d_idx, const float* d_dist,
+                                int64_t stride, int64_t self_base, int32_t k_lo, int32_t k_hi, float* d_kd,
+                                double* d_lrd, float* d_lof, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    c->stages.clear();
+    knn_status s;
+    const void* any = d_kd ? (const void*)d_kd : d_lrd ? (const void*)d_lrd : (const void*)d_lof;
+    if ((s = lof_args_check(c, k_lo, k_hi, self_base, any)) != KNN_OK) return s;
+    if (self_base > 0) return fail(c, KNN_EINVAL, kLofText.bad_self, (long long)self_base);
+    if (kin != k_hi + (self_base >= 0 ? 1 : 0)) return fail(c, KNN_EINVAL, kLofText.bad_kin, kin, k_hi);
+    if (n < 0 || n > 0x7fffffffLL || stride < kin)
+        return fail(c, KNN_EINVAL, kConsumerText[LOF_SCORES].bad_lists, (long long)n, kin, (long long)stride);
+    if (n > 0 && (!d_idx || !d_dist)) return fail(c, KNN_EINVAL, "%s", kConsumerText[LOF_SCORES].null_lists);
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (n == 0) return KNN_OK;
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    if ((s = lof_enqueue(c, Lists{d_idx, d_dist, n, stride, kin, true}, self_base, n, k_lo, k_hi, nullptr, nullptr,
+                         LofOut{d_kd, d_lrd, d_lof, n}, st)) != KNN_OK)
+        return s;
+    return lof_finish(c, st);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 //
 //   knn_cli train.arff test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]]
 //           [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress]
-//           [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]]
+//           [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]] [--lof[=KLO] [--lof-threshold=T]]
 //
 // Same positional arguments as ./main (main.cpp:114-122; k parsed with strtol) plus the
 // optional worker count of ./multi-thread (multi-thread.cpp:135-143), here the number of
@@ -33,6 +33,12 @@
 // the radius classifier's line once per radius, in ascending order.  Composes like --radius=; with
 // --regress, with --radius=, with plain --sweep, with more than 32 values or a value that is not a
 // number >= 0, it prints a usage error and exits 1.
+// --lof[=KLO] [--lof-threshold=T]: the local outlier factor (KNN_lof) of the train file's rows for
+// every k in [KLO, K] (default KLO = K) from one pass; the test path keeps its position and is not
+// read.  One line per k: the rows whose LOF is above T (default 1.5), and the largest LOF with its
+// row.  Composes with --metric=.  With --regress, --radius=, --radii=, --weights= or --sweep, with a
+// KLO that is no integer in [1, K], a K above 255 or a T that is no number, it prints a usage error
+// and exits 1.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -55,11 +61,18 @@ static int run(int argc, char* argv[]) {
     const char* radius_arg = nullptr;
     const char* radii_arg = nullptr;
     int outlier = -1;
+    bool lof = false, weights_given = false;
+    const char* lof_arg = nullptr;
+    const char* lof_thr_arg = nullptr;
     for (int i = 0; i < argc; i++) {
+        if (!std::strncmp(argv[i], "--weights=", 10)) weights_given = true;
         if (!std::strncmp(argv[i], "--shard=", 8)) setenv("KNN_AMD_SHARD", argv[i] + 8, 1);
         else if (!std::strcmp(argv[i], "--sweep")) sweep = true;
         else if (!std::strcmp(argv[i], "--sweep=loo")) sweep = loo = true;
         else if (!std::strcmp(argv[i], "--regress")) regress = true;
+        else if (!std::strcmp(argv[i], "--lof")) lof = true;
+        else if (!std::strncmp(argv[i], "--lof=", 6)) { lof = true; lof_arg = argv[i] + 6; }
+        else if (!std::strncmp(argv[i], "--lof-threshold=", 16)) lof_thr_arg = argv[i] + 16;
         else if (!std::strncmp(argv[i], "--radius=", 9)) radius_arg = argv[i] + 9;
         else if (!std::strncmp(argv[i], "--radii=", 8)) radii_arg = argv[i] + 8;
         else if (!std::strncmp(argv[i], "--outlier=", 10)) outlier = (int)std::strtol(argv[i] + 10, NULL, 10);
@@ -80,7 +93,7 @@ static int run(int argc, char* argv[]) {
     }
     argc = n;
     if (argc != 4 && argc != 5) {
-        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress] [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]]"
+        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress] [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]] [--lof[=KLO] [--lof-threshold=T]]"
                   << std::endl;
         std::exit(0);
     }
@@ -115,15 +128,65 @@ static int run(int argc, char* argv[]) {
         }
         std::sort(radii.begin(), radii.end());
     }
+    int lof_lo = k;
+    float lof_thr = 1.5f;
+    if (lof || lof_thr_arg) {
+        bool ok = lof && !regress && !radius_arg && !radii_arg && !weights_given && !sweep && k >= 1 && k <= 255;
+        if (ok && lof_arg) {
+            char* end = nullptr;
+            const long v = std::strtol(lof_arg, &end, 10);
+            ok = end != lof_arg && *end == '\0' && v >= 1 && v <= k;
+            lof_lo = (int)v;
+        }
+        if (ok && lof_thr_arg) {
+            char* end = nullptr;
+            lof_thr = std::strtof(lof_thr_arg, &end);
+            ok = end != lof_thr_arg && *end == '\0' && lof_thr == lof_thr;
+        }
+        if (!ok) {
+            std::cerr << "usage: --lof[=KLO] needs 1 <= KLO <= K <= 255, --lof-threshold=T a number, and does not combine "
+                         "with --regress, --radius=, --radii=, --weights= or --sweep"
+                      << std::endl;
+            std::exit(1);
+        }
+    }
     if (argc == 5) setenv("KNN_AMD_DEVICES", argv[4], 1);
 
     ArffParser parserTrain(argv[1]);
     ArffParser parserTest(argv[2]);
     ArffData* train = parserTrain.parse();
-    ArffData* test = loo ? train : parserTest.parse();
+    ArffData* test = (loo || lof) ? train : parserTest.parse();
     knn_amd_init();
 
     struct timespec start, end;
+    if (lof) {
+        clock_gettime(CLOCK_MONOTONIC_RAW, &start);
+        float* all = KNN_lof(train, lof_lo, k);
+        clock_gettime(CLOCK_MONOTONIC_RAW, &end);
+        uint64_t diff = (1000000000L * (end.tv_sec - start.tv_sec) + end.tv_nsec - start.tv_nsec) / 1e6;
+        const long nt = train->num_instances();
+        for (int kk = lof_lo; kk <= k; kk++) {
+            const float* row = all + (size_t)(kk - lof_lo) * nt;
+            long above = 0, at = -1;
+            for (long i = 0; i < nt; i++) {
+                above += row[i] > lof_thr;
+                if (row[i] == row[i] && (at < 0 || row[i] > row[at])) at = i;  // (the first of the largest; NaN never)
+            }
+            printf("The %i-NN local outlier factor of %lu train instances required %llu ms CPU time. %ld rows above %g, largest %.4f at row %ld\n",
+                   kk, (unsigned long)nt, (long long unsigned int)diff, above, (double)lof_thr,
+                   at < 0 ? std::nan("") : (double)row[at], at);
+        }
+        if (const char* p = std::getenv("KNN_CLI_PRED_OUT")) {  // test hook: one line of n scores per k, as %.9g
+            FILE* f = std::fopen(p, "w");
+            for (int kk = lof_lo; kk <= k; kk++) {
+                for (long i = 0; i < nt; i++) std::fprintf(f, i ? " %.9g" : "%.9g", all[(size_t)(kk - lof_lo) * nt + i]);
+                std::fprintf(f, "\n");
+            }
+            std::fclose(f);
+        }
+        std::free(all);
+        return 0;
+    }
     if (radii_arg) {
         const int R = (int)radii.size();
         std::vector<long> outliers((size_t)R, 0);

@@ -1,5 +1,5 @@
 // knn_device.h -- device helpers shared by the kernel translation units of libknn_amd
-// (knn_kernels.hip, knn_metric.hip, knn_radius.hip, knn_radius_gemm.hip, knn_fused.hip, knn_vote_weighted.hip, knn_regress.hip): keys and
+// (knn_kernels.hip, knn_metric.hip, knn_radius.hip, knn_radius_gemm.hip, knn_fused.hip, knn_vote_weighted.hip, knn_regress.hip, knn_lof.hip): keys and
 // wave bitonic networks, the vote and outputs of a finished wave list, the lane-shift insert, bf16 helpers, ordered-float bits, LDS-DMA issue and the GEMM filter tile
 // geometry.
 #pragma once

@@ -170,6 +170,34 @@ hipError_t knn_launch_regress(const RegressArgs& a, hipStream_t st);
 hipError_t knn_launch_regress_reduce(const double* part, int64_t nq, int kmax, int row0, double* sse, double* sae,
                                      hipStream_t st);
 
+// Local outlier factor (knn_lof.hip; knn_amd.h "Local outlier factor"): LOF for every k in
+// [k_lo, k_hi], 1 <= k_lo <= k_hi <= KNN_LOF_MAX_K, Kr = k_hi - k_lo + 1.
+// k_lof_compact: lists idx / dist [nq][stride], the first kin = k_hi (+ 1 with self_base >= 0)
+// entries of a row -> cidx / delta [nq][k_hi] after self-removal (delta binary32: sqrtf of the
+// distance when euclid, else the distance; -1 / NaN where missing) and kd (optional) [nq][Kr], delta
+// at positions k_lo - 1 .. k_hi - 1.  Indices are checked against [0, n_table) (KNN_STATUS_BAD_INDEX)
+// and, with check_dist, distances for NaN / negative (KNN_STATUS_BAD_DIST); such entries are stored
+// as missing.  A missing entry sets KNN_STATUS_TOO_FEW.
+#define KNN_LOF_MAX_K 255
+struct LofCompactArgs {
+    const int32_t* idx; const float* dist; int64_t stride;
+    int64_t nq; int64_t n_table; int kin; int k_lo; int k_hi; int64_t self_base;
+    int euclid; int check_dist;
+    int32_t* cidx; float* delta; float* kd;
+    int32_t* status;
+};
+hipError_t knn_launch_lof_compact(const LofCompactArgs& a, hipStream_t st);
+// k_lof_lrd: lrd_out [nq][Kr] binary64 from the rows' compacted lists and kd_table [n_table][Kr].
+// k_lof_score: lof [Kr][lof_stride >= nq] binary32 from the lists, lrd_table [n_table][Kr] and the
+// rows' own lrd_own [nq][Kr] (the table itself when the table's rows are scored).
+struct LofWalkArgs {
+    const int32_t* cidx; const float* delta; int64_t nq; int k_lo; int k_hi;
+    const float* kd_table; double* lrd_out;
+    const double* lrd_table; const double* lrd_own; float* lof; int64_t lof_stride;
+};
+hipError_t knn_launch_lof_lrd(const LofWalkArgs& a, hipStream_t st);
+hipError_t knn_launch_lof_score(const LofWalkArgs& a, hipStream_t st);
+
 // class counts up to this many live in a per-wave LDS table; above it the vote runs
 // table-free (vote_ballot), so every path accepts any num_classes
 #define KNN_VOTE_LDS_MAX_C 1024
