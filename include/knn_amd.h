@@ -717,9 +717,11 @@ int32_t knn_stage_times(const knn_ctx* ctx, const char** names, float* ms, int32
  * width of the last filter pass in features (the rows the MFMA multiplied: d padded with zero
  * columns, knn_filter_policy's operand_width; 0 when no filter ran), [16] the chunks the filter
  * cut an operand row into (1 for k_gemm_fused and k_gemm_filter, operand width / 128 for
- * k_gemm_wide; 0 when no filter ran).
- * Returns the number written (<= 17); a caller that asks for 11, 12, 13 or 15 gets the first 11,
- * 12, 13 or 15 as before. */
+ * k_gemm_wide; 0 when no filter ran), [17] the queries of the last pass whose start threshold the
+ * int8 filter's seed pass lowered to a finite bound (k_seed_thr; counted under profile = 2 only,
+ * like [0] and [12]; 0 otherwise).
+ * Returns the number written (<= 18); a caller that asks for 11, 12, 13, 15 or 17 gets the first 11,
+ * 12, 13, 15 or 17 as before. */
 int32_t knn_last_stats(const knn_ctx* ctx, int64_t* out, int32_t n);
 
 /*

@@ -1261,8 +1261,8 @@ class Context:
         return out
 
     def stats(self):
-        v = (ctypes.c_int64 * 17)()
-        self.lib.knn_last_stats(self.h, v, 17)
+        v = (ctypes.c_int64 * 18)()
+        self.lib.knn_last_stats(self.h, v, 18)
         return {"candidates": v[0], "fallback_queries": v[1], "train_segments": v[2],
                 "filter_operands": FILTER_OPERANDS.get(v[3], v[3]), "rerun_split": bool(v[4]),
                 "fused_norm": bool(v[5]), "h2d_train_bytes": v[6], "h2d_query_bytes": v[7],
@@ -1270,7 +1270,20 @@ class Context:
                 "queries_per_wave": v[10],
                 "filter_element": FILTER_ELEMENTS.get(v[11], v[11]) if v[3] in (1, 2, 3) else None,
                 "parked_passes": v[12], "radius_form": RADIUS_FORMS.get(v[13], v[13]),
-                "radius_exact_pairs": v[14], "filter_width": v[15], "filter_chunks": v[16]}
+                "radius_exact_pairs": v[14], "filter_width": v[15], "filter_chunks": v[16],
+                "seeded_queries": v[17]}
+
+    def last_seed(self, nq):
+        """Test hook (knn_debug_last_seed): the thresholds the int8 filter's seed pass published in the
+        last pass of the last call, one float32 per query (+inf: none).  profile = 2 contexts only;
+        an empty array when that pass ran no seed."""
+        out = np.full(nq, np.inf, dtype=np.float32)
+        fn = self.lib.knn_debug_last_seed  # (a test hook: not in load_library's table)
+        fn.restype, fn.argtypes = ctypes.c_longlong, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong]
+        n = fn(self.h, out.ctypes.data, nq)
+        if n < 0:
+            raise KnnError(KNN_EINVAL, "knn_debug_last_seed")
+        return out[:n]
 
 
 def comm_unique_id():

@@ -82,6 +82,8 @@ struct knn_ctx {
     DBuf lshare;            // fused filter: per (query, piece) threshold lists shared between pieces
     DBuf parkcnt;           // fused filter, profile = 2: the records its parked passes held (one 64-bit word)
     bool park_counted = false;  // the last pass's filter counted into parkcnt
+    DBuf seedbuf;               // profile = 2: the last pass's seeds (k_seed_thr), ordered bits per query
+    int64_t seed_nq = 0;        // ... and how many queries it holds (0: the pass ran no seed)
     DBuf qstat;             // fused filter: per-query {|q|, |q - rq|} upper bounds
     DBuf tblk;              // fused filter: train tile blocks [bn rows rn(t) | bn norms | tile stats]
     DBuf tctrl;             // the train norms' share of the status word: [unsafe bits, 0, max norm, 0]
@@ -180,7 +182,7 @@ struct knn_ctx {
     bool stage_open = false;  // the last stage_begin recorded an event (profile = 3 skips some)
     std::vector<float> stage_ms;
     std::vector<const char*> stage_names;
-    int64_t stats[17] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
+    int64_t stats[18] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
                                                       // operand type, rerun, fused, train / query H2D
                                                       // bytes, train-side filter operands from the cache,
                                                       // MFMA form, queries per wave, [11] the filter's
@@ -1045,6 +1047,32 @@ knn_status run_gemm(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, in
         g.park_cnt = c->parkcnt.as<unsigned long long>();
     }
     if (!gate) c->park_counted = g.park_cnt != nullptr;
+    // seeded thresholds (k_seed_thr, knn_seed.hip): the int8 class's first pass lowers gthr from +inf
+    // to a bound from a strided sample of the tile blocks the filter is about to read -- the same
+    // cached operand, nothing of its own to keep.  Not on the gated re-run (never int8).  Like the
+    // parked passes' count the seeds themselves are a diagnostic of profile = 2: the timed path
+    // hands the kernel no side buffer.
+    if (!gate) c->seed_nq = 0;
+    if (i8 && fused && !gate && c->fforce.seed) {
+        SeedArgs sa{};
+        sa.sample = knn_seed_sample(nt, bn_f, nq, c->num_cus);
+        if (sa.sample.ns > 0) {
+            sa.tblk = c->tblk.p; sa.bn = bn_f; sa.qop = c->split_q.p; sa.nq = nq;
+            sa.pad_blk = (ntp + 256) / bn_f - 1;  // (the operand ends in 256 pad rows, above)
+            sa.qnorm = g.qnorm; sa.qstat = g.qstat; sa.tsmax = g.tsmax;
+            sa.coef = coef; sa.eta = eta; sa.i8_s2 = g.i8_s2; sa.k = k;
+            sa.gthr = g.gthr; sa.status = g.status; sa.gate = gate;
+            if (c->profile == 2) {
+                HIP_OR_FAIL(c, c->seedbuf.ensure(sizeof(uint32_t) * nq));
+                HIP_OR_FAIL(c, knn_launch_fill_u32(c->seedbuf.as<uint32_t>(), nq, 0xFF800000u, nullptr, st));  // ordered(+inf)
+                sa.seed_out = c->seedbuf.as<uint32_t>();
+                c->seed_nq = nq;
+            }
+            stage_begin(c, st, "seed");
+            HIP_OR_FAIL(c, knn_launch_seed_thr(sa, st));
+            stage_end(c, st);
+        }
+    }
     const int subs = KNN_FILTER_SUBSLICES;  // candidate sub-slices per segment: one per lane half
     if (fused && g.g2 >= 0 && nseg > 1)  // whole query tiles write only their piece's sub-slices
         HIP_OR_FAIL(c, hipMemsetAsync(c->cnt.p, 0, sizeof(int32_t) * subs * nseg * nq, st));
@@ -1123,12 +1151,14 @@ knn_status knn_create(knn_ctx** out, const knn_opts* opts) {
     //   KNN_FUSED_QG=1|2   the fused filter's queries per wave, 32 or 64 (knn_fused_plan's fill rule)
     //   KNN_FUSED_HEAPS    (set) the LDS-heap shape for 32 < k <= 104 at d = 256
     //   KNN_FUSED_PARK=0|1 the int8 filter's parked passes off (the immediate slow path) / on
+    //   KNN_FUSED_SEED=0|1 the int8 filter's seeded thresholds (k_seed_thr) off / on
     //   KNN_WS_QUERIES=n   queries per pass of the GEMM path's candidate workspace
     //   KNN_BATCH_ROWS=n   query rows per batch of the host pipeline
     if (const char* e = getenv("KNN_RESCORE_SU")) c->rescore_su = atoi(e);
     if (const char* e = getenv("KNN_FUSED_QG")) c->fforce.qg = atoi(e);
     c->fforce.heaps = getenv("KNN_FUSED_HEAPS") != nullptr;
     if (const char* e = getenv("KNN_FUSED_PARK")) c->fforce.park = atoi(e) != 0 ? 1 : 0;
+    if (const char* e = getenv("KNN_FUSED_SEED")) c->fforce.seed = atoi(e) != 0 ? 1 : 0;
     if (c->device < 0 || c->device >= ndev) { delete c; return KNN_ENODEV; }
     hipDeviceProp_t prop;
     if (hipSetDevice(c->device) != hipSuccess || hipGetDeviceProperties(&prop, c->device) != hipSuccess) {
@@ -1175,7 +1205,7 @@ void knn_destroy(knn_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     for (DBuf* b : {&c->tnorm, &c->tnp, &c->qnorm, &c->gthr, &c->cnt, &c->cand,
-                    &c->fb_list, &c->ctrl, &c->scratch, &c->split_t, &c->split_q, &c->pad_t, &c->seg_rec, &c->arrive, &c->tmax, &c->tsmax, &c->qstat, &c->tblk, &c->tctrl, &c->cursor, &c->lshare, &c->parkcnt, &c->h_train, &c->h_labels, &c->h_test, &c->h_pred,
+                    &c->fb_list, &c->ctrl, &c->scratch, &c->split_t, &c->split_q, &c->pad_t, &c->seg_rec, &c->arrive, &c->tmax, &c->tsmax, &c->qstat, &c->tblk, &c->tctrl, &c->cursor, &c->lshare, &c->parkcnt, &c->seedbuf, &c->h_train, &c->h_labels, &c->h_test, &c->h_pred,
                     &c->h_dist, &c->h_idx, &c->sw_dist, &c->sw_idx, &c->sw_pred, &c->sw_qside, &c->sw_acc, &c->sw_scores,
                     &c->rg_part, &c->rg_zero, &c->rg_targets, &c->rd_segcnt, &c->rd_base, &c->rd_cc, &c->rd_scores,
                     &c->rm_tnorm, &c->rm_tmax, &c->rm_tsmax, &c->rm_tblk, &c->rm_tctrl, &c->rm_qnorm, &c->rm_qstat,
@@ -1320,7 +1350,8 @@ knn_dataset offset_rows(const knn_dataset& x, int64_t r0, int64_t n) {
 
 void reset_stats(knn_ctx* c) {
     c->stages.clear();
-    for (int i = 0; i < 17; i++) c->stats[i] = 0;
+    for (int i = 0; i < 18; i++) c->stats[i] = 0;
+    c->seed_nq = 0;
     c->stats[3] = -1;
 }
 // the vote / regression on CSR lists run no distance pass: the form and the exact evaluations of the
@@ -1331,6 +1362,19 @@ void reset_stats_keep_radius(knn_ctx* c) {
     reset_stats(c);
     c->stats[13] = form;
     c->stats[14] = exact;
+}
+
+// the last pass's seeds as floats (+inf: none); false when that pass recorded none
+bool last_seeds(knn_ctx* c, std::vector<float>& out) {
+    if (c->seed_nq <= 0 || !c->seedbuf.p) return false;
+    std::vector<uint32_t> o((size_t)c->seed_nq);
+    if (hipMemcpy(o.data(), c->seedbuf.p, sizeof(uint32_t) * o.size(), hipMemcpyDeviceToHost) != hipSuccess) return false;
+    out.resize(o.size());
+    for (size_t i = 0; i < o.size(); i++) {
+        const uint32_t b = (o[i] & 0x80000000u) ? (o[i] & 0x7fffffffu) : ~o[i];  // (o2f, knn_device.h)
+        std::memcpy(&out[i], &b, sizeof(float));
+    }
+    return true;
 }
 
 // Shared pipeline of knn_predict_device / knn_shard_topk_device: the GEMM path runs the
@@ -1371,6 +1415,13 @@ knn_status predict_core(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te
         if (c->stats[11] == 1 && c->park_counted &&
             hipMemcpy(&parked, c->parkcnt.p, sizeof(parked), hipMemcpyDeviceToHost) == hipSuccess)
             c->stats[12] = (int64_t)parked;
+        // ... and the queries whose threshold the seed pass lowered (last pass)
+        std::vector<float> seeds;
+        if (c->stats[11] == 1 && last_seeds(c, seeds)) {
+            int64_t n = 0;
+            for (float v : seeds) n += std::isfinite(v) ? 1 : 0;
+            c->stats[17] = n;
+        }
     }
     return KNN_OK;
 }
@@ -2930,7 +2981,7 @@ int32_t knn_stage_times(const knn_ctx* c, const char** names, float* ms, int32_t
 
 int32_t knn_last_stats(const knn_ctx* c, int64_t* out, int32_t n) {
     if (!c || !out) return 0;
-    int32_t m = std::min(n, 17);
+    int32_t m = std::min(n, 18);
     for (int32_t i = 0; i < m; i++) out[i] = c->stats[i];
     return m;
 }
@@ -2975,6 +3026,19 @@ knn_status knn_mfma_probe_i8(knn_ctx* c, const int8_t* d_a, const int8_t* d_b, i
     HIP_OR_FAIL(c, knn_launch_mfma_probe_i8(d_a, d_b, K, d_out, st));
     HIP_OR_FAIL(c, hipStreamSynchronize(st));
     return KNN_OK;
+}
+
+// test hook (not in knn_amd.h): the seeds k_seed_thr published in the last pass of the last call
+// on a profile = 2 context, one float per query of that pass (+inf: none); host_out takes
+// min(n, queries).  Returns how many it wrote, 0 when that pass ran no seed, -1 on an error.
+long long knn_debug_last_seed(knn_ctx* c, float* host_out, long long n) {
+    if (!c || !host_out || n < 0) return -1;
+    if (hipSetDevice(c->device) != hipSuccess) return -1;
+    std::vector<float> seeds;
+    if (!last_seeds(c, seeds)) return 0;
+    const size_t m = std::min<size_t>((size_t)n, seeds.size());
+    std::memcpy(host_out, seeds.data(), sizeof(float) * m);
+    return (long long)m;
 }
 
 // test hook (not in knn_amd.h): the int8 operand class's step times mul (a factor in [1, 8]) on

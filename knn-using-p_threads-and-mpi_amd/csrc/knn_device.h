@@ -1,5 +1,5 @@
 // knn_device.h -- device helpers shared by the kernel translation units of libknn_amd
-// (knn_kernels.hip, knn_metric.hip, knn_radius.hip, knn_radius_gemm.hip, knn_fused.hip, knn_vote_weighted.hip, knn_regress.hip, knn_lof.hip): keys and
+// (knn_kernels.hip, knn_metric.hip, knn_radius.hip, knn_radius_gemm.hip, knn_fused.hip, knn_seed.hip, knn_vote_weighted.hip, knn_regress.hip, knn_lof.hip): keys and
 // wave bitonic networks, the vote and outputs of a finished wave list, the lane-shift insert, bf16 helpers, ordered-float bits, LDS-DMA issue and the GEMM filter tile
 // geometry.
 #pragma once
@@ -269,6 +269,35 @@ __host__ __device__ inline int32_t knn_i8_fast_thr(float tf, float s2) {
     if (!(x > -0x1p31f)) return (int32_t)0x80000000u;
     return (int32_t)x;
 }
+// The seed pass's bound (k_seed_thr, DESIGN.md "Seeded thresholds"): U of accumulator value a for a
+// query with norm qn and statistics qs = {|q|, |q - rq|}, by the slow path's formula (fused_piece's
+// bounds and tile_q) with the train set's maxima smax (a.tsmax) in place of the tile's own
+// statistics.  Every term is monotone in the statistic it takes, so U >= the slow path's U of the
+// same row >= its direct-form distance D; and U is non-increasing in a (-s2 < 0, float(a) is
+// monotone).  A NaN or infinite qn gives a non-finite U, which the caller must not publish.
+__host__ __device__ inline float knn_i8_seed_bound(int32_t a, float qn, float2 qs, float s2, float coef, float eta,
+                                                   float4 smax) {
+    const float qe2 = 2.0f * qs.x * (1.0f + 0x1p-17f);
+    const float eq2 = 2.0f * qs.y * (1.0f + 0x1p-17f);
+    const float G = fmaf(-s2, (float)a, qn);
+    const float dl = fmaf(coef, qn + smax.x, eta) + (fmaf(qe2, smax.y, eq2 * smax.z) + smax.w * (1.0f + 0x1p-20f));
+    return G + dl;
+}
+// The k-th largest (with multiplicity) of a multiset of int32, given count_ge(t) = how many of its
+// values are >= t: the largest t with count_ge(t) >= k, built bit by bit from the top of the
+// values' order-preserving unsigned keys (32 counts).  Fewer than k values: INT32_MIN.
+template <typename CountGE>
+__host__ __device__ inline int32_t knn_kth_largest_i32(int k, CountGE count_ge) {
+    uint32_t key = 0u;
+    for (int b = 31; b >= 0; b--) {
+        const uint32_t c = key | (1u << b);
+        if (count_ge((int32_t)(c ^ 0x80000000u)) >= k) key = c;
+    }
+    return (int32_t)(key ^ 0x80000000u);
+}
+// a group maximum at or below this is an empty group: pad rows start their accumulators from
+// -2^30 (k_i8_rows), and a valid row's a = nq . nt - n_r is above -2^22 at d = 128
+static constexpr int32_t KNN_SEED_EMPTY = -(1 << 29);
 
 // ordered uint <-> float (monotone for all non-NaN floats)
 __device__ __forceinline__ uint32_t f2o(float f) {

@@ -455,13 +455,14 @@ hipError_t knn_launch_rescore(const RescoreArgs& a, hipStream_t st);
 // bn fp32 norms | tile statistics] (k_tn_rows), each accumulator starting from the norms
 bool knn_fused_supported(int d);
 // Test hooks of the fused plan (the product plan is knn_fused_plan's rule; a context snapshots
-// these once, at knn_create, from KNN_FUSED_QG / KNN_FUSED_HEAPS / KNN_FUSED_PARK so the tests can
+// these once, at knn_create, from KNN_FUSED_QG / KNN_FUSED_HEAPS / KNN_FUSED_PARK / KNN_FUSED_SEED so the tests can
 // run every shape): qg 1|2 forces the queries per wave, heaps the LDS-heap shape for 32 < k <= 104
 // at d = 256, park 0|1 the int8 shapes' parked passes off / on.  0 / false / -1: the rule.
 struct FusedForce {
     int qg = 0;
     bool heaps = false;
     int park = -1;  // KNN_FUSED_PARK=0|1: the int8 shapes' parked passes off / on; -1: the rule
+    int seed = 1;   // KNN_FUSED_SEED=0|1: the int8 shapes' seeded thresholds (k_seed_thr) off / on; not part of the plan
 };
 // nw == 0: k too large.  nq, num_cus and max_pieces (the most pieces a query's candidate list
 // allows) pick the queries per wave (register-list shapes): 64 on 32-row tiles when the
@@ -509,6 +510,32 @@ hipError_t knn_launch_i8_rows(const float* x, int64_t n, int64_t n_valid, int ld
                               void* out, const float4* tstat, int bn, hipStream_t st);
 // s2 = fl(2 s s) of scale s, as the kernels round it (knn_i8_s2, knn_device.h)
 float knn_i8_s2_of(float s);
+// Seeded thresholds of the int8 fused filter (knn_seed.hip, k_seed_thr; DESIGN.md "Seeded
+// thresholds"): a pass over a strided sample of the train tile blocks that lowers gthr[q] from
+// +inf to an upper bound of the query's k-th distance, so the filter's pieces start warm.
+// The sample (no GPU call): tile block i (stride) of the train set's bn-row tile blocks, i < ns;
+// each of `slices` blocks per query tile takes every slices-th of them and publishes its own bound.
+// ns == 0: no seed for this shape.
+struct SeedSample {
+    int ns = 0;
+    int64_t stride = 0;
+    int slices = 1;
+};
+SeedSample knn_seed_sample(int64_t nt, int bn, int64_t nq, int num_cus);
+struct SeedArgs {
+    const void* tblk; int bn;      // the filter's train operand (k_i8_rows), bn = 32 or 64
+    int64_t pad_blk;               // a tile block of it that holds pad rows only (the operand's last)
+    const void* qop; int64_t nq;   // int8 query rows [nq][128]
+    const float* qnorm; const float2* qstat; const float4* tsmax;
+    float coef, eta, i8_s2;
+    int k;                         // <= 32
+    SeedSample sample;
+    uint32_t* gthr;                // ordered bits; lowered with atomicMin
+    uint32_t* seed_out;            // optional (profile = 2): the same bound, into a buffer of ordered(+inf)
+    const int32_t* status;         // a set KNN_STATUS_GEMM_UNSAFE bit skips the pass
+    const int32_t* gate;           // optional: the pass runs only when *gate != 0
+};
+hipError_t knn_launch_seed_thr(const SeedArgs& a, hipStream_t st);
 // the int8 filter's MFMA chain on [32][K] int8 operands (K % 32 == 0): out [32][32] int32
 hipError_t knn_launch_mfma_probe_i8(const int8_t* a, const int8_t* b, int K, int32_t* out, hipStream_t st);
 hipError_t knn_launch_merge(const MergeArgs& a, hipStream_t st);
