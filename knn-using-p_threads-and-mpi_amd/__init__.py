@@ -262,7 +262,10 @@ def _device_dataset(feat, labels=None, d=None):
         raise KnnError(KNN_EINVAL, "features must be a 2-D [n][ld] tensor")
     if feat.shape[0] > 1 and feat.stride(1) != 1:
         raise KnnError(KNN_EINVAL, "features must have unit stride along the feature axis")
-    ld = feat.stride(0) if feat.shape[0] > 1 else feat.shape[1]
+    # (one row: torch may report any stride(0) for it; a view of a wider table keeps the table's
+    # pitch -- x[:1, :257] of 264-column rows is as aligned as x[:2, :257] -- anything shorter than
+    # the row is not a pitch)
+    ld = feat.stride(0) if feat.shape[0] > 1 or feat.stride(0) >= feat.shape[1] else feat.shape[1]
     d = feat.shape[1] if d is None else d
     if d > feat.shape[1]:
         raise KnnError(KNN_EINVAL, f"d={d} exceeds the tensor's {feat.shape[1]} columns")

@@ -2414,6 +2414,17 @@ size_t knn_gemm_filter_lds(int elem, int row_bytes, int k) {
     return knn_gemm_filter_plan(elem, row_bytes, k).lds;
 }
 
+// The plan knn_gemm_filter_plan makes (elem: ELEM_F32 / ELEM_BF16 / ELEM_SPLIT / ELEM_ROUND, the
+// caller's element or the filter's): out[7] = {nw, qg, rg, minw, nbuf, bm, lds}.  A test hook like
+// knn_fused_debug_plan (tests/test_plan_lattice_cpu.py).  No GPU call.
+extern "C" int knn_debug_gemm_filter_plan(int elem, int row_bytes, int k, long long* out) {
+    if (!out || k < 1 || elem < ELEM_F32 || elem > ELEM_ROUND || !knn_gemm_filter_supported(elem, row_bytes)) return -1;
+    const FilterPlan f = knn_gemm_filter_plan(elem == ELEM_ROUND ? ELEM_BF16 : elem, row_bytes, k);
+    const long long v[7] = {f.nw, f.qg, f.rg, f.minw, f.nbuf, f.bm, (long long)f.lds};
+    for (int i = 0; i < 7; i++) out[i] = v[i];
+    return 0;
+}
+
 bool knn_gemm_filter_supported(int elem, int row_bytes) {
     (void)elem;
     return row_bytes == 128 || row_bytes == 256 || row_bytes == 512;

@@ -286,6 +286,16 @@ FilterPlan knn_wide_plan(int k) {
     return FilterPlan{WIDE_NW, 1, 1, 2, WIDE_NBUF, WideTile::BM, lds};
 }
 
+// The plan knn_wide_plan makes: out[8] = {nw, qg, rg, minw, nbuf, bm, lds, train rows per group}.  A
+// test hook like knn_fused_debug_plan (tests/test_plan_lattice_cpu.py).  No GPU call.
+extern "C" int knn_debug_wide_plan(int k, long long* out) {
+    if (!out || k < 1) return -1;
+    const FilterPlan f = knn_wide_plan(k);
+    const long long v[8] = {f.nw, f.qg, f.rg, f.minw, f.nbuf, f.bm, (long long)f.lds, knn_wide_group_rows()};
+    for (int i = 0; i < 8; i++) out[i] = v[i];
+    return 0;
+}
+
 hipError_t knn_wide_occupancy(int k, int* blocks_per_cu) {
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, reinterpret_cast<const void*>(&k_gemm_wide),
                                                         64 * WIDE_NW, knn_wide_plan(k).lds);
