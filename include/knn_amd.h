@@ -694,6 +694,67 @@ knn_status knn_radius_vote_sweep_device(knn_ctx* ctx, int64_t nq, int64_t n_trai
                                         int32_t outlier_label, const int32_t* d_query_labels, int64_t ld_out,
                                         int32_t* d_pred, int64_t* d_correct, float* d_scores, void* hip_stream);
 
+/*
+ * DBSCAN: the clustering most fixed-radius self-joins are run for, from three distance passes over
+ * the train set against itself and no neighbour list.  Per pair it needs one bit, D <= thr.
+ *   T, thr, min_samples
+ *               T is the train set of n rows under the context's metric.  thr follows "Radius
+ *               neighbours": binary32, 0 <= thr < FLT_MAX, in the units of the reported distance (a
+ *               radius r is float32(r) * float32(r) under the Euclidean metric).  min_samples >= 1.
+ *   neighbourhood
+ *               N(i) = { t : D(i, t) <= thr }, D bit for bit what knn_radius_count_device tests.  The
+ *               row itself is a member and so are its exact copies: a self-join with self_base = -1.
+ *               D is symmetric to the bit under all three metrics ((q - t)^2 and |q - t| commute and
+ *               the features are taken in the same order).  A row with a NaN feature has an empty
+ *               neighbourhood and is noise (Euclidean, Manhattan: its D is NaN against every row,
+ *               itself included; the Chebyshev maximum skips a NaN difference, see "Metrics").
+ *   core        row i is a core row iff |N(i)| >= min_samples (sklearn's rule: the row counts itself).
+ *   clusters    the connected components of the graph on the core rows with an edge wherever
+ *               D <= thr.  A component's representative is its smallest row index, and clusters are
+ *               numbered 0, 1, ... in ascending order of representative.
+ *   border      a non-core row with at least one core neighbour takes the SMALLEST CLUSTER NUMBER
+ *               AMONG ITS CORE NEIGHBOURS.  (sklearn expands cluster c completely before it starts
+ *               cluster c + 1 and labels every unlabelled row a core row reaches: the first cluster
+ *               to claim a border row is the smallest-numbered one next to it.)
+ *   noise       every other row: -1.
+ *   Together: labels == sklearn.cluster.DBSCAN(metric="precomputed").fit(D).labels_ exactly, given
+ *   the same membership matrix.
+ *   outputs     d_labels int32 [n]; d_count int32 [n], optional, |N(i)| -- the very bits
+ *               knn_radius_count_device returns for (T, T, thr, self_base = -1); d_summary int64 [4],
+ *               optional, {clusters, core rows, border rows, noise rows}.
+ *   determinism the same bits on every run, through both forms of the pass and any number of train
+ *               segments: every step is integer, and the union-find's roots do not depend on the
+ *               order of the unions (parents only ever decrease, so a component's root is its
+ *               smallest row).
+ * knn_dbscan_device: the count pass (as knn_radius_count_device; the form knn_radius_policy states
+ *   for (n, n)), the link pass (a passing pair of core rows q > t is joined in a lock-free
+ *   union-find; only rows below a block's last query are scanned), the numbering (flatten, an
+ *   exclusive scan of the roots, labels), and the border pass over the compacted rows with
+ *   !core && count >= 2, in the link pass's form, whose per-query minimum of the core neighbours'
+ *   cluster numbers meets across train segments in an integer atomicMin.  One synchronisation.
+ *   KNN_EINVAL for min_samples < 1, a thr outside [0, FLT_MAX), n > INT32_MAX or a NULL d_labels, the
+ *   outputs untouched; n == 0 returns KNN_OK (and a zero summary).
+ * knn_dbscan_lists_device: the same union-find and labelling on CSR lists the caller holds --
+ *   d_offsets int64 [n + 1], d_idx int32 [offsets[n]]: a knn_radius_fill_device self-join with
+ *   self_base = -1 (the row itself is in its list), or lists concatenated from train shards.
+ *   count[i] = offsets[i + 1] - offsets[i].  An index outside [0, n) gives KNN_EINVAL (it is checked
+ *   before any table is read with it), and so do offsets that decrease.
+ * Stages under profile = 1: "radius_count" (and the MFMA form's "radius_norms", "radius_operands",
+ * "radius_scan" with several segments), "dbscan_link", "dbscan_border" (compaction and pass),
+ * "dbscan_labels" (init, flatten, scan, labels, summary).  knn_last_stats()[13] reads as after a radius
+ * call; [18] is the number of rows sent through the border pass, [19], under profile = 2, the
+ * successful hooks of the union-find.  A union-find loop that reaches its iteration cap (3 n + 8
+ * steps, a bound no correct run can reach) gives KNN_EHIP, "internal error", never a hang.
+ * Not here: an eps sweep (the radius sweep's counts give the core sets of 32 radii; the links are
+ * what is missing), sample_weight, HDBSCAN / OPTICS, a host-buffer entry point, a multi-rank driver
+ * (lists concatenate by shard: knn_dbscan_lists_device).
+ */
+knn_status knn_dbscan_device(knn_ctx* ctx, const knn_dataset* train, float thr, int32_t min_samples,
+                             int32_t* d_labels, int32_t* d_count, int64_t* d_summary, void* hip_stream);
+knn_status knn_dbscan_lists_device(knn_ctx* ctx, int64_t n, const int64_t* d_offsets, const int32_t* d_idx,
+                                   int32_t min_samples, int32_t* d_labels, int32_t* d_count, int64_t* d_summary,
+                                   void* hip_stream);
+
 /* Per-stage device times (ms) of the last predict call when opts.profile >= 1.
  * names: optional array of n const char* to receive stage names. Returns the
  * number of stages recorded (<= n). */
@@ -719,9 +780,11 @@ int32_t knn_stage_times(const knn_ctx* ctx, const char** names, float* ms, int32
  * cut an operand row into (1 for k_gemm_fused and k_gemm_filter, operand width / 128 for
  * k_gemm_wide; 0 when no filter ran), [17] the queries of the last pass whose start threshold the
  * int8 filter's seed pass lowered to a finite bound (k_seed_thr; counted under profile = 2 only,
- * like [0] and [12]; 0 otherwise).
- * Returns the number written (<= 18); a caller that asks for 11, 12, 13, 15 or 17 gets the first 11,
- * 12, 13, 15 or 17 as before. */
+ * like [0] and [12]; 0 otherwise), [18] the rows a DBSCAN call sent through its border pass (the
+ * non-core rows with a neighbour besides themselves), [19] the successful hooks of its union-find
+ * (profile = 2 only; 0 otherwise).
+ * Returns the number written (<= 20); a caller that asks for 11, 12, 13, 15, 17 or 18 gets the first
+ * 11, 12, 13, 15, 17 or 18 as before. */
 int32_t knn_last_stats(const knn_ctx* ctx, int64_t* out, int32_t n);
 
 /*

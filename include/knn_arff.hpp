@@ -214,6 +214,12 @@ int* KNN_radius_sweep_loo(ArffData* train, const float* radii, int n_radii, int 
 // float[(k_hi - k_lo + 1) * n] laid out [k_hi - k_lo + 1][n], row k - k_lo for k, caller frees.
 // Runs on the first device.
 float* KNN_lof(ArffData* train, int k_lo, int k_hi);
+// DBSCAN (knn_amd.h "DBSCAN"; sklearn's DBSCAN labels): the clusters of the train rows at that radius
+// under the run's metric, a core row having at least min_samples rows (itself included) within it.
+// The last attribute is not read.  Returns malloc'd int[n]: clusters 0, 1, ... in ascending order of
+// their smallest row, -1 noise; caller frees.  summary (optional) receives {clusters, core rows,
+// border rows, noise rows}.  Runs on the first device.
+int* KNN_dbscan(ArffData* train, float radius, int min_samples, long* summary = nullptr);
 // main.cpp:87 -- calloc'd int[C*C], C = dataset->num_classes(), row = true class.
 int* computeConfusionMatrix(int* predictions, ArffData* dataset);
 // main.cpp:102

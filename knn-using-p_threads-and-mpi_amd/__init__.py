@@ -152,6 +152,8 @@ def load_library(path=LIB_PATH):
         "knn_radius_sweep_count_device": (I32, [P, DS, DS, P, I32, I32, I64, I32, P, I64, P, P, P, P, P, P]),
         "knn_radius_sweep_max_queries": (I64, [P, I32, I32]),
         "knn_radius_vote_sweep_device": (I32, [P, I64, I64, P, P, P, P, I32, I32, P, I32, I32, P, I64, P, P, P, P]),
+        "knn_dbscan_device": (I32, [P, DS, F, I32, P, P, P, P]),
+        "knn_dbscan_lists_device": (I32, [P, I64, P, P, I32, P, P, P, P]),
         "knn_arff_copy_targets": (I32, [P, P, I32, P]),
         "knn_stage_times": (I32, [P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(F), I32]),
         "knn_last_stats": (I32, [P, ctypes.POINTER(I64), I32]),
@@ -1021,6 +1023,64 @@ class Context:
                                           outlier_label, query_labels=labels, self_base=0, scores=scores,
                                           stream=stream, d=d)
 
+    # DBSCAN (knn_amd.h "DBSCAN")
+    def _dbscan_out(self, n, labels, count, dev):
+        """labels int32 [n] (the caller's, or new), count int32 [n] or None, summary int64 [4]."""
+        import torch
+        if labels is None:
+            labels = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+        else:
+            _check_tensor(labels, "labels", torch.int32, n)
+        if count is True:
+            count = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+        elif count is False or count is None:
+            count = None
+        else:
+            _check_tensor(count, "count", torch.int32, n)
+        return labels, count, torch.zeros(4, dtype=torch.int64, device=dev)
+
+    def dbscan_device(self, train, radius=None, threshold=None, min_samples=5, labels=None, count=False, stream=None,
+                      d=None):
+        """sklearn.cluster.DBSCAN's labels of the train rows under the context's metric
+        (knn_dbscan_device): three distance passes over the rows against themselves, no neighbour
+        lists.  Exactly one of radius= and threshold= (as the radius calls); a row is a core row when
+        at least min_samples rows, itself included, lie within the threshold.  Returns (labels int32
+        [n]: clusters 0, 1, ... in ascending order of their smallest row, a border row the smallest
+        cluster number among its core neighbours, -1 noise; count int32 [n] or None with count=False;
+        summary int64 [4] = clusters, core rows, border rows, noise rows).  labels / count may be
+        tensors to fill."""
+        thr = self._threshold(radius, threshold)
+        if int(min_samples) != min_samples:
+            raise KnnError(KNN_EINVAL, f"min_samples must be an integer, got {min_samples!r}")
+        self._on_device(train)
+        self._note_train(train)
+        tr = _device_dataset(train, None, d)
+        labels, count, summary = self._dbscan_out(tr.n, labels, count, train.device)
+        self._check(self.lib.knn_dbscan_device(
+            self.h, ctypes.byref(tr), thr, int(min_samples), labels.data_ptr(), _opt_ptr(count), summary.data_ptr(),
+            self._stream(stream, train)))
+        return labels, count, summary
+
+    def dbscan_lists_device(self, offsets, idx, min_samples=5, labels=None, count=False, stream=None):
+        """The same clustering on CSR lists the caller holds (knn_dbscan_lists_device): offsets int64
+        [n + 1] and idx int32 of a self-join whose lists hold the row itself
+        (radius_neighbors_device(train, train, ...)), or lists concatenated from train shards.
+        Returns (labels, count or None, summary) as dbscan_device."""
+        import torch
+        self._on_device(idx)
+        _check_tensor(offsets, "offsets", torch.int64, 1)
+        _check_tensor(idx, "idx", torch.int32)
+        if int(min_samples) != min_samples:
+            raise KnnError(KNN_EINVAL, f"min_samples must be an integer, got {min_samples!r}")
+        n = offsets.numel() - 1
+        labels, count, summary = self._dbscan_out(n, labels, count, idx.device)
+        # (at least one element: an empty tensor has no address to hand to the library)
+        ip = idx if idx.numel() else torch.zeros(1, dtype=torch.int32, device=idx.device)
+        self._check(self.lib.knn_dbscan_lists_device(
+            self.h, n, offsets.data_ptr(), ip.data_ptr(), int(min_samples), labels.data_ptr(), _opt_ptr(count),
+            summary.data_ptr(), self._stream(stream, idx)))
+        return labels, count, summary
+
     # radius sweep (knn_amd.h "Radius sweep")
     def _thresholds(self, radii, thresholds):
         """The binary32 thresholds of a sweep: exactly one of radii= (each float32(r) * float32(r)
@@ -1264,8 +1324,8 @@ class Context:
         return out
 
     def stats(self):
-        v = (ctypes.c_int64 * 18)()
-        self.lib.knn_last_stats(self.h, v, 18)
+        v = (ctypes.c_int64 * 20)()
+        self.lib.knn_last_stats(self.h, v, 20)
         return {"candidates": v[0], "fallback_queries": v[1], "train_segments": v[2],
                 "filter_operands": FILTER_OPERANDS.get(v[3], v[3]), "rerun_split": bool(v[4]),
                 "fused_norm": bool(v[5]), "h2d_train_bytes": v[6], "h2d_query_bytes": v[7],
@@ -1274,7 +1334,7 @@ class Context:
                 "filter_element": FILTER_ELEMENTS.get(v[11], v[11]) if v[3] in (1, 2, 3) else None,
                 "parked_passes": v[12], "radius_form": RADIUS_FORMS.get(v[13], v[13]),
                 "radius_exact_pairs": v[14], "filter_width": v[15], "filter_chunks": v[16],
-                "seeded_queries": v[17]}
+                "seeded_queries": v[17], "dbscan_border_queries": v[18], "dbscan_unions": v[19]}
 
     def last_seed(self, nq):
         """Test hook (knn_debug_last_seed): the thresholds the int8 filter's seed pass published in the
@@ -1617,6 +1677,17 @@ def lof_outliers(scores, threshold=1.5):
         return torch.nonzero(scores > threshold).reshape(-1)
     with np.errstate(invalid="ignore"):
         return np.flatnonzero(np.asarray(scores) > threshold).astype(np.int64)
+
+
+def dbscan_sizes(labels):
+    """The cluster sizes of DBSCAN labels [n] (noise, -1, is not counted): int64 [clusters], entry c
+    the rows of cluster c; a tensor for a tensor, else a numpy array."""
+    if hasattr(labels, "cpu"):
+        import torch
+        lab = labels.reshape(-1).to(torch.int64)
+        return torch.bincount(lab[lab >= 0])
+    lab = np.asarray(labels).reshape(-1).astype(np.int64)
+    return np.bincount(lab[lab >= 0]).astype(np.int64)
 
 
 def _host_targets(t, name, n):

@@ -1125,6 +1125,49 @@ float* KNN_lof(ArffData* train, int k_lo, int k_hi) {
     return lof;
 }
 
+// DBSCAN of the train rows on the first device (knn_amd.h "DBSCAN"), staged as KNN_lof: the cached
+// train upload, knn_dbscan_device on the context's stream, the n labels back
+int* KNN_dbscan(ArffData* train, float radius, int min_samples, long* summary) {
+    const KnnFlatView& tr = train->flat();
+    if (!(radius >= 0.0f)) throwf("KNN_dbscan: radius=%g must be >= 0", (double)radius);
+    if (min_samples < 1) throwf("KNN_dbscan: min_samples=%d must be >= 1", min_samples);
+    const size_t n = (size_t)tr.n;
+    int* labels = (int*)std::malloc(sizeof(int) * (n > 0 ? n : 1));
+    if (!labels) throwf("KNN_dbscan: out of memory");
+    int64_t sum[4] = {0, 0, 0, 0};
+    std::string why;
+    knn_status s = KNN_OK;
+    try {
+        std::vector<knn_ctx*>& cs = contexts();
+        knn_ctx* c = cs[0];
+        std::lock_guard<std::mutex> busy(*devices().busy[0]);
+        // the reported distance is squared under the Euclidean metric (one binary32 product)
+        const float thr = knn_get_metric(c) == KNN_METRIC_SQEUCLIDEAN ? radius * radius : radius;
+        const int dev = knn_ctx_device(c);
+        hipStream_t st = (hipStream_t)knn_ctx_stream(c);
+        knn_dataset htr{tr.feat.data(), tr.labels.data(), tr.n, tr.d, tr.ld, KNN_F32}, dtr{};
+        s = knn_set_generation(c, tr.uid);
+        if (s == KNN_OK) s = knn_ctx_train_device(c, &htr, &dtr);
+        DevMem dlab(dev, sizeof(int32_t) * n), dsum(dev, sizeof(int64_t) * 4);
+        if (s == KNN_OK && (!dlab.p || !dsum.p)) throwf("KNN_dbscan: device allocation failed");
+        if (s == KNN_OK)
+            s = knn_dbscan_device(c, &dtr, thr, min_samples, (int32_t*)dlab.p, nullptr, (int64_t*)dsum.p, st);
+        if (s == KNN_OK && ((n > 0 && hipMemcpy(labels, dlab.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost) != hipSuccess) ||
+                            hipMemcpy(sum, dsum.p, sizeof(sum), hipMemcpyDeviceToHost) != hipSuccess))
+            throwf("KNN_dbscan: download failed");
+        if (s != KNN_OK) why = knn_last_error(c);
+    } catch (...) {
+        std::free(labels);
+        throw;
+    }
+    if (s != KNN_OK) {
+        std::free(labels);
+        throwf("KNN_dbscan: %s (status %d)", why.c_str(), (int)s);
+    }
+    for (int i = 0; summary && i < 4; i++) summary[i] = (long)sum[i];
+    return labels;
+}
+
 void* KNN(void* params) {
     arguments* a = static_cast<arguments*>(params);
     predict_range(a->train, a->test, a->k, a->start, a->end, predictions + a->start);

@@ -11,6 +11,9 @@
 //     k_tn_rows x2 -> k_radius_gemm (k_radius_tile behind it, gated on unsafe norms)
 //   local outlier factor (knn_lof_*): the vote-less top-k pass of ALL rows, then k_lof_compact ->
 //     k_lof_lrd -> k_lof_score (two gather rounds over the rows' own tables)
+//   DBSCAN (knn_dbscan_*): the radius count pass of the train set against itself -> k_dbscan_init ->
+//     the pass in RADIUS_LINK mode (a lock-free union-find) -> k_dbscan_flatten -> k_radius_scan ->
+//     k_dbscan_labels -> k_dbscan_candidates -> the pass in RADIUS_BORDER mode -> k_dbscan_summary
 // Train-sharded runs use the same pipeline per shard with the vote
 // replaced by a packed (dist, global idx, label) neighbour list, then k_merge_vote.
 #include <hip/hip_runtime.h>
@@ -140,6 +143,10 @@ struct knn_ctx {
     DBuf rd_segcnt, rd_base, rd_cc, rd_scores;
     // the radius sweep's bucket histograms: hist [nq][R + 1] | chist [nq][R + 1][C], int32
     DBuf rd_sweep;
+    // DBSCAN: the int32 tables parent | root | isroot | cluster | cand [5][n], the int64 scan of the
+    // roots [n + 1], the summary words {clusters, core, border, noise, unions} and the neighbour
+    // counts a caller did not ask for
+    DBuf db_tab, db_offs, db_info, db_count;
     // the pass rd_segcnt's counts came from: a fill whose pass has the same key takes them as they
     // are instead of counting again.  (Rows rewritten in place in between are caught where stale
     // counts would matter: the fill checks every (segment, query) count against its own.)
@@ -182,7 +189,7 @@ struct knn_ctx {
     bool stage_open = false;  // the last stage_begin recorded an event (profile = 3 skips some)
     std::vector<float> stage_ms;
     std::vector<const char*> stage_names;
-    int64_t stats[18] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
+    int64_t stats[20] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
                                                       // operand type, rerun, fused, train / query H2D
                                                       // bytes, train-side filter operands from the cache,
                                                       // MFMA form, queries per wave, [11] the filter's
@@ -192,6 +199,8 @@ struct knn_ctx {
                                                       // [13] the radius pass's form (0 direct, 1 MFMA,
                                                       // 2 direct because of unsafe norms), [14] the
                                                       // pairs its MFMA form evaluated exactly
+                                                      // (profile = 2 only), [18] DBSCAN's border
+                                                      // candidates, [19] its successful unions
                                                       // (profile = 2 only)
     int64_t rerun_stats[4] = {0, -1, 0, 0};  // segments, operand type, fused, operand width of AUTO's gated split re-run
     int num_cus = 256;
@@ -234,7 +243,8 @@ knn_status fail(knn_ctx* c, knn_status s, const char* fmt, ...) {
 // 3.44 -> 3.56 ms per step, A 22.58 -> 22.73 (scripts/event_overhead.py, profiles/r04n).
 static bool hot_stage(const char* n) {
     static const char* const hot[] = {"gemm_filter", "rescore", "direct_tile", "metric_tile", "exact_scan", "merge_vote",
-                                      "exchange", "radius_count", "radius_fill", "radius_sweep"};
+                                      "exchange", "radius_count", "radius_fill", "radius_sweep", "dbscan_link",
+                                      "dbscan_border"};
     for (const char* h : hot)
         if (!strcmp(n, h)) return true;
     return false;
@@ -387,6 +397,8 @@ void collect_stages(knn_ctx* c) {
 
 knn_status check_status(knn_ctx* c, const int32_t* ctrl) {
     const int32_t status = ctrl[0];
+    if (status & KNN_STATUS_UF_LIMIT)
+        return fail(c, KNN_EHIP, "dbscan: internal error: a union-find loop reached its iteration cap");
     if (status & KNN_STATUS_BAD_LABEL) return fail(c, KNN_EINVAL, "a train label is outside [0, num_classes)");
     if (status & KNN_STATUS_UNSORTED)
         return fail(c, KNN_EINVAL, "merge: a source neighbour list is not ascending by (distance, index)");
@@ -1210,7 +1222,7 @@ void knn_destroy(knn_ctx* c) {
                     &c->rg_part, &c->rg_zero, &c->rg_targets, &c->rd_segcnt, &c->rd_base, &c->rd_cc, &c->rd_scores,
                     &c->rm_tnorm, &c->rm_tmax, &c->rm_tsmax, &c->rm_tblk, &c->rm_tctrl, &c->rm_qnorm, &c->rm_qstat,
                     &c->rm_qop, &c->rm_exact, &c->lof_idx, &c->lof_dist, &c->lof_cidx, &c->lof_delta, &c->lof_kd,
-                    &c->lof_lrd, &c->lof_qlrd})
+                    &c->lof_lrd, &c->lof_qlrd, &c->rd_sweep, &c->db_tab, &c->db_offs, &c->db_info, &c->db_count})
         b->release();
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; i++) {
@@ -1350,7 +1362,7 @@ knn_dataset offset_rows(const knn_dataset& x, int64_t r0, int64_t n) {
 
 void reset_stats(knn_ctx* c) {
     c->stages.clear();
-    for (int i = 0; i < 18; i++) c->stats[i] = 0;
+    for (int i = 0; i < 20; i++) c->stats[i] = 0;
     c->seed_nq = 0;
     c->stats[3] = -1;
 }
@@ -2534,6 +2546,179 @@ knn_status knn_radius_fill_device(knn_ctx* c, const knn_dataset* tr, const knn_d
     return s;
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------
+// DBSCAN (knn_amd.h "DBSCAN"): the radius passes' RADIUS_LINK / RADIUS_BORDER modes and
+// knn_dbscan.hip's kernels around them
+// ---------------------------------------------------------------------------------
+namespace {
+
+struct DbscanBufs {
+    int32_t *count, *parent, *root, *isroot, *cluster, *cand, *nb;
+    int64_t *offs, *info;
+    unsigned long long* unions;
+};
+
+// the tables of a call over n rows; count is the caller's when it asked for it.  nb is a spare
+// status word (ctrl[3], zero at a call's start, read back and zeroed by k_finish): the host learns
+// the number of border candidates without a copy of its own.
+knn_status dbscan_bufs(knn_ctx* c, int64_t n, int32_t* d_count, hipStream_t st, DbscanBufs* b) {
+    HIP_OR_FAIL(c, c->db_tab.ensure(sizeof(int32_t) * 5 * (size_t)n));
+    HIP_OR_FAIL(c, c->db_offs.ensure(sizeof(int64_t) * ((size_t)n + 1)));
+    HIP_OR_FAIL(c, c->db_info.ensure(sizeof(int64_t) * 8));
+    if (!d_count) HIP_OR_FAIL(c, c->db_count.ensure(sizeof(int32_t) * (size_t)n));
+    int32_t* t = c->db_tab.as<int32_t>();
+    b->count = d_count ? d_count : c->db_count.as<int32_t>();
+    b->parent = t; b->root = t + n; b->isroot = t + 2 * n; b->cluster = t + 3 * n; b->cand = t + 4 * n;
+    b->nb = c->ctrl.as<int32_t>() + 3;
+    b->offs = c->db_offs.as<int64_t>();
+    b->info = c->db_info.as<int64_t>();
+    b->unions = c->profile == 2 ? reinterpret_cast<unsigned long long*>(b->info + 4) : nullptr;
+    HIP_OR_FAIL(c, hipMemsetAsync(b->info, 0, sizeof(int64_t) * 8, st));
+    return KNN_OK;
+}
+
+// after the link step: every core row's root -> cluster numbers -> labels and the cluster table
+knn_status dbscan_number(knn_ctx* c, const DbscanBufs& b, int64_t n, int32_t min_samples, int32_t* d_labels,
+                         hipStream_t st) {
+    stage_begin(c, st, "dbscan_labels");
+    HIP_OR_FAIL(c, knn_launch_dbscan_flatten(b.parent, b.count, min_samples, n, b.root, b.isroot, c->ctrl.as<int32_t>(), st));
+    HIP_OR_FAIL(c, knn_launch_radius_scan(b.isroot, 1, n, nullptr, b.offs, st));
+    HIP_OR_FAIL(c, knn_launch_dbscan_labels(b.root, b.offs, n, d_labels, b.cluster, st));
+    stage_end(c, st);
+    return KNN_OK;
+}
+
+// the summary, the call's one synchronisation, and the counters
+knn_status dbscan_end(knn_ctx* c, const DbscanBufs& b, int64_t n, int32_t min_samples, const int32_t* d_labels,
+                      int64_t* d_summary, hipStream_t st, int form, bool passes) {
+    stage_begin(c, st, "dbscan_labels");
+    HIP_OR_FAIL(c, knn_launch_dbscan_summary(d_labels, b.count, min_samples, b.offs, n, b.info, st));
+    if (d_summary) HIP_OR_FAIL(c, hipMemcpyAsync(d_summary, b.info, sizeof(int64_t) * 4, hipMemcpyDeviceToDevice, st));
+    stage_end(c, st);
+    const knn_status s = passes ? radius_finish(c, st, form) : finish_call(c, st);
+    if (s == KNN_OK) {
+        c->stats[18] = c->ctrl_host[3];
+        unsigned long long u = 0;
+        if (b.unions && hipMemcpy(&u, b.unions, sizeof(u), hipMemcpyDeviceToHost) == hipSuccess) c->stats[19] = (int64_t)u;
+    }
+    return s;
+}
+
+}  // namespace
+
+extern "C" {
+
+knn_status knn_dbscan_device(knn_ctx* c, const knn_dataset* tr, float thr, int32_t min_samples, int32_t* d_labels,
+                             int32_t* d_count, int64_t* d_summary, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    reset_stats(c);
+    knn_status s;
+    if (min_samples < 1) return fail(c, KNN_EINVAL, "dbscan: min_samples=%d must be >= 1", min_samples);
+    if ((s = radius_check(c, tr, tr, thr, -1, false)) != KNN_OK) return s;
+    const int64_t n = tr->n;
+    if (n > 0 && !d_labels) return fail(c, KNN_EINVAL, "dbscan: d_labels is NULL");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (n == 0) {
+        if (d_summary) HIP_OR_FAIL(c, hipMemsetAsync(d_summary, 0, sizeof(int64_t) * 4, st));
+        HIP_OR_FAIL(c, hipStreamSynchronize(st));
+        return KNN_OK;
+    }
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    // the three passes share the count pass's form and segments: the link pass is routed on (n, n),
+    // the border pass goes with it (its query count is known on the device alone)
+    const int form = radius_policy(c->metric, tr->d, n, n, c->algo);
+    RadiusTileArgs a = radius_args(c, tr, tr, thr, -1, 0, form);
+    RadiusGemmArgs g{};
+    if (form) {
+        if ((s = radius_prep(c, tr, tr, a, st, &g)) != KNN_OK) return s;
+        a.gate = a.status;
+    }
+    DbscanBufs b{};
+    if ((s = dbscan_bufs(c, n, d_count, st, &b)) != KNN_OK) return s;
+    c->rd_key.valid = false;
+    if (a.nseg == 1) {
+        a.seg_count = b.count;
+    } else {
+        HIP_OR_FAIL(c, c->rd_segcnt.ensure(sizeof(int32_t) * (size_t)n * a.nseg));
+        a.seg_count = c->rd_segcnt.as<int32_t>();
+    }
+    stage_begin(c, st, "radius_count");
+    if (form) {
+        g.seg_count = a.seg_count;
+        HIP_OR_FAIL(c, knn_launch_radius_gemm(g, RADIUS_COUNT, st));
+    }
+    HIP_OR_FAIL(c, knn_launch_radius_tile(a, c->metric, RADIUS_COUNT, st));
+    stage_end(c, st);
+    if (a.nseg > 1) {
+        stage_begin(c, st, "radius_scan");
+        HIP_OR_FAIL(c, knn_launch_radius_scan(a.seg_count, a.nseg, n, b.count, nullptr, st));
+        stage_end(c, st);
+    }
+    stage_begin(c, st, "dbscan_labels");
+    HIP_OR_FAIL(c, knn_launch_dbscan_init(b.parent, n, st));
+    stage_end(c, st);
+
+    a.db.dcount = b.count; a.db.min_samples = min_samples; a.db.parent = b.parent; a.db.unions = b.unions;
+    a.db.cand = b.cand; a.db.nb = b.nb; a.db.cluster = b.cluster; a.db.out_labels = d_labels;
+    g.db = a.db;
+    stage_begin(c, st, "dbscan_link");
+    if (form) HIP_OR_FAIL(c, knn_launch_radius_gemm(g, RADIUS_LINK, st));
+    HIP_OR_FAIL(c, knn_launch_radius_tile(a, c->metric, RADIUS_LINK, st));
+    stage_end(c, st);
+
+    if ((s = dbscan_number(c, b, n, min_samples, d_labels, st)) != KNN_OK) return s;
+
+    stage_begin(c, st, "dbscan_border");
+    HIP_OR_FAIL(c, knn_launch_dbscan_candidates(b.count, min_samples, n, b.cand, b.nb, st));
+    if (form) HIP_OR_FAIL(c, knn_launch_radius_gemm(g, RADIUS_BORDER, st));
+    HIP_OR_FAIL(c, knn_launch_radius_tile(a, c->metric, RADIUS_BORDER, st));
+    stage_end(c, st);
+
+    return dbscan_end(c, b, n, min_samples, d_labels, d_summary, st, form, true);
+}
+
+knn_status knn_dbscan_lists_device(knn_ctx* c, int64_t n, const int64_t* d_offsets, const int32_t* d_idx,
+                                   int32_t min_samples, int32_t* d_labels, int32_t* d_count, int64_t* d_summary,
+                                   void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    reset_stats_keep_radius(c);
+    if (min_samples < 1) return fail(c, KNN_EINVAL, "dbscan lists: min_samples=%d must be >= 1", min_samples);
+    if (n < 0 || n > 0x7fffffffLL) return fail(c, KNN_EINVAL, "dbscan lists: n=%lld outside [0, 2^31-1]", (long long)n);
+    // (d_idx may be NULL only when the lists are empty, which the host cannot know: refuse)
+    if (n > 0 && (!d_offsets || !d_idx || !d_labels))
+        return fail(c, KNN_EINVAL, "dbscan lists: d_offsets / d_idx / d_labels is NULL");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (n == 0) {
+        if (d_summary) HIP_OR_FAIL(c, hipMemsetAsync(d_summary, 0, sizeof(int64_t) * 4, st));
+        HIP_OR_FAIL(c, hipStreamSynchronize(st));
+        return KNN_OK;
+    }
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    knn_status s;
+    DbscanBufs b{};
+    if ((s = dbscan_bufs(c, n, d_count, st, &b)) != KNN_OK) return s;
+    int32_t* status = c->ctrl.as<int32_t>();
+    stage_begin(c, st, "dbscan_labels");
+    HIP_OR_FAIL(c, knn_launch_dbscan_lists_count(d_offsets, n, b.count, status, st));
+    HIP_OR_FAIL(c, knn_launch_dbscan_init(b.parent, n, st));
+    stage_end(c, st);
+    stage_begin(c, st, "dbscan_link");
+    HIP_OR_FAIL(c, knn_launch_dbscan_lists_link(d_offsets, d_idx, n, b.count, min_samples, b.parent, status, b.unions, st));
+    stage_end(c, st);
+    if ((s = dbscan_number(c, b, n, min_samples, d_labels, st)) != KNN_OK) return s;
+    stage_begin(c, st, "dbscan_border");
+    HIP_OR_FAIL(c, knn_launch_dbscan_candidates(b.count, min_samples, n, b.cand, b.nb, st));
+    HIP_OR_FAIL(c, knn_launch_dbscan_lists_border(d_offsets, d_idx, n, b.count, b.cand, b.nb, b.cluster, d_labels, st));
+    stage_end(c, st);
+    return dbscan_end(c, b, n, min_samples, d_labels, d_summary, st, 0, false);
+}
+
 int32_t knn_radius_policy(int32_t metric, int32_t dtype, int32_t d, int64_t n_train, int64_t n_query, int32_t algo,
                           int32_t* form) {
     if (!form || d <= 0 || n_train < 0 || n_query < 0 || (dtype != KNN_F32 && dtype != KNN_BF16) ||
@@ -2981,7 +3166,7 @@ int32_t knn_stage_times(const knn_ctx* c, const char** names, float* ms, int32_t
 
 int32_t knn_last_stats(const knn_ctx* c, int64_t* out, int32_t n) {
     if (!c || !out) return 0;
-    int32_t m = std::min(n, 18);
+    int32_t m = std::min(n, 20);
     for (int32_t i = 0; i < m; i++) out[i] = c->stats[i];
     return m;
 }

@@ -3,6 +3,7 @@
 //   knn_cli train.arff test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]]
 //           [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress]
 //           [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]] [--lof[=KLO] [--lof-threshold=T]]
+//           [--dbscan=R [--min-samples=M]]
 //
 // Same positional arguments as ./main (main.cpp:114-122; k parsed with strtol) plus the
 // optional worker count of ./multi-thread (multi-thread.cpp:135-143), here the number of
@@ -39,6 +40,12 @@
 // row.  Composes with --metric=.  With --regress, --radius=, --radii=, --weights= or --sweep, with a
 // KLO that is no integer in [1, K], a K above 255 or a T that is no number, it prints a usage error
 // and exits 1.
+// --dbscan=R [--min-samples=M]: DBSCAN (KNN_dbscan) of the train file's rows at radius R, a core row
+// having at least M rows (default 5, itself included) within it; K and the test path keep their
+// positions and are not read.  One line: the clusters and the core, border and noise rows.  Composes
+// with --metric=.  With any other mode switch (--sweep, --weights=, --regress, --radius=, --radii=,
+// --outlier=, --lof), an R that is not a number >= 0 or an M that is no integer >= 1, it prints a
+// usage error and exits 1.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -64,7 +71,11 @@ static int run(int argc, char* argv[]) {
     bool lof = false, weights_given = false;
     const char* lof_arg = nullptr;
     const char* lof_thr_arg = nullptr;
+    const char* dbscan_arg = nullptr;
+    const char* min_samples_arg = nullptr;
+    bool outlier_given = false;
     for (int i = 0; i < argc; i++) {
+        if (!std::strncmp(argv[i], "--outlier=", 10)) outlier_given = true;
         if (!std::strncmp(argv[i], "--weights=", 10)) weights_given = true;
         if (!std::strncmp(argv[i], "--shard=", 8)) setenv("KNN_AMD_SHARD", argv[i] + 8, 1);
         else if (!std::strcmp(argv[i], "--sweep")) sweep = true;
@@ -73,6 +84,8 @@ static int run(int argc, char* argv[]) {
         else if (!std::strcmp(argv[i], "--lof")) lof = true;
         else if (!std::strncmp(argv[i], "--lof=", 6)) { lof = true; lof_arg = argv[i] + 6; }
         else if (!std::strncmp(argv[i], "--lof-threshold=", 16)) lof_thr_arg = argv[i] + 16;
+        else if (!std::strncmp(argv[i], "--dbscan=", 9)) dbscan_arg = argv[i] + 9;
+        else if (!std::strncmp(argv[i], "--min-samples=", 14)) min_samples_arg = argv[i] + 14;
         else if (!std::strncmp(argv[i], "--radius=", 9)) radius_arg = argv[i] + 9;
         else if (!std::strncmp(argv[i], "--radii=", 8)) radii_arg = argv[i] + 8;
         else if (!std::strncmp(argv[i], "--outlier=", 10)) outlier = (int)std::strtol(argv[i] + 10, NULL, 10);
@@ -93,7 +106,7 @@ static int run(int argc, char* argv[]) {
     }
     argc = n;
     if (argc != 4 && argc != 5) {
-        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress] [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]] [--lof[=KLO] [--lof-threshold=T]]"
+        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress] [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]] [--lof[=KLO] [--lof-threshold=T]] [--dbscan=R [--min-samples=M]]"
                   << std::endl;
         std::exit(0);
     }
@@ -150,15 +163,51 @@ static int run(int argc, char* argv[]) {
             std::exit(1);
         }
     }
+    float dbscan_r = 0.0f;
+    int min_samples = 5;
+    if (dbscan_arg || min_samples_arg) {
+        bool ok = dbscan_arg && !sweep && !regress && !radius_arg && !radii_arg && !weights_given && !outlier_given &&
+                  !lof && !lof_thr_arg;
+        if (ok) {
+            char* end = nullptr;
+            dbscan_r = std::strtof(dbscan_arg, &end);
+            ok = end != dbscan_arg && *end == '\0' && dbscan_r >= 0.0f;  // (NaN fails >=)
+        }
+        if (ok && min_samples_arg) {
+            char* end = nullptr;
+            const long v = std::strtol(min_samples_arg, &end, 10);
+            ok = end != min_samples_arg && *end == '\0' && v >= 1 && v <= 0x7fffffffL;
+            min_samples = (int)v;
+        }
+        if (!ok) {
+            std::cerr << "usage: --dbscan=R needs a number R >= 0, --min-samples=M an integer M >= 1, and does not combine "
+                         "with --sweep, --weights=, --regress, --radius=, --radii=, --outlier= or --lof"
+                      << std::endl;
+            std::exit(1);
+        }
+    }
     if (argc == 5) setenv("KNN_AMD_DEVICES", argv[4], 1);
 
     ArffParser parserTrain(argv[1]);
     ArffParser parserTest(argv[2]);
     ArffData* train = parserTrain.parse();
-    ArffData* test = (loo || lof) ? train : parserTest.parse();
+    ArffData* test = (loo || lof || dbscan_arg) ? train : parserTest.parse();
     knn_amd_init();
 
     struct timespec start, end;
+    if (dbscan_arg) {
+        long summary[4] = {0, 0, 0, 0};
+        int* labels = KNN_dbscan(train, dbscan_r, min_samples, summary);
+        printf("The radius-%g DBSCAN (min_samples %d) of %s found %ld clusters: %ld core, %ld border, %ld noise rows\n",
+               (double)dbscan_r, min_samples, argv[1], summary[0], summary[1], summary[2], summary[3]);
+        if (const char* p = std::getenv("KNN_CLI_PRED_OUT")) {  // test hook: dump the labels
+            FILE* f = std::fopen(p, "w");
+            for (long i = 0; i < train->num_instances(); i++) std::fprintf(f, "%d\n", labels[i]);
+            std::fclose(f);
+        }
+        std::free(labels);
+        return 0;
+    }
     if (lof) {
         clock_gettime(CLOCK_MONOTONIC_RAW, &start);
         float* all = KNN_lof(train, lof_lo, k);

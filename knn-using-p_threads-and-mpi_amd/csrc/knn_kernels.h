@@ -11,6 +11,7 @@
 #define KNN_STATUS_BAD_DIST 16     // k_vote_weighted: a caller-supplied distance is NaN or negative
 #define KNN_STATUS_BAD_OFFSETS 32  // radius fill / vote: the CSR offsets do not belong to this call
 #define KNN_STATUS_BAD_INDEX 64    // radius vote / regression: a list index is outside [0, n_train)
+#define KNN_STATUS_UF_LIMIT 128    // DBSCAN: a union-find loop reached its iteration cap (an internal error)
 
 // candidate-list capacity per query on the GEMM path (entries = 64 * CAPW)
 #define KNN_RESCORE_CAPW 32
@@ -254,13 +255,27 @@ hipError_t knn_metric_units(int metric, int k, int elem, int d, int C, int* quer
 // fills dc / stride / vote_lds / n_qblocks and launches n_qblocks * nseg blocks
 hipError_t knn_launch_metric_tile(DirectTileArgs a, int metric, hipStream_t st);
 
-// Radius neighbours (knn_radius.hip; knn_amd.h "Radius neighbours").  k_radius_tile<M, E, FILL>:
+// Radius neighbours (knn_radius.hip; knn_amd.h "Radius neighbours").  k_radius_tile<M, E, MODE>:
 // k_metric_tile's block shape, tile staging and geometry (knn_direct_tile_geom) for all three
 // metrics, 8 queries per wave for every shape, the selection replaced by D <= thr.
 #define KNN_RADIUS_QW 8
 // class counts up to this many live in the count pass's per-wave LDS block [8][Cpad] (16 KiB a
 // block at the limit, beside the tiles); above it they are integer atomics on class_counts
 #define KNN_RADIUS_LDS_MAX_C 64
+// what a distance pass does with a passing pair: count it, store it, or one of DBSCAN's two modes
+// (knn_amd.h "DBSCAN"): LINK unions core rows q > t, BORDER takes the smallest cluster number among
+// a candidate's core neighbours
+enum { RADIUS_COUNT = 0, RADIUS_FILL = 1, RADIUS_LINK = 2, RADIUS_BORDER = 3 };
+// the DBSCAN modes' tables (RadiusTileArgs / RadiusGemmArgs .db; a self-join: test == train, nq == nt)
+struct RadiusDbscanArgs {
+    const int32_t* dcount; int32_t min_samples;  // LINK: row i is core iff dcount[i] >= min_samples
+    int32_t* parent;             // LINK: the union-find forest [nt]
+    unsigned long long* unions;  // LINK, optional (profile = 2): += successful hooks, one add per wave
+    // BORDER: query q is train row cand[q], q < *nb (blocks past it return at once); cluster [nt]
+    // is a core row's cluster number and -1 for every other row; the minimum goes into
+    // out_labels[cand[q]] with an unsigned atomicMin (-1 is the largest value)
+    const int32_t* cand; const int32_t* nb; const int32_t* cluster; int32_t* out_labels;
+};
 struct RadiusTileArgs {
     const void* train; const int32_t* labels; int64_t nt; int ld_t;
     const void* test; int ld_q; int64_t nq;
@@ -281,9 +296,11 @@ struct RadiusTileArgs {
     // optional: a status word; the kernel runs only when it says KNN_STATUS_GEMM_UNSAFE (the pass
     // behind k_radius_gemm, which returns at once in that case)
     const int32_t* gate;
+    RadiusDbscanArgs db;       // RADIUS_LINK / RADIUS_BORDER only
 };
 hipError_t knn_radius_units(int metric, int elem, int d, int C, int* queries_per_unit, int* units_per_cu);
-hipError_t knn_launch_radius_tile(RadiusTileArgs a, int metric, bool fill, hipStream_t st);
+// mode: RADIUS_COUNT / _FILL / _LINK / _BORDER
+hipError_t knn_launch_radius_tile(RadiusTileArgs a, int metric, int mode, hipStream_t st);
 // whether the count pass writes pred / correct itself (no k_radius_argmax behind it)
 bool knn_radius_pass_votes(int C, int nseg);
 // count (optional, may alias seg_count when nseg == 1) and the int64 exclusive scan offsets [nq + 1] (optional)
@@ -306,7 +323,7 @@ struct RadiusVoteArgs {
 hipError_t knn_launch_radius_vote(const RadiusVoteArgs& a, hipStream_t st);
 hipError_t knn_launch_radius_regress(const RadiusVoteArgs& a, hipStream_t st);
 
-// The MFMA-filtered form of the radius pass (knn_radius_gemm.hip): k_radius_gemm<RB, E, FILL>,
+// The MFMA-filtered form of the radius pass (knn_radius_gemm.hip): k_radius_gemm<RB, E, MODE>,
 // squared Euclidean, d in {64, 128, 256}.  8 waves a block, 32 queries a wave; train segments are
 // multiples of 64 rows.  tblk: the fused filter's train tile blocks of 64 rows (knn_launch_tn_rows
 // with bn = 64 over the 64-row grid), qop / qnorm / qstat its query operand, tsmax the maxima of the
@@ -330,12 +347,37 @@ struct RadiusGemmArgs {
     int32_t* idx; float* dist;
     int32_t* status;           // a set KNN_STATUS_GEMM_UNSAFE bit skips the pass
     unsigned long long* exact_cnt;  // optional (profile = 2): += the pairs given the exact evaluation
+    RadiusDbscanArgs db;       // RADIUS_LINK / RADIUS_BORDER only
 };
 bool knn_radius_gemm_supported(int d);
 // bytes of one 64-row tile block of the train operand
 size_t knn_radius_gemm_tile_bytes(int d);
 hipError_t knn_radius_gemm_units(int elem, int d, int* queries_per_unit, int* units_per_cu);
-hipError_t knn_launch_radius_gemm(RadiusGemmArgs a, bool fill, hipStream_t st);
+hipError_t knn_launch_radius_gemm(RadiusGemmArgs a, int mode, hipStream_t st);
+
+// DBSCAN's small kernels (knn_dbscan.hip; knn_amd.h "DBSCAN").  count [n]: a row's neighbours, itself
+// included; a row is core iff count >= min_samples.  parent / root / isroot / cluster / cand: int32
+// [n] workspace, nb one int32 (zeroed by the caller), offsets the int64 exclusive scan of isroot
+// (k_radius_scan, one segment), info int64 [4] {clusters, core, border, noise} (zeroed by the
+// caller).  unions: optional, += successful hooks.
+hipError_t knn_launch_dbscan_init(int32_t* parent, int64_t n, hipStream_t st);
+hipError_t knn_launch_dbscan_flatten(int32_t* parent, const int32_t* count, int32_t min_samples, int64_t n, int32_t* root,
+                                     int32_t* isroot, int32_t* status, hipStream_t st);
+hipError_t knn_launch_dbscan_labels(const int32_t* root, const int64_t* offsets, int64_t n, int32_t* labels,
+                                    int32_t* cluster, hipStream_t st);
+hipError_t knn_launch_dbscan_candidates(const int32_t* count, int32_t min_samples, int64_t n, int32_t* cand, int32_t* nb,
+                                        hipStream_t st);
+hipError_t knn_launch_dbscan_summary(const int32_t* labels, const int32_t* count, int32_t min_samples,
+                                     const int64_t* offsets, int64_t n, int64_t* info, hipStream_t st);
+// the same clustering on CSR lists [list_offsets[i], list_offsets[i + 1]) of idx
+hipError_t knn_launch_dbscan_lists_count(const int64_t* list_offsets, int64_t n, int32_t* count, int32_t* status,
+                                         hipStream_t st);
+hipError_t knn_launch_dbscan_lists_link(const int64_t* list_offsets, const int32_t* idx, int64_t n, const int32_t* count,
+                                        int32_t min_samples, int32_t* parent, int32_t* status, unsigned long long* unions,
+                                        hipStream_t st);
+hipError_t knn_launch_dbscan_lists_border(const int64_t* list_offsets, const int32_t* idx, int64_t n, const int32_t* count,
+                                          const int32_t* cand, const int32_t* nb, const int32_t* cluster, int32_t* labels,
+                                          hipStream_t st);
 
 // The radius sweep (knn_radius_sweep.hip; knn_amd.h "Radius sweep"): R <= 32 non-decreasing
 // thresholds in one distance pass.  k_radius_sweep_tile<M, E> has k_radius_tile's block shape,

@@ -1,7 +1,7 @@
 // knn_radius.hip -- radius neighbours (include/knn_amd.h, "Radius neighbours"): which train rows
 // lie within a fixed threshold of a query, how many, and what they vote.
 //
-//   k_radius_tile<M, E, FILL>  the distance pass: k_metric_tile's skeleton (knn_metric.hip) with
+//   k_radius_tile<M, E, MODE>  the distance pass: k_metric_tile's skeleton (knn_metric.hip) with
 //                              the selection replaced by `D <= thr`, a ballot and a popcount
 //   k_radius_scan              per-(segment, query) counts -> count [nq], int64 offsets [nq + 1]
 //   k_radius_bases             a caller's offsets + the counts -> where each segment's part starts
@@ -25,6 +25,7 @@
 
 #pragma clang fp contract(off)
 #include "knn_radius_dev.h"  // radius_step<M>, load4q
+#include "knn_dbscan_dev.h"  // uf_union
 
 // set bits of m below this lane
 __device__ __forceinline__ int lanes_below(u64 m) {
@@ -32,32 +33,40 @@ __device__ __forceinline__ int lanes_below(u64 m) {
 }
 
 // ---------------------------------------------------------------------------------
-// k_radius_tile<M, E, FILL> (RadiusTileArgs; the launcher fills dc / stride / n_qblocks).  A block
+// k_radius_tile<M, E, MODE> (RadiusTileArgs; the launcher fills dc / stride / n_qblocks).  A block
 // of DT_NW = 8 waves owns 64 queries, 8 per wave (there are no list registers to make room for);
 // lane l of every wave computes the distances of train row r0 + l to its wave's 8 queries.
 //  * Train tiles, query operands, chunks and the accumulator: as k_metric_tile.
 //  * After a tile's last chunk, per query: pass = valid && acc <= thr && row != self (a NaN or
 //    inf distance is never <= thr < FLT_MAX), m = ballot(pass), and the query's wave-uniform
 //    counter grows by popcount(m).
-//  * FILL = false, the count pass: passing lanes add 1 to their label's class count -- in the
+//  * MODE = RADIUS_COUNT, the count pass: passing lanes add 1 to their label's class count -- in the
 //    wave's LDS block [8][Cpad] (classes == 1) or straight in class_counts (classes == 2, integer
 //    atomics).  The tile's 64 labels are loaded once per wave, one per lane, and every one is
 //    range-checked.  At the end seg_count[seg][q] is written; the LDS counts go to class_counts
 //    (stores when nseg == 1, integer atomic adds of the non-zero ones otherwise), and with
 //    fuse_vote (nseg == 1, LDS counts) the wave votes: argmax of the counts, ties to the smallest
 //    label, outlier when the query has no neighbour.
-//  * FILL = true, the fill pass: the part of query q's CSR segment that belongs to this train
+//  * MODE = RADIUS_FILL, the fill pass: the part of query q's CSR segment that belongs to this train
 //    segment starts at base[seg][q] and ends where the next one starts (offsets[q + 1] for the last);
 //    a passing lane stores its row (and distance) at base + counter + (passing lanes below it),
 //    only inside that part and below offsets[q + 1].  A counter that does not end at the part's
 //    length sets KNN_STATUS_BAD_OFFSETS.
+//  * MODE = RADIUS_LINK / RADIUS_BORDER, DBSCAN's two passes over the train set against itself
+//    (RadiusDbscanArgs; knn_amd.h "DBSCAN").  LINK: a passing pair of core rows with row < query
+//    calls uf_union; the scan ends at the block's last query, a block without a core query returns
+//    and a wave without one only stages tiles.  BORDER: query q is train row cand[q] (q < *nb; blocks
+//    past it return), a passing core row offers its cluster number, each lane keeps its minimum per
+//    query, and the wave's minimum goes into out_labels with an integer atomicMin.
 // LDS: 2 tile buffers [64][stride] f32 | per-wave class counts [8 waves][8 queries][Cpad] (classes == 1)
 // ---------------------------------------------------------------------------------
-template <int M, typename E, bool FILL>
+template <int M, typename E, int MODE>
 __global__ __launch_bounds__(64 * DT_NW, 4) void k_radius_tile(RadiusTileArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // (the pass behind k_radius_gemm: only when a norm made the certificate unsafe)
     if (a.gate && !(*a.gate & KNN_STATUS_GEMM_UNSAFE)) return;
+    constexpr bool COUNT = MODE == RADIUS_COUNT, FILL = MODE == RADIUS_FILL;
+    constexpr bool LINK = MODE == RADIUS_LINK, BORDER = MODE == RADIUS_BORDER;
     constexpr int NT = 64 * DT_NW;
     constexpr int QW = KNN_RADIUS_QW;
     const int lane = lane_id();
@@ -69,12 +78,21 @@ __global__ __launch_bounds__(64 * DT_NW, 4) void k_radius_tile(RadiusTileArgs a)
     const int qb = blockIdx.x % a.n_qblocks;
     const int seg = blockIdx.x / a.n_qblocks;
     const int64_t row_begin = (int64_t)seg * a.seg_len;
-    const int64_t row_end = min(a.nt, row_begin + a.seg_len);
+    int64_t row_end = min(a.nt, row_begin + a.seg_len);
+    // (BORDER: the candidates, counted on the device; the grid is sized for every row)
+    int64_t nq = a.nq;
+    if constexpr (BORDER) {
+        nq = *a.db.nb;
+        if ((int64_t)qb * (DT_NW * QW) >= nq) return;
+    }
+    // (LINK: D is symmetric, so the pair (q, t) with t < q makes the union: no row past the
+    // block's last query is scanned)
+    if constexpr (LINK) row_end = min(row_end, min(nq, (int64_t)(qb + 1) * (DT_NW * QW)));
     const E* __restrict__ train = reinterpret_cast<const E*>(a.train);
     const E* __restrict__ test = reinterpret_cast<const E*>(a.test);
     const int d = a.d;
     const float thr = a.thr;
-    const bool lds_counts = !FILL && a.classes == 1;
+    const bool lds_counts = COUNT && a.classes == 1;
 
     int64_t qi[QW];
     const E* qrow[QW];
@@ -82,12 +100,28 @@ __global__ __launch_bounds__(64 * DT_NW, 4) void k_radius_tile(RadiusTileArgs a)
     int run[QW];
     int64_t base[QW];
     int room[QW];
+    [[maybe_unused]] int64_t qr[QW];        // (BORDER) the candidate's train row
+    [[maybe_unused]] uint32_t best[QW];     // (BORDER) this lane's smallest cluster number per query
+    [[maybe_unused]] bool wave_any = true;  // (LINK) one of the wave's queries is a core row
+    [[maybe_unused]] unsigned long long nun = 0;  // (LINK) successful hooks
+    if constexpr (LINK) wave_any = false;
 #pragma unroll
     for (int i = 0; i < QW; i++) {
         qi[i] = (int64_t)qb * (DT_NW * QW) + wave * QW + i;
-        qrow[i] = test + (qi[i] < a.nq ? qi[i] : a.nq - 1) * (int64_t)a.ld_q;
+        if constexpr (BORDER) {
+            qr[i] = qi[i] < nq ? a.db.cand[qi[i]] : 0;
+            best[i] = 0xffffffffu;
+            qrow[i] = test + qr[i] * (int64_t)a.ld_q;
+        } else {
+            qrow[i] = test + (qi[i] < nq ? qi[i] : nq - 1) * (int64_t)a.ld_q;
+        }
         // (a query past the end tests against row -2: nothing passes)
-        self[i] = qi[i] < a.nq ? (a.self_base >= 0 ? a.self_base + qi[i] : -1) : -2;
+        self[i] = qi[i] < nq ? (a.self_base >= 0 ? a.self_base + qi[i] : -1) : -2;
+        if constexpr (LINK) {
+            // (nor for a query that is no core row)
+            if (qi[i] < nq && a.db.dcount[qi[i]] >= a.db.min_samples) wave_any = true;
+            else self[i] = -2;
+        }
         run[i] = 0;
         base[i] = 0;
         room[i] = 0;
@@ -100,6 +134,10 @@ __global__ __launch_bounds__(64 * DT_NW, 4) void k_radius_tile(RadiusTileArgs a)
                 room[i] = base[i] >= a.offsets[qi[i]] ? (int)max((int64_t)0, min(r, (int64_t)0x7fffffff)) : 0;
             }
         }
+    }
+    if constexpr (LINK) {
+        // a block without a core query has nothing to link; a wave without one only stages tiles
+        if (!__syncthreads_or(wave_any ? 1 : 0)) return;
     }
     if (lds_counts)
         for (int c = lane; c < QW * Cpad; c += 64) counts[c] = 0;
@@ -149,7 +187,7 @@ __global__ __launch_bounds__(64 * DT_NW, 4) void k_radius_tile(RadiusTileArgs a)
         const int ch = (int)(s % nchunk);
         const int c0 = ch * a.dc;
         const float* tb = bufs + (s & 1) * tile_floats + lane * a.stride;
-        const int gend = min(gpc, ngr - ch * gpc);
+        const int gend = wave_any ? min(gpc, ngr - ch * gpc) : 0;
         for (int g = 0; g < gend; g++) {
             const float4 t = *reinterpret_cast<const float4*>(tb + 4 * g);
             const int col = c0 + 4 * g;
@@ -177,12 +215,12 @@ __global__ __launch_bounds__(64 * DT_NW, 4) void k_radius_tile(RadiusTileArgs a)
                 }
             }
         }
-        if (ch == nchunk - 1) {
+        if (ch == nchunk - 1 && wave_any) {
             // the tile's distances are final: the threshold test
             const int64_t row = row_begin + (s / nchunk) * 64 + lane;
             const bool valid = row < row_end;
             int lab = -1;
-            if constexpr (!FILL) {
+            if constexpr (COUNT) {
                 if (a.classes && valid) {
                     lab = a.labels[row];
                     if (lab < 0 || lab >= a.C) {
@@ -191,23 +229,36 @@ __global__ __launch_bounds__(64 * DT_NW, 4) void k_radius_tile(RadiusTileArgs a)
                     }
                 }
             }
+            // (LINK) whether this lane's row is a core row; (BORDER) its cluster number, -1 for
+            // a row that is none: one word per tile and lane, where COUNT loads its label
+            [[maybe_unused]] int tword = -1;
+            if constexpr (LINK) tword = valid && a.db.dcount[row] >= a.db.min_samples ? 0 : -1;
+            if constexpr (BORDER) tword = valid ? a.db.cluster[row] : -1;
 #pragma unroll
             for (int i = 0; i < QW; i++) {
                 const bool pass = valid && acc[i] <= thr && row != self[i] && self[i] != -2;
-                const u64 m = __ballot(pass);
-                if constexpr (FILL) {
-                    const int p = run[i] + lanes_below(m);
-                    if (pass && p < room[i]) {
-                        a.idx[base[i] + p] = (int32_t)row;
-                        if (a.dist) a.dist[base[i] + p] = acc[i];
-                    }
+                if constexpr (LINK) {
+                    if (pass && tword >= 0 && row < qi[i] &&
+                        uf_union(a.db.parent, (int32_t)qi[i], (int32_t)row, a.nt, a.status))
+                        nun++;
+                } else if constexpr (BORDER) {
+                    if (pass && tword >= 0) best[i] = min(best[i], (uint32_t)tword);
                 } else {
-                    if (pass && lab >= 0) {
-                        if (lds_counts) atomicAdd(&counts[i * Cpad + lab], 1);
-                        else atomicAdd(&a.class_counts[qi[i] * a.C + lab], 1);
+                    const u64 m = __ballot(pass);
+                    if constexpr (FILL) {
+                        const int p = run[i] + lanes_below(m);
+                        if (pass && p < room[i]) {
+                            a.idx[base[i] + p] = (int32_t)row;
+                            if (a.dist) a.dist[base[i] + p] = acc[i];
+                        }
+                    } else {
+                        if (pass && lab >= 0) {
+                            if (lds_counts) atomicAdd(&counts[i * Cpad + lab], 1);
+                            else atomicAdd(&a.class_counts[qi[i] * a.C + lab], 1);
+                        }
                     }
+                    run[i] += __popcll(m);
                 }
-                run[i] += __popcll(m);
                 acc[i] = 0.0f;  // every metric restarts from +0
             }
         }
@@ -215,7 +266,24 @@ __global__ __launch_bounds__(64 * DT_NW, 4) void k_radius_tile(RadiusTileArgs a)
         __syncthreads();
     }
 
-    if constexpr (FILL) {
+    if constexpr (LINK) {
+        if (a.db.unions) {  // (profile = 2) one 64-bit add per wave
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) nun += __shfl_xor(nun, o);
+            if (lane == 0 && nun) atomicAdd(a.db.unions, nun);
+        }
+    } else if constexpr (BORDER) {
+        // the smallest cluster number among the core neighbours in this train segment; the
+        // segments meet in an integer atomicMin (unsigned: -1, "none yet", is the largest value)
+#pragma unroll
+        for (int i = 0; i < QW; i++) {
+            uint32_t b = best[i];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) b = min(b, (uint32_t)__shfl_xor((int)b, o));
+            if (lane == 0 && qi[i] < nq && b != 0xffffffffu)
+                atomicMin(reinterpret_cast<unsigned int*>(a.db.out_labels) + qr[i], b);
+        }
+    } else if constexpr (FILL) {
 #pragma unroll
         for (int i = 0; i < QW; i++) {
             if (qi[i] >= a.nq) continue;
@@ -468,12 +536,17 @@ __global__ __launch_bounds__(256) void k_radius_regress(RadiusVoteArgs a) {
 // Launchers (host side): k_direct_tile's geometry, one kernel per (metric, element type, pass)
 // ---------------------------------------------------------------------------------
 template <int M, typename E>
-static const void* radius_tile_fn(bool fill) {
-    return fill ? reinterpret_cast<const void*>(&k_radius_tile<M, E, true>)
-                : reinterpret_cast<const void*>(&k_radius_tile<M, E, false>);
+static const void* radius_tile_fn(int mode) {
+    switch (mode) {
+        case RADIUS_COUNT: return reinterpret_cast<const void*>(&k_radius_tile<M, E, RADIUS_COUNT>);
+        case RADIUS_FILL: return reinterpret_cast<const void*>(&k_radius_tile<M, E, RADIUS_FILL>);
+        case RADIUS_LINK: return reinterpret_cast<const void*>(&k_radius_tile<M, E, RADIUS_LINK>);
+        case RADIUS_BORDER: return reinterpret_cast<const void*>(&k_radius_tile<M, E, RADIUS_BORDER>);
+        default: return nullptr;
+    }
 }
-// nullptr: no such metric
-static const void* radius_tile_ptr(int metric, int elem, bool fill) {
+// nullptr: no such metric or mode
+static const void* radius_tile_ptr(int metric, int elem, int fill) {
     const bool bf = elem == ELEM_BF16;
     switch (metric) {
         case METRIC_SQEUCLIDEAN:
@@ -504,12 +577,20 @@ hipError_t knn_radius_units(int metric, int elem, int d, int C, int* queries_per
     return e;
 }
 
-hipError_t knn_launch_radius_tile(RadiusTileArgs a, int metric, bool fill, hipStream_t st) {
+hipError_t knn_launch_radius_tile(RadiusTileArgs a, int metric, int mode, hipStream_t st) {
     if (a.nq <= 0) return hipSuccess;
-    const void* fn = radius_tile_ptr(metric, a.elem, fill);
+    const void* fn = radius_tile_ptr(metric, a.elem, mode);
     if (!fn || a.nseg < 1 || a.d < 1 || !a.status) return hipErrorInvalidValue;
-    if (fill ? (!a.base || !a.offsets || !a.idx) : !a.seg_count) return hipErrorInvalidValue;
-    if (!fill && a.classes) {
+    const bool fill = mode == RADIUS_FILL, count = mode == RADIUS_COUNT;
+    if (fill && (!a.base || !a.offsets || !a.idx)) return hipErrorInvalidValue;
+    if (count && !a.seg_count) return hipErrorInvalidValue;
+    // the DBSCAN modes are self-joins over tables of nt rows
+    if (mode == RADIUS_LINK && (a.nq != a.nt || a.test != a.train || !a.db.dcount || !a.db.parent || a.nt > 0x7fffffffLL))
+        return hipErrorInvalidValue;
+    if (mode == RADIUS_BORDER &&
+        (a.nq != a.nt || a.test != a.train || !a.db.cand || !a.db.nb || !a.db.cluster || !a.db.out_labels))
+        return hipErrorInvalidValue;
+    if (count && a.classes) {
         if (a.C < 1 || !a.labels) return hipErrorInvalidValue;
         a.classes = a.C <= KNN_RADIUS_LDS_MAX_C ? 1 : 2;
         a.fuse_vote = a.classes == 1 && a.nseg == 1;

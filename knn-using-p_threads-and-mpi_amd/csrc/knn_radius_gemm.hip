@@ -2,7 +2,7 @@
 // "Radius neighbours"; DESIGN.md "Radius neighbours", "The MFMA form"): squared Euclidean, d in
 // {64, 128, 256}, fp32 or bf16 rows.
 //
-//   k_radius_gemm<RB, E, FILL>  the fused filter's operands and certificate (knn_fused.hip) against
+//   k_radius_gemm<RB, E, MODE>  the fused filter's operands and certificate (knn_fused.hip) against
 //                               a threshold that is known before the scan
 //
 // Operands (built by the fused filter's own launchers): train as tile blocks of 64 rows,
@@ -28,9 +28,10 @@
 
 #pragma clang fp contract(off)
 #include "knn_radius_dev.h"  // RadiusGemmTile<RB>, radius_exact<E>
+#include "knn_dbscan_dev.h"  // uf_union
 
 // ---------------------------------------------------------------------------------
-// k_radius_gemm<RB, E, FILL> (RadiusGemmArgs; RB = 2 d operand bytes per row, E the caller's
+// k_radius_gemm<RB, E, MODE> (RadiusGemmArgs; RB = 2 d operand bytes per row, E the caller's
 // element).  A block of 8 waves owns 256 queries, 32 per wave, against one train segment (a
 // multiple of 64 rows); lane (j, h) holds its query's B fragments in VGPRs for the whole scan.
 //  * Train tile blocks go global -> registers -> LDS, two buffers, one barrier per tile; the LDS
@@ -42,19 +43,29 @@
 //    never sure and always maybe), masks rows past the segment's end and the self row, resolves
 //    its maybe-but-not-sure rows with radius_exact, and ORs its 64-bit member mask with its
 //    partner's (lane ^ 32): both then hold the query's members of the tile.
-//  * FILL = false: the running count grows by popcount; members add 1 to class_counts[q][label]
+//  * MODE = RADIUS_COUNT: the running count grows by popcount; members add 1 to class_counts[q][label]
 //    (integer atomics; members are rare where this form runs).  Wave 0 of query block 0 range-checks
 //    every label of the segment, one 256-byte load per tile.  At the end seg_count[seg][q].
-//  * FILL = true: member row b stores at base + count + popcount(mask & rows below b), inside the
+//  * MODE = RADIUS_FILL: member row b stores at base + count + popcount(mask & rows below b), inside the
 //    part [base[seg][q], base[seg + 1][q]) and below offsets[q + 1], with D when dist is asked
 //    (radius_exact for a sure row; a band member's D is the one that classified it); a count that does not end at the part's length sets KNN_STATUS_BAD_OFFSETS.
+//  * MODE = RADIUS_LINK / RADIUS_BORDER, DBSCAN's two passes (RadiusDbscanArgs; knn_amd.h "DBSCAN"):
+//    the valid-row mask also drops the tile's non-core rows (one word per lane and tile, a ballot)
+//    and, for LINK, the rows not below the query, BEFORE the band is resolved -- no exact distance
+//    is spent on a pair that cannot matter.  LINK: a lane whose query is no core row takes no part,
+//    the scan ends at the tile of the block's last query, and each member calls uf_union.  BORDER:
+//    lane's query is train row cand[q] (operands, norms and rows are read through it; blocks past *nb
+//    return), each member offers its cluster number, and the minimum of both lane halves goes into
+//    out_labels with an integer atomicMin.
 // The kernel returns at once when the status word says KNN_STATUS_GEMM_UNSAFE (a norm that is NaN,
 // inf or >= 2^125: the certificate does not hold; k_radius_tile, gated the other way, runs instead).
 // LDS: 2 tile images.
 // ---------------------------------------------------------------------------------
-template <int RB, typename E, bool FILL>
+template <int RB, typename E, int MODE>
 __global__ __launch_bounds__(64 * KNN_RADIUS_GEMM_NW) void k_radius_gemm(RadiusGemmArgs a) {
     typedef RadiusGemmTile<RB> RT;
+    constexpr bool COUNT = MODE == RADIUS_COUNT, FILL = MODE == RADIUS_FILL;
+    constexpr bool LINK = MODE == RADIUS_LINK, BORDER = MODE == RADIUS_BORDER;
     constexpr int NW = KNN_RADIUS_GEMM_NW, NT = 64 * NW;
     constexpr int NS = RB / 32;                      // k-steps: d / 16
     constexpr int D = RB / 2;
@@ -69,7 +80,16 @@ __global__ __launch_bounds__(64 * KNN_RADIUS_GEMM_NW) void k_radius_gemm(RadiusG
     const int qb = blockIdx.x % a.n_qblocks;
     const int seg = blockIdx.x / a.n_qblocks;
     const int64_t row_begin = (int64_t)seg * a.seg_len;
-    const int64_t row_end = min(a.nt, row_begin + a.seg_len);
+    int64_t row_end = min(a.nt, row_begin + a.seg_len);
+    // (BORDER: the candidates, counted on the device; the grid is sized for every row)
+    int64_t nq = a.nq;
+    if constexpr (BORDER) {
+        nq = *a.db.nb;
+        if ((int64_t)qb * (32 * NW) >= nq) return;  // (block-uniform, before any barrier)
+    }
+    // (LINK: only rows below the query make a union, so the scan ends at the 64-row tile that
+    // holds the block's last query)
+    if constexpr (LINK) row_end = min(row_end, (min(nq, (int64_t)(qb + 1) * (32 * NW)) + 63) & ~(int64_t)63);
     const int ntiles = row_end > row_begin ? (int)((row_end - row_begin + 63) >> 6) : 0;
     const float thr = a.thr, coef = a.coef, eta = a.eta;
     const float INF = __uint_as_float(0x7f800000u);
@@ -77,20 +97,26 @@ __global__ __launch_bounds__(64 * KNN_RADIUS_GEMM_NW) void k_radius_gemm(RadiusG
 
     // this lane's query (both lane halves hold the same query, different rows)
     const int64_t q = (int64_t)qb * (32 * NW) + wave * 32 + j;
-    const bool qvalid = q < a.nq;
-    const E* qrow = reinterpret_cast<const E*>(a.test) + (qvalid ? q : 0) * (int64_t)a.ld_q;
+    const bool qvalid = q < nq;
+    // the row its operands are read from: q itself, or (BORDER) the candidate's train row
+    int64_t qx = qvalid ? q : 0;
+    if constexpr (BORDER) qx = qvalid ? a.db.cand[q] : 0;
+    // whether the query takes part in the scan: (LINK) only a core row does
+    bool qlive = qvalid;
+    if constexpr (LINK) qlive = qvalid && a.db.dcount[q] >= a.db.min_samples;
+    const E* qrow = reinterpret_cast<const E*>(a.test) + qx * (int64_t)a.ld_q;
     const int64_t self = (qvalid && a.self_base >= 0) ? a.self_base + q : -1;
     uint4 qf[NS];
     {
-        const unsigned char* qop = reinterpret_cast<const unsigned char*>(a.qop) + (qvalid ? q : 0) * (int64_t)RB;
+        const unsigned char* qop = reinterpret_cast<const unsigned char*>(a.qop) + qx * (int64_t)RB;
 #pragma unroll
         for (int s = 0; s < NS; s++)
             qf[s] = qvalid ? *reinterpret_cast<const uint4*>(qop + 32 * s + 16 * h) : make_uint4(0u, 0u, 0u, 0u);
     }
-    const float qn = qvalid ? a.qnorm[q] : 0.0f;
+    const float qn = qvalid ? a.qnorm[qx] : 0.0f;
     float qe2 = 0.0f, eq2 = 0.0f;  // 2 |q| and 2 |q - rq|, rounded up
     if (qvalid) {
-        const float2 qs = a.qstat[q];
+        const float2 qs = a.qstat[qx];
         qe2 = 2.0f * qs.x * (1.0f + 0x1p-17f);
         eq2 = 2.0f * qs.y * (1.0f + 0x1p-17f);
     }
@@ -100,12 +126,14 @@ __global__ __launch_bounds__(64 * KNN_RADIUS_GEMM_NW) void k_radius_gemm(RadiusG
     // implies y <= tf.  A passing y is never NaN here: the pass runs only with every norm finite
     // and below 2^125, where every partial sum of the MFMA chain is finite.
     float tf = -INF;
-    if (qvalid) {
+    if (qlive) {
         const float4 smax = *a.tsmax;
         const float tk = fmaf(coef + 0x1p-18f, smax.x, fmaf(qe2, smax.y, eq2 * smax.z));
         tf = ((thr - qn) + fmaf(coef, qn, eta)) + 0x1p-18f * (fabsf(thr) + qn + eta) + tk;
     }
-    const bool wave_live = __ballot(qvalid) != 0ull;
+    const bool wave_live = __ballot(qlive) != 0ull;
+    [[maybe_unused]] uint32_t best = 0xffffffffu;  // (BORDER) the smallest cluster number so far
+    [[maybe_unused]] unsigned long long nun = 0;   // (LINK) successful hooks
 
     int run = 0;        // the query's members so far (the same in both lane halves)
     int64_t base = 0;   // (FILL) where this segment's part of the query's list starts
@@ -156,7 +184,7 @@ __global__ __launch_bounds__(64 * KNN_RADIUS_GEMM_NW) void k_radius_gemm(RadiusG
         if (t + 1 < ntiles) load_tile(t + 1);
         const unsigned char* tile = smem + (t & 1) * TILE;
         const int64_t r0 = row_begin + (int64_t)t * 64;
-        if constexpr (!FILL) {
+        if constexpr (COUNT) {
             // every label of the segment is range-checked, neighbour or not
             if (a.classes && qb == 0 && wave == 0 && r0 + lane < row_end) {
                 const int lab = a.labels[r0 + lane];
@@ -210,7 +238,20 @@ __global__ __launch_bounds__(64 * KNN_RADIUS_GEMM_NW) void k_radius_gemm(RadiusG
                 const int64_t nv = row_end - r0;
                 u64 vm = nv >= 64 ? ~0ull : ((1ull << nv) - 1ull);
                 if (self >= r0 && self < r0 + 64) vm &= ~(1ull << (int)(self - r0));
-                if (!qvalid) vm = 0ull;
+                if (!qlive) vm = 0ull;
+                if constexpr (LINK || BORDER) {
+                    // the tile's core rows, one word per lane (LINK: the neighbour count against
+                    // min_samples; BORDER: a cluster number); LINK keeps the rows below the query
+                    const int64_t tr = r0 + lane;
+                    bool tc = false;
+                    if constexpr (LINK) tc = tr < row_end && a.db.dcount[tr] >= a.db.min_samples;
+                    else tc = tr < row_end && a.db.cluster[tr] >= 0;
+                    vm &= __ballot(tc);
+                    if constexpr (LINK) {
+                        const int64_t below = q - r0;  // rows of the tile with an index under q's
+                        if (below < 64) vm &= below > 0 ? (1ull << below) - 1ull : 0ull;
+                    }
+                }
                 mb = (mb << (4 * h)) & vm;
                 sb = (sb << (4 * h)) & vm;
                 u64 band = mb & ~sb;
@@ -234,7 +275,21 @@ __global__ __launch_bounds__(64 * KNN_RADIUS_GEMM_NW) void k_radius_gemm(RadiusG
                     }
                 }
                 u64 mem = sb | bmem;
-                const u64 m64 = mem | lane_xor64(mem, 32);
+                if constexpr (LINK) {
+                    while (mem) {
+                        const int b = __ffsll((long long)mem) - 1;
+                        mem &= mem - 1ull;
+                        if (uf_union(a.db.parent, (int32_t)q, (int32_t)(r0 + b), a.nt, a.status)) nun++;
+                    }
+                } else if constexpr (BORDER) {
+                    while (mem) {
+                        const int b = __ffsll((long long)mem) - 1;
+                        mem &= mem - 1ull;
+                        best = min(best, (uint32_t)a.db.cluster[r0 + b]);
+                    }
+                }
+                [[maybe_unused]] u64 m64 = 0ull;
+                if constexpr (COUNT || FILL) m64 = mem | lane_xor64(mem, 32);
                 if constexpr (FILL) {
                     while (mem) {
                         const int b = __ffsll((long long)mem) - 1;
@@ -257,7 +312,7 @@ __global__ __launch_bounds__(64 * KNN_RADIUS_GEMM_NW) void k_radius_gemm(RadiusG
                             }
                         }
                     }
-                } else if (a.classes) {
+                } else if (COUNT && a.classes) {
                     while (mem) {
                         const int b = __ffsll((long long)mem) - 1;
                         mem &= mem - 1ull;
@@ -272,7 +327,19 @@ __global__ __launch_bounds__(64 * KNN_RADIUS_GEMM_NW) void k_radius_gemm(RadiusG
         __syncthreads();
     }
 
-    if (qvalid && h == 0) {
+    if constexpr (LINK) {
+        if (a.db.unions) {  // (profile = 2) one 64-bit add per wave
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) nun += __shfl_xor(nun, o);
+            if (lane == 0 && nun) atomicAdd(a.db.unions, nun);
+        }
+    } else if constexpr (BORDER) {
+        // both lane halves' minima, then the train segments' through an integer atomicMin
+        // (unsigned: -1, "none yet", is the largest value)
+        best = min(best, lane_xor(best, 32));
+        if (qvalid && h == 0 && best != 0xffffffffu)
+            atomicMin(reinterpret_cast<unsigned int*>(a.db.out_labels) + qx, best);
+    } else if (qvalid && h == 0) {
         if constexpr (FILL) {
             const int64_t end = a.offsets[q + 1];
             const int64_t next = seg + 1 < a.nseg ? a.base[(int64_t)(seg + 1) * a.nq + q] : end;
@@ -293,16 +360,22 @@ __global__ __launch_bounds__(64 * KNN_RADIUS_GEMM_NW) void k_radius_gemm(RadiusG
 // ---------------------------------------------------------------------------------
 // Launchers (host side)
 // ---------------------------------------------------------------------------------
-template <int RB>
-static const void* radius_gemm_fn(int elem, bool fill) {
-    if (elem == ELEM_BF16)
-        return fill ? reinterpret_cast<const void*>(&k_radius_gemm<RB, bf16_t, true>)
-                    : reinterpret_cast<const void*>(&k_radius_gemm<RB, bf16_t, false>);
-    return fill ? reinterpret_cast<const void*>(&k_radius_gemm<RB, float, true>)
-                : reinterpret_cast<const void*>(&k_radius_gemm<RB, float, false>);
+template <int RB, typename E>
+static const void* radius_gemm_mode(int mode) {
+    switch (mode) {
+        case RADIUS_COUNT: return reinterpret_cast<const void*>(&k_radius_gemm<RB, E, RADIUS_COUNT>);
+        case RADIUS_FILL: return reinterpret_cast<const void*>(&k_radius_gemm<RB, E, RADIUS_FILL>);
+        case RADIUS_LINK: return reinterpret_cast<const void*>(&k_radius_gemm<RB, E, RADIUS_LINK>);
+        case RADIUS_BORDER: return reinterpret_cast<const void*>(&k_radius_gemm<RB, E, RADIUS_BORDER>);
+        default: return nullptr;
+    }
 }
-// nullptr: no such shape
-static const void* radius_gemm_ptr(int d, int elem, bool fill) {
+template <int RB>
+static const void* radius_gemm_fn(int elem, int mode) {
+    return elem == ELEM_BF16 ? radius_gemm_mode<RB, bf16_t>(mode) : radius_gemm_mode<RB, float>(mode);
+}
+// nullptr: no such shape or mode
+static const void* radius_gemm_ptr(int d, int elem, int fill) {
     switch (d) {
         case 64: return radius_gemm_fn<128>(elem, fill);
         case 128: return radius_gemm_fn<256>(elem, fill);
@@ -328,14 +401,22 @@ hipError_t knn_radius_gemm_units(int elem, int d, int* queries_per_unit, int* un
     return e;
 }
 
-hipError_t knn_launch_radius_gemm(RadiusGemmArgs a, bool fill, hipStream_t st) {
+hipError_t knn_launch_radius_gemm(RadiusGemmArgs a, int mode, hipStream_t st) {
     if (a.nq <= 0) return hipSuccess;
-    const void* fn = radius_gemm_ptr(a.d, a.elem, fill);
+    const void* fn = radius_gemm_ptr(a.d, a.elem, mode);
     if (!fn || a.nseg < 1 || a.seg_len < 64 || a.seg_len % 64 || !a.status || !a.tblk || !a.qop || !a.qnorm ||
         !a.qstat || !a.tsmax || !a.train || !a.test)
         return hipErrorInvalidValue;
-    if (fill ? (!a.base || !a.offsets || !a.idx) : !a.seg_count) return hipErrorInvalidValue;
-    if (!fill && a.classes && (a.C < 1 || !a.labels || !a.class_counts)) return hipErrorInvalidValue;
+    const bool fill = mode == RADIUS_FILL, count = mode == RADIUS_COUNT;
+    if (fill && (!a.base || !a.offsets || !a.idx)) return hipErrorInvalidValue;
+    if (count && !a.seg_count) return hipErrorInvalidValue;
+    if (count && a.classes && (a.C < 1 || !a.labels || !a.class_counts)) return hipErrorInvalidValue;
+    // the DBSCAN modes are self-joins over tables of nt rows
+    if (mode == RADIUS_LINK && (a.nq != a.nt || a.test != a.train || !a.db.dcount || !a.db.parent || a.nt > 0x7fffffffLL))
+        return hipErrorInvalidValue;
+    if (mode == RADIUS_BORDER &&
+        (a.nq != a.nt || a.test != a.train || !a.db.cand || !a.db.nb || !a.db.cluster || !a.db.out_labels))
+        return hipErrorInvalidValue;
     const int qb = 32 * KNN_RADIUS_GEMM_NW;
     a.n_qblocks = (int)((a.nq + qb - 1) / qb);
     const dim3 grid((unsigned)((int64_t)a.n_qblocks * a.nseg));
