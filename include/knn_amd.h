@@ -745,14 +745,79 @@ knn_status knn_radius_vote_sweep_device(knn_ctx* ctx, int64_t nq, int64_t n_trai
  * call; [18] is the number of rows sent through the border pass, [19], under profile = 2, the
  * successful hooks of the union-find.  A union-find loop that reaches its iteration cap (3 n + 8
  * steps, a bound no correct run can reach) gives KNN_EHIP, "internal error", never a hang.
- * Not here: an eps sweep (the radius sweep's counts give the core sets of 32 radii; the links are
- * what is missing), sample_weight, HDBSCAN / OPTICS, a host-buffer entry point, a multi-rank driver
- * (lists concatenate by shard: knn_dbscan_lists_device).
+ * Not here: sample_weight, HDBSCAN / OPTICS, a host-buffer entry point, a multi-rank driver (lists
+ * concatenate by shard: knn_dbscan_lists_device).  The eps sweep is "DBSCAN sweep" below.
  */
 knn_status knn_dbscan_device(knn_ctx* ctx, const knn_dataset* train, float thr, int32_t min_samples,
                              int32_t* d_labels, int32_t* d_count, int64_t* d_summary, void* hip_stream);
 knn_status knn_dbscan_lists_device(knn_ctx* ctx, int64_t n, const int64_t* d_offsets, const int32_t* d_idx,
                                    int32_t min_samples, int32_t* d_labels, int32_t* d_count, int64_t* d_summary,
+                                   void* hip_stream);
+
+/*
+ * DBSCAN sweep: DBSCAN's labels at every one of R <= 32 thresholds -- the eps ladder a user walks to
+ * find the radius -- from three distance passes over the train set against itself, whatever R is,
+ * and no neighbour list.
+ *   thresholds  thr[0 .. R - 1], a HOST array, 1 <= R <= 32, each in [0, FLT_MAX), non-decreasing
+ *               (equal neighbours are allowed and give equal rows): "Radius sweep"'s checks.
+ *               min_samples >= 1.
+ *   definitions D, neighbourhood, core, clusters, border, noise and the numbering are "DBSCAN"'s,
+ *               applied per r.  Row r of every output equals, bit for bit, what knn_dbscan_device
+ *               returns at thr[r] on the same context.
+ *   outputs     d_labels int32 [R][ld_out] (ld_out >= n; the columns past n are not touched);
+ *               d_count int32 [R][ld_out], optional -- the very bits knn_radius_sweep_count_device
+ *               gives for (T, T, self_base = -1), which are by that entry's contract
+ *               knn_radius_count_device's at thr[r]; d_summary int64 [R][4], optional, per r
+ *               {clusters, core rows, border rows, noise rows}.
+ *   level       c(i) = the smallest r with count[r][i] >= min_samples, R if there is none.  The
+ *               counts are nested, so row i is a core row at r iff c(i) <= r.
+ *   determinism every step is integer: the same bits on every run, through both forms of the pass
+ *               and with any number of train segments.
+ * The passes:
+ *   1. count    the sweep's count pass as a self-join (classes = 0), in the form knn_radius_policy
+ *               states for (n, n).  The histograms are bounded by the workspace budget: the entry
+ *               walks the rows in query blocks of knn_radius_sweep_max_queries(ctx, R, 0) itself (no
+ *               KNN_ERANGE).  A small kernel derives level[i] = c(i) and compacts the border
+ *               candidates: c(i) >= 1 and count[c(i) - 1][i] >= 2.
+ *   2. link     R union-find forests parent[R][n], each starting as the identity.  A pair of rows
+ *               t < q with c(q) < R, c(t) < R and D <= thr[R - 1] first becomes a core-core edge at
+ *               level a = max(bucket(q, t), c(q), c(t)), bucket = the smallest r with D <= thr[r].
+ *               If a < R the pair makes ONE union, into forest a.  Only rows below a block's last
+ *               query are scanned; the MFMA form applies the level table's ballot and the t < q
+ *               mask before the band is resolved, and gives a pair its exact distance only when a
+ *               threshold of index >= max(c(q), c(t)) lies inside its bracket.
+ *   3. chain    one small kernel per level, ascending.  For a row with c(i) <= r: root_r[i] =
+ *               find(forest r, i), and if r + 1 < R the row is joined to that root in forest r + 1.
+ *               The graph at level r is the core rows of level r with the edges of level <= r; its
+ *               components are the closure of the edges of level exactly r (put into forest r by
+ *               the pass) together with the components of level r - 1 (carried in by this step).
+ *               Forest r - 1 is final when kernel r - 1 starts, and the union-find's invariant (the
+ *               larger root is hooked under the smaller) makes each root the component's smallest
+ *               row whatever the order.  Cluster numbers per level: the exclusive scan of isroot.
+ *   4. border   one pass over the candidates, read through cand[] (not gathered).  A pair (q, t)
+ *               with c(t) < R offers root_r[t] to best[r][q] for r in [max(bucket, c(t)), c(q)), an
+ *               unsigned integer atomicMin.  Clusters are numbered in ascending order of root, so
+ *               the smallest root is the smallest cluster number.  The self pair's range is empty.
+ *   5. labels   per (r, i): a core row its root's number, a row with an offer that root's number,
+ *               every other row -1; summary[r] by integer adds.  One synchronisation.
+ *   Unsafe norms: "Radius neighbours"' protocol in all three passes (the MFMA kernel returns, the
+ *   direct kernel runs behind the gate, knn_last_stats()[13] == 2).
+ * KNN_EINVAL before anything is launched, the outputs untouched, for everything
+ * knn_radius_sweep_count_device and knn_dbscan_device refuse, and for ld_out < n.  n == 0 returns
+ * KNN_OK and zero summaries.  A failed workspace allocation (about R * n * 4 bytes each for parent,
+ * root, best, the roots' flags and own counts, R * n * 8 for the scans) returns KNN_ENOMEM.
+ * Stages under profile = 1: "radius_sweep" and "radius_sweep_finish" (once per query block; and the
+ * MFMA form's "radius_norms", "radius_operands"), "dbscan_sweep_link", "dbscan_sweep_border",
+ * "dbscan_labels" (levels and candidates, init, the chain and its scans, labels, summary).
+ * knn_last_stats(): [13] and [14] read as after a radius call ([14]: all three passes together);
+ * [18] the rows sent through the border pass; [19], under profile = 2, the successful hooks of the
+ * link pass and the level chain together.  The union-find's step cap gives KNN_EHIP, never a hang.
+ * Not here: sample_weight, a lists-held sweep, a min_samples sweep, HDBSCAN / OPTICS, host-buffer
+ * entry points, the MFMA form at widths other than 64 / 128 / 256.
+ */
+knn_status knn_dbscan_sweep_device(knn_ctx* ctx, const knn_dataset* train, const float* thresholds, int32_t R,
+                                   int32_t min_samples, int64_t ld_out, int32_t* d_labels /* [R][ld_out] */,
+                                   int32_t* d_count /* optional */, int64_t* d_summary /* [R][4], optional */,
                                    void* hip_stream);
 
 /* Per-stage device times (ms) of the last predict call when opts.profile >= 1.

@@ -220,6 +220,12 @@ float* KNN_lof(ArffData* train, int k_lo, int k_hi);
 // their smallest row, -1 noise; caller frees.  summary (optional) receives {clusters, core rows,
 // border rows, noise rows}.  Runs on the first device.
 int* KNN_dbscan(ArffData* train, float radius, int min_samples, long* summary = nullptr);
+// DBSCAN at every one of 1 <= n_radii <= 32 non-decreasing radii from three distance passes (knn_amd.h
+// "DBSCAN sweep").  Returns malloc'd int[n_radii * n] laid out [n_radii][n], row r what KNN_dbscan
+// returns at radii[r]; caller frees.  summary (optional) receives [n_radii][4] {clusters, core rows,
+// border rows, noise rows}.  Runs on the first device.
+int* KNN_dbscan_sweep(ArffData* train, const float* radii, int n_radii, int min_samples,
+                      long* summary /* [n_radii][4] */ = nullptr);
 // main.cpp:87 -- calloc'd int[C*C], C = dataset->num_classes(), row = true class.
 int* computeConfusionMatrix(int* predictions, ArffData* dataset);
 // main.cpp:102

@@ -31,6 +31,9 @@ Names follow the reference (srna99/KNN-using-p_threads-and-MPI):
   and ``lof_outliers``: the local outlier factor of every train row for every k in [k_lo, k_hi]
   from one leave-one-out top-k pass, and novelty scores of queries against the fitted tables (no
   reference counterpart; the rules are in ``knn_amd.h`` "Local outlier factor")
+* ``Context.dbscan_sweep_device`` and ``best_eps``: DBSCAN's labels, counts and summaries at every
+  one of up to 32 radii from three distance passes -- row r is ``Context.dbscan_device`` at
+  ``radii[r]`` (no reference counterpart; the rules are in ``knn_amd.h`` "DBSCAN sweep")
 
 Features are fp32 or bf16.  Host bf16 arrays are numpy ``uint16`` holding bf16 bits
 (``to_bf16_bits`` / ``bf16_bits_to_f32``); device tensors are ``torch.bfloat16``.
@@ -154,6 +157,7 @@ def load_library(path=LIB_PATH):
         "knn_radius_vote_sweep_device": (I32, [P, I64, I64, P, P, P, P, I32, I32, P, I32, I32, P, I64, P, P, P, P]),
         "knn_dbscan_device": (I32, [P, DS, F, I32, P, P, P, P]),
         "knn_dbscan_lists_device": (I32, [P, I64, P, P, I32, P, P, P, P]),
+        "knn_dbscan_sweep_device": (I32, [P, DS, P, I32, I32, I64, P, P, P, P]),
         "knn_arff_copy_targets": (I32, [P, P, I32, P]),
         "knn_stage_times": (I32, [P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(F), I32]),
         "knn_last_stats": (I32, [P, ctypes.POINTER(I64), I32]),
@@ -1081,6 +1085,41 @@ class Context:
             summary.data_ptr(), self._stream(stream, idx)))
         return labels, count, summary
 
+    def dbscan_sweep_device(self, train, radii=None, thresholds=None, min_samples=5, labels=None, count=False,
+                            stream=None, d=None):
+        """dbscan_device at every one of R <= 32 non-decreasing radii from three distance passes,
+        whatever R is (knn_dbscan_sweep_device).  Exactly one of radii= and thresholds= (as the
+        radius sweep).  Returns (labels int32 [R][n], count int32 [R][n] or None with count=False,
+        summary int64 [R][4]); row r holds the very bits dbscan_device returns at radii[r] on this
+        context.  labels may be an int32 tensor [R][ld] with ld >= n to fill: the columns past n
+        are not touched, and count=True then has the same pitch."""
+        import torch
+        thr = self._thresholds(radii, thresholds)
+        R = int(thr.size)
+        if int(min_samples) != min_samples:
+            raise KnnError(KNN_EINVAL, f"min_samples must be an integer, got {min_samples!r}")
+        self._on_device(train)
+        self._note_train(train)
+        tr = _device_dataset(train, None, d)
+        n, dev, rows = tr.n, train.device, max(R, 1)
+        ld = n
+        if labels is None:
+            labels = torch.empty((rows, max(n, 1)), dtype=torch.int32, device=dev)[:, :n]
+            ld = max(n, 1)
+        else:
+            if labels.dtype != torch.int32 or labels.dim() != 2 or labels.shape[0] < rows or labels.stride(1) != 1:
+                raise KnnError(KNN_EINVAL, "labels must be an int32 tensor [R][ld] with unit column stride")
+            self._on_device(labels)
+            ld = labels.stride(0) if labels.shape[0] > 1 else max(labels.shape[1], 1)
+            if labels.shape[1] < n:
+                ld = labels.shape[1]  # (the library refuses ld_out < n)
+        cnt = torch.empty((rows, max(ld, 1)), dtype=torch.int32, device=dev) if count else None
+        summary = torch.zeros((rows, 4), dtype=torch.int64, device=dev)
+        self._check(self.lib.knn_dbscan_sweep_device(
+            self.h, ctypes.byref(tr), thr.ctypes.data_as(ctypes.c_void_p), R, int(min_samples), ld, labels.data_ptr(),
+            _opt_ptr(cnt), summary.data_ptr(), self._stream(stream, train)))
+        return labels, (None if cnt is None else cnt[:, :n]), summary
+
     # radius sweep (knn_amd.h "Radius sweep")
     def _thresholds(self, radii, thresholds):
         """The binary32 thresholds of a sweep: exactly one of radii= (each float32(r) * float32(r)
@@ -1688,6 +1727,20 @@ def dbscan_sizes(labels):
         return torch.bincount(lab[lab >= 0])
     lab = np.asarray(labels).reshape(-1).astype(np.int64)
     return np.bincount(lab[lab >= 0]).astype(np.int64)
+
+
+def best_eps(summary):
+    """The index of the row of a DBSCAN sweep's summary [R][4] (clusters, core, border, noise; a
+    tensor or an array) to look at first: among the rows with the MOST CLUSTERS the one with the
+    FEWEST NOISE ROWS, and the smallest index when several rows tie on both.  A host helper: a
+    tensor is copied to the host."""
+    s = summary.cpu().numpy() if hasattr(summary, "cpu") else np.asarray(summary)
+    s = s.reshape(-1, 4).astype(np.int64)
+    if s.shape[0] == 0:
+        raise KnnError(KNN_EINVAL, "best_eps: the summary has no rows")
+    top = s[:, 0] == s[:, 0].max()
+    noise = np.where(top, s[:, 3], np.iinfo(np.int64).max)
+    return int(np.argmin(noise))  # (argmin: the first of equal values)
 
 
 def _host_targets(t, name, n):

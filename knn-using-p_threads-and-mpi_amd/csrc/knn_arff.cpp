@@ -1168,6 +1168,57 @@ int* KNN_dbscan(ArffData* train, float radius, int min_samples, long* summary) {
     return labels;
 }
 
+// DBSCAN at every one of n_radii radii on the first device (knn_amd.h "DBSCAN sweep"), staged as
+// KNN_dbscan: the cached train upload, knn_dbscan_sweep_device, the [n_radii][n] labels back
+int* KNN_dbscan_sweep(ArffData* train, const float* radii, int n_radii, int min_samples, long* summary) {
+    const KnnFlatView& tr = train->flat();
+    if (n_radii < 1 || n_radii > 32 || !radii) throwf("KNN_dbscan_sweep: n_radii=%d outside [1, 32]", n_radii);
+    for (int r = 0; r < n_radii; r++) {
+        if (!(radii[r] >= 0.0f)) throwf("KNN_dbscan_sweep: radius %d = %g must be >= 0", r, (double)radii[r]);
+        if (r && radii[r] < radii[r - 1]) throwf("KNN_dbscan_sweep: radii %d and %d descend", r - 1, r);
+    }
+    if (min_samples < 1) throwf("KNN_dbscan_sweep: min_samples=%d must be >= 1", min_samples);
+    const size_t n = (size_t)tr.n, R = (size_t)n_radii;
+    int* labels = (int*)std::malloc(sizeof(int) * (n > 0 ? R * n : 1));
+    if (!labels) throwf("KNN_dbscan_sweep: out of memory");
+    std::vector<int64_t> sum(4 * R, 0);
+    std::string why;
+    knn_status s = KNN_OK;
+    try {
+        std::vector<knn_ctx*>& cs = contexts();
+        knn_ctx* c = cs[0];
+        std::lock_guard<std::mutex> busy(*devices().busy[0]);
+        // the reported distance is squared under the Euclidean metric (one binary32 product)
+        std::vector<float> thr(radii, radii + R);
+        if (knn_get_metric(c) == KNN_METRIC_SQEUCLIDEAN)
+            for (float& t : thr) t = t * t;
+        const int dev = knn_ctx_device(c);
+        hipStream_t st = (hipStream_t)knn_ctx_stream(c);
+        knn_dataset htr{tr.feat.data(), tr.labels.data(), tr.n, tr.d, tr.ld, KNN_F32}, dtr{};
+        s = knn_set_generation(c, tr.uid);
+        if (s == KNN_OK) s = knn_ctx_train_device(c, &htr, &dtr);
+        DevMem dlab(dev, sizeof(int32_t) * R * n), dsum(dev, sizeof(int64_t) * 4 * R);
+        if (s == KNN_OK && (!dlab.p || !dsum.p)) throwf("KNN_dbscan_sweep: device allocation failed");
+        if (s == KNN_OK)
+            s = knn_dbscan_sweep_device(c, &dtr, thr.data(), n_radii, min_samples, tr.n, (int32_t*)dlab.p, nullptr,
+                                        (int64_t*)dsum.p, st);
+        if (s == KNN_OK &&
+            ((n > 0 && hipMemcpy(labels, dlab.p, sizeof(int32_t) * R * n, hipMemcpyDeviceToHost) != hipSuccess) ||
+             hipMemcpy(sum.data(), dsum.p, sizeof(int64_t) * 4 * R, hipMemcpyDeviceToHost) != hipSuccess))
+            throwf("KNN_dbscan_sweep: download failed");
+        if (s != KNN_OK) why = knn_last_error(c);
+    } catch (...) {
+        std::free(labels);
+        throw;
+    }
+    if (s != KNN_OK) {
+        std::free(labels);
+        throwf("KNN_dbscan_sweep: %s (status %d)", why.c_str(), (int)s);
+    }
+    for (size_t i = 0; summary && i < 4 * R; i++) summary[i] = (long)sum[i];
+    return labels;
+}
+
 void* KNN(void* params) {
     arguments* a = static_cast<arguments*>(params);
     predict_range(a->train, a->test, a->k, a->start, a->end, predictions + a->start);

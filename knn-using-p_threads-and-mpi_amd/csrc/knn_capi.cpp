@@ -147,6 +147,10 @@ struct knn_ctx {
     // roots [n + 1], the summary words {clusters, core, border, noise, unions} and the neighbour
     // counts a caller did not ask for
     DBuf db_tab, db_offs, db_info, db_count;
+    // the DBSCAN sweep: the int32 tables level | cand [2][n] and parent | root | isroot | best [4][R][n],
+    // the int64 scans of the roots [R][n + 1], the summary words [R][4] + unions, and the counts
+    // [R][n] a caller did not ask for
+    DBuf dbs_tab, dbs_offs, dbs_info, dbs_count;
     // the pass rd_segcnt's counts came from: a fill whose pass has the same key takes them as they
     // are instead of counting again.  (Rows rewritten in place in between are caught where stale
     // counts would matter: the fill checks every (segment, query) count against its own.)
@@ -244,7 +248,7 @@ knn_status fail(knn_ctx* c, knn_status s, const char* fmt, ...) {
 static bool hot_stage(const char* n) {
     static const char* const hot[] = {"gemm_filter", "rescore", "direct_tile", "metric_tile", "exact_scan", "merge_vote",
                                       "exchange", "radius_count", "radius_fill", "radius_sweep", "dbscan_link",
-                                      "dbscan_border"};
+                                      "dbscan_border", "dbscan_sweep_link", "dbscan_sweep_border"};
     for (const char* h : hot)
         if (!strcmp(n, h)) return true;
     return false;
@@ -1222,7 +1226,8 @@ void knn_destroy(knn_ctx* c) {
                     &c->rg_part, &c->rg_zero, &c->rg_targets, &c->rd_segcnt, &c->rd_base, &c->rd_cc, &c->rd_scores,
                     &c->rm_tnorm, &c->rm_tmax, &c->rm_tsmax, &c->rm_tblk, &c->rm_tctrl, &c->rm_qnorm, &c->rm_qstat,
                     &c->rm_qop, &c->rm_exact, &c->lof_idx, &c->lof_dist, &c->lof_cidx, &c->lof_delta, &c->lof_kd,
-                    &c->lof_lrd, &c->lof_qlrd, &c->rd_sweep, &c->db_tab, &c->db_offs, &c->db_info, &c->db_count})
+                    &c->lof_lrd, &c->lof_qlrd, &c->rd_sweep, &c->db_tab, &c->db_offs, &c->db_info, &c->db_count,
+                    &c->dbs_tab, &c->dbs_offs, &c->dbs_info, &c->dbs_count})
         b->release();
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; i++) {
@@ -2987,6 +2992,147 @@ knn_status knn_radius_vote_sweep_device(knn_ctx* c, int64_t nq, int64_t n_train,
     HIP_OR_FAIL(c, knn_launch_radius_vote_sweep(v, st));
     stage_end(c, st);
     return finish_call(c, st);
+}
+
+// The DBSCAN eps sweep (knn_amd.h "DBSCAN sweep"): the sweep's count pass as a self-join, walked in
+// query blocks the histograms' budget takes -> k_dbscan_sweep_prepare (levels, candidates) ->
+// k_dbscan_sweep_init -> the link pass (one union per pair, into the forest of the pair's level) ->
+// per level k_dbscan_sweep_level and k_radius_scan -> the border pass -> k_dbscan_sweep_labels.
+knn_status knn_dbscan_sweep_device(knn_ctx* c, const knn_dataset* tr, const float* thresholds, int32_t R,
+                                   int32_t min_samples, int64_t ld_out, int32_t* d_labels, int32_t* d_count,
+                                   int64_t* d_summary, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    reset_stats(c);
+    knn_status s;
+    if (min_samples < 1) return fail(c, KNN_EINVAL, "dbscan sweep: min_samples=%d must be >= 1", min_samples);
+    if ((s = sweep_thresholds_check(c, "dbscan sweep", thresholds, R)) != KNN_OK) return s;
+    if ((s = radius_check(c, tr, tr, thresholds[R - 1], -1, false)) != KNN_OK) return s;
+    const int64_t n = tr->n;
+    if (ld_out < n) return fail(c, KNN_EINVAL, "dbscan sweep: ld_out=%lld < n=%lld", (long long)ld_out, (long long)n);
+    if (n > 0 && !d_labels) return fail(c, KNN_EINVAL, "dbscan sweep: d_labels is NULL");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (n == 0) {
+        if (d_summary) HIP_OR_FAIL(c, hipMemsetAsync(d_summary, 0, sizeof(int64_t) * 4 * (size_t)R, st));
+        HIP_OR_FAIL(c, hipStreamSynchronize(st));
+        return KNN_OK;
+    }
+    // every buffer before the first launch: a failed allocation leaves the outputs untouched
+    const size_t N = (size_t)n, RN = (size_t)R * N;
+    const int64_t qblock = std::max<int64_t>(1, std::min<int64_t>(n, knn_radius_sweep_max_queries(c, R, 0)));
+    HIP_OR_FAIL(c, c->dbs_tab.ensure(sizeof(int32_t) * (2 * N + 4 * RN)));
+    HIP_OR_FAIL(c, c->dbs_offs.ensure(sizeof(int64_t) * (size_t)R * (N + 1)));
+    HIP_OR_FAIL(c, c->dbs_info.ensure(sizeof(int64_t) * (4 * (size_t)R + 1)));
+    if (!d_count) HIP_OR_FAIL(c, c->dbs_count.ensure(sizeof(int32_t) * RN));
+    HIP_OR_FAIL(c, c->rd_sweep.ensure(sizeof(int32_t) * (size_t)(R + 1) * (size_t)qblock));
+    int32_t* t = c->dbs_tab.as<int32_t>();
+    int32_t *level = t, *cand = t + N, *parent = t + 2 * N, *root = parent + RN, *isroot = root + RN;
+    uint32_t* best = reinterpret_cast<uint32_t*>(isroot + RN);
+    int64_t* offs = c->dbs_offs.as<int64_t>();
+    int64_t* info = c->dbs_info.as<int64_t>();
+    int32_t* count = d_count ? d_count : c->dbs_count.as<int32_t>();
+    const int64_t ldc = d_count ? ld_out : n;
+    int32_t* status = c->ctrl.as<int32_t>();
+    int32_t* nb = status + 3;  // (a spare status word: dbscan_bufs)
+    unsigned long long* unions = c->profile == 2 ? reinterpret_cast<unsigned long long*>(info + 4 * R) : nullptr;
+
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    HIP_OR_FAIL(c, hipMemsetAsync(info, 0, sizeof(int64_t) * (4 * (size_t)R + 1), st));
+    c->rd_key.valid = false;
+    // the three passes share the form and the segments of a single-threshold pass on (n, n)
+    const int form = radius_policy(c->metric, tr->d, n, n, c->algo);
+    const RadiusTileArgs ta = radius_args(c, tr, tr, thresholds[R - 1], -1, 0, form);
+    DbscanSweepTileArgs a{};
+    a.s.train = tr->feat; a.s.nt = n; a.s.ld_t = tr->ld;
+    a.s.test = tr->feat; a.s.ld_q = tr->ld; a.s.nq = n;
+    a.s.d = tr->d; a.s.elem = tr->dtype;
+    a.s.self_base = -1; a.s.R = R;
+    std::copy(thresholds, thresholds + R, a.s.thr);
+    a.s.nseg = ta.nseg; a.s.seg_len = ta.seg_len;
+    a.s.hist = c->rd_sweep.as<int32_t>();
+    a.s.status = status;
+    DbscanSweepGemmArgs g{};
+    if (form) {
+        RadiusGemmArgs r{};
+        if ((s = radius_prep(c, tr, tr, ta, st, &r)) != KNN_OK) return s;
+        g.s.tblk = r.tblk; g.s.qop = r.qop; g.s.qnorm = r.qnorm; g.s.qstat = r.qstat; g.s.tsmax = r.tsmax;
+        g.s.train = r.train; g.s.nt = r.nt; g.s.ld_t = r.ld_t;
+        g.s.test = r.test; g.s.ld_q = r.ld_q; g.s.nq = r.nq;
+        g.s.d = r.d; g.s.elem = r.elem;
+        g.s.seg_len = r.seg_len; g.s.nseg = r.nseg;
+        g.s.self_base = -1; g.s.coef = r.coef; g.s.eta = r.eta;
+        g.s.R = R;
+        g.s.hist = a.s.hist; g.s.status = r.status; g.s.exact_cnt = r.exact_cnt;
+        std::copy(thresholds, thresholds + R, g.s.thr);
+        a.s.gate = a.s.status;
+    }
+
+    // 1. the count pass, one query block of the rows at a time over the whole train set
+    const size_t es = (size_t)elem_size(tr->dtype);
+    for (int64_t q0 = 0; q0 < n; q0 += qblock) {
+        const int64_t nb_q = std::min(qblock, n - q0);
+        RadiusSweepArgs ca = a.s;
+        ca.test = static_cast<const char*>(tr->feat) + (size_t)q0 * (size_t)tr->ld * es;
+        ca.nq = nb_q;
+        stage_begin(c, st, "radius_sweep");
+        HIP_OR_FAIL(c, hipMemsetAsync(ca.hist, 0, sizeof(int32_t) * (size_t)(R + 1) * (size_t)nb_q, st));
+        if (form) {
+            RadiusSweepGemmArgs cg = g.s;
+            cg.test = ca.test; cg.nq = nb_q;
+            cg.qop = static_cast<const char*>(g.s.qop) + (size_t)q0 * 2 * (size_t)tr->d;
+            cg.qnorm = g.s.qnorm + q0; cg.qstat = g.s.qstat + q0;
+            HIP_OR_FAIL(c, knn_launch_radius_sweep_gemm(cg, st));
+        }
+        HIP_OR_FAIL(c, knn_launch_radius_sweep_tile(ca, c->metric, st));
+        stage_end(c, st);
+        RadiusSweepFinishArgs f{};
+        f.hist = ca.hist; f.nq = nb_q; f.R = R; f.ld_out = ldc; f.count = count + q0;
+        stage_begin(c, st, "radius_sweep_finish");
+        HIP_OR_FAIL(c, knn_launch_radius_sweep_finish(f, st));
+        stage_end(c, st);
+    }
+    stage_begin(c, st, "dbscan_labels");
+    HIP_OR_FAIL(c, knn_launch_dbscan_sweep_prepare(count, ldc, R, min_samples, n, level, cand, nb, st));
+    HIP_OR_FAIL(c, knn_launch_dbscan_sweep_init(parent, best, R, n, st));
+    stage_end(c, st);
+
+    // 2. the link pass
+    a.db.level = level; a.db.parent = parent; a.db.unions = unions;
+    a.db.cand = cand; a.db.nb = nb; a.db.root = root; a.db.best = best;
+    g.db = a.db;
+    stage_begin(c, st, "dbscan_sweep_link");
+    if (form) HIP_OR_FAIL(c, knn_launch_dbscan_sweep_gemm(g, DBSCAN_SWEEP_LINK, st));
+    HIP_OR_FAIL(c, knn_launch_dbscan_sweep_tile(a, c->metric, DBSCAN_SWEEP_LINK, st));
+    stage_end(c, st);
+
+    // 3. the level chain and the cluster numbers of every level
+    stage_begin(c, st, "dbscan_labels");
+    for (int r = 0; r < R; r++) {
+        HIP_OR_FAIL(c, knn_launch_dbscan_sweep_level(parent, level, r, R, n, root, isroot + (size_t)r * N, status, unions, st));
+        HIP_OR_FAIL(c, knn_launch_radius_scan(isroot + (size_t)r * N, 1, n, nullptr, offs + (size_t)r * (N + 1), st));
+    }
+    stage_end(c, st);
+
+    // 4. the border pass
+    stage_begin(c, st, "dbscan_sweep_border");
+    if (form) HIP_OR_FAIL(c, knn_launch_dbscan_sweep_gemm(g, DBSCAN_SWEEP_BORDER, st));
+    HIP_OR_FAIL(c, knn_launch_dbscan_sweep_tile(a, c->metric, DBSCAN_SWEEP_BORDER, st));
+    stage_end(c, st);
+
+    // 5. labels, summary, and the call's one synchronisation
+    stage_begin(c, st, "dbscan_labels");
+    HIP_OR_FAIL(c, knn_launch_dbscan_sweep_labels(level, root, best, offs, R, n, ld_out, d_labels, info, st));
+    if (d_summary)
+        HIP_OR_FAIL(c, hipMemcpyAsync(d_summary, info, sizeof(int64_t) * 4 * (size_t)R, hipMemcpyDeviceToDevice, st));
+    stage_end(c, st);
+    s = radius_finish(c, st, form);
+    if (s == KNN_OK) {
+        c->stats[18] = c->ctrl_host[3];
+        unsigned long long u = 0;
+        if (unions && hipMemcpy(&u, unions, sizeof(u), hipMemcpyDeviceToHost) == hipSuccess) c->stats[19] = (int64_t)u;
+    }
+    return s;
 }
 
 }  // extern "C"

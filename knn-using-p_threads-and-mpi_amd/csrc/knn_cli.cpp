@@ -3,7 +3,7 @@
 //   knn_cli train.arff test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]]
 //           [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress]
 //           [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]] [--lof[=KLO] [--lof-threshold=T]]
-//           [--dbscan=R [--min-samples=M]]
+//           [--dbscan=R [--min-samples=M]] [--dbscan-radii=R1,R2,... [--min-samples=M]]
 //
 // Same positional arguments as ./main (main.cpp:114-122; k parsed with strtol) plus the
 // optional worker count of ./multi-thread (multi-thread.cpp:135-143), here the number of
@@ -46,6 +46,11 @@
 // with --metric=.  With any other mode switch (--sweep, --weights=, --regress, --radius=, --radii=,
 // --outlier=, --lof), an R that is not a number >= 0 or an M that is no integer >= 1, it prints a
 // usage error and exits 1.
+// --dbscan-radii=R1,R2,... [--min-samples=M]: DBSCAN at up to 32 non-decreasing radii from three
+// distance passes (KNN_dbscan_sweep): --dbscan='s line once per radius, in the order given.  Composes
+// with --metric=.  With --dbscan=, with any other mode switch, with more than 32 values, a value that
+// is not a number >= 0, values that descend or an M that is no integer >= 1, it prints a usage error
+// and exits 1.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -73,6 +78,7 @@ static int run(int argc, char* argv[]) {
     const char* lof_thr_arg = nullptr;
     const char* dbscan_arg = nullptr;
     const char* min_samples_arg = nullptr;
+    const char* dbscan_radii_arg = nullptr;
     bool outlier_given = false;
     for (int i = 0; i < argc; i++) {
         if (!std::strncmp(argv[i], "--outlier=", 10)) outlier_given = true;
@@ -85,6 +91,7 @@ static int run(int argc, char* argv[]) {
         else if (!std::strncmp(argv[i], "--lof=", 6)) { lof = true; lof_arg = argv[i] + 6; }
         else if (!std::strncmp(argv[i], "--lof-threshold=", 16)) lof_thr_arg = argv[i] + 16;
         else if (!std::strncmp(argv[i], "--dbscan=", 9)) dbscan_arg = argv[i] + 9;
+        else if (!std::strncmp(argv[i], "--dbscan-radii=", 15)) dbscan_radii_arg = argv[i] + 15;
         else if (!std::strncmp(argv[i], "--min-samples=", 14)) min_samples_arg = argv[i] + 14;
         else if (!std::strncmp(argv[i], "--radius=", 9)) radius_arg = argv[i] + 9;
         else if (!std::strncmp(argv[i], "--radii=", 8)) radii_arg = argv[i] + 8;
@@ -106,7 +113,7 @@ static int run(int argc, char* argv[]) {
     }
     argc = n;
     if (argc != 4 && argc != 5) {
-        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress] [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]] [--lof[=KLO] [--lof-threshold=T]] [--dbscan=R [--min-samples=M]]"
+        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress] [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]] [--lof[=KLO] [--lof-threshold=T]] [--dbscan=R [--min-samples=M]] [--dbscan-radii=R1,R2,... [--min-samples=M]]"
                   << std::endl;
         std::exit(0);
     }
@@ -165,7 +172,33 @@ static int run(int argc, char* argv[]) {
     }
     float dbscan_r = 0.0f;
     int min_samples = 5;
-    if (dbscan_arg || min_samples_arg) {
+    std::vector<float> dbscan_radii;
+    if (dbscan_radii_arg) {
+        bool ok = !dbscan_arg && !sweep && !regress && !radius_arg && !radii_arg && !weights_given && !outlier_given &&
+                  !lof && !lof_thr_arg;
+        for (const char* p = dbscan_radii_arg; ok;) {
+            char* end = nullptr;
+            const float r = std::strtof(p, &end);
+            ok = end != p && (*end == ',' || *end == '\0') && r >= 0.0f && dbscan_radii.size() < 32 &&  // (NaN fails >=)
+                 (dbscan_radii.empty() || r >= dbscan_radii.back());
+            if (ok) dbscan_radii.push_back(r);
+            if (!ok || *end == '\0') break;
+            p = end + 1;
+        }
+        if (ok && min_samples_arg) {
+            char* end = nullptr;
+            const long v = std::strtol(min_samples_arg, &end, 10);
+            ok = end != min_samples_arg && *end == '\0' && v >= 1 && v <= 0x7fffffffL;
+            min_samples = (int)v;
+        }
+        if (!ok) {
+            std::cerr << "usage: --dbscan-radii=R1,R2,... needs 1 to 32 non-decreasing numbers >= 0, --min-samples=M an "
+                         "integer M >= 1, and does not combine with --dbscan=, --sweep, --weights=, --regress, --radius=, "
+                         "--radii=, --outlier= or --lof"
+                      << std::endl;
+            std::exit(1);
+        }
+    } else if (dbscan_arg || min_samples_arg) {
         bool ok = dbscan_arg && !sweep && !regress && !radius_arg && !radii_arg && !weights_given && !outlier_given &&
                   !lof && !lof_thr_arg;
         if (ok) {
@@ -191,10 +224,30 @@ static int run(int argc, char* argv[]) {
     ArffParser parserTrain(argv[1]);
     ArffParser parserTest(argv[2]);
     ArffData* train = parserTrain.parse();
-    ArffData* test = (loo || lof || dbscan_arg) ? train : parserTest.parse();
+    ArffData* test = (loo || lof || dbscan_arg || dbscan_radii_arg) ? train : parserTest.parse();
     knn_amd_init();
 
     struct timespec start, end;
+    if (dbscan_radii_arg) {
+        const int R = (int)dbscan_radii.size();
+        const long nt = train->num_instances();
+        std::vector<long> summary((size_t)R * 4, 0);
+        int* labels = KNN_dbscan_sweep(train, dbscan_radii.data(), R, min_samples, summary.data());
+        for (int r = 0; r < R; r++)
+            printf("The radius-%g DBSCAN (min_samples %d) of %s found %ld clusters: %ld core, %ld border, %ld noise rows\n",
+                   (double)dbscan_radii[r], min_samples, argv[1], summary[4 * r], summary[4 * r + 1], summary[4 * r + 2],
+                   summary[4 * r + 3]);
+        if (const char* p = std::getenv("KNN_CLI_PRED_OUT")) {  // test hook: one line of n labels per radius
+            FILE* f = std::fopen(p, "w");
+            for (int r = 0; r < R; r++) {
+                for (long i = 0; i < nt; i++) std::fprintf(f, i ? " %d" : "%d", labels[(size_t)r * nt + i]);
+                std::fprintf(f, "\n");
+            }
+            std::fclose(f);
+        }
+        std::free(labels);
+        return 0;
+    }
     if (dbscan_arg) {
         long summary[4] = {0, 0, 0, 0};
         int* labels = KNN_dbscan(train, dbscan_r, min_samples, summary);

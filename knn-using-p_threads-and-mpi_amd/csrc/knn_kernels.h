@@ -441,6 +441,41 @@ struct RadiusVoteSweepArgs {
 };
 hipError_t knn_launch_radius_vote_sweep(const RadiusVoteSweepArgs& a, hipStream_t st);
 
+// The DBSCAN eps sweep (knn_dbscan_sweep.hip; knn_amd.h "DBSCAN sweep"): the link and the border
+// pass of all R thresholds at once, over a self-join (test == train, nq == nt) with the sweep
+// pass's arguments (hist / chist / classes / labels unused), and the integer kernels around them.
+//   level [nt]      c(i): the smallest r at which row i is a core row, R when there is none
+//   parent [R][nt]  LINK: one union-find forest per level, each started as the identity
+//   cand / nb       BORDER: query q is train row cand[q], q < *nb (blocks past it return at once)
+//   root [nt][R]    BORDER: a row's root at every level at which it is a core row, else -1
+//   best [R][nt]    BORDER: unsigned atomicMin of the offered roots (0xffffffff: none)
+enum { DBSCAN_SWEEP_LINK = 0, DBSCAN_SWEEP_BORDER = 1 };
+struct DbscanSweepArgs {
+    const int32_t* level;
+    int32_t* parent;
+    unsigned long long* unions;  // LINK, optional (profile = 2): += successful hooks, one add per wave
+    const int32_t* cand; const int32_t* nb;
+    const int32_t* root;
+    uint32_t* best;
+};
+struct DbscanSweepTileArgs { RadiusSweepArgs s; DbscanSweepArgs db; };
+struct DbscanSweepGemmArgs { RadiusSweepGemmArgs s; DbscanSweepArgs db; };
+hipError_t knn_launch_dbscan_sweep_tile(DbscanSweepTileArgs a, int metric, int mode, hipStream_t st);
+hipError_t knn_launch_dbscan_sweep_gemm(DbscanSweepGemmArgs a, int mode, hipStream_t st);
+// count [R][ldc] (the sweep's) -> level [n] and the border candidates cand[0 .. *nb) (nb zeroed by the caller)
+hipError_t knn_launch_dbscan_sweep_prepare(const int32_t* count, int64_t ldc, int R, int32_t min_samples, int64_t n,
+                                           int32_t* level, int32_t* cand, int32_t* nb, hipStream_t st);
+hipError_t knn_launch_dbscan_sweep_init(int32_t* parent, uint32_t* best, int R, int64_t n, hipStream_t st);
+// level r of the chain, to be launched for r = 0 .. R - 1 in this order: root[.][r], isroot_r [n],
+// and every core row of level r joined to its root in forest r + 1
+hipError_t knn_launch_dbscan_sweep_level(int32_t* parent, const int32_t* level, int r, int R, int64_t n, int32_t* root,
+                                         int32_t* isroot_r, int32_t* status, unsigned long long* unions, hipStream_t st);
+// offs [R][n + 1]: per level the exclusive scan of isroot (k_radius_scan); labels [R][ld_out];
+// info int64 [R][4] {clusters, core, border, noise}, zeroed by the caller
+hipError_t knn_launch_dbscan_sweep_labels(const int32_t* level, const int32_t* root, const uint32_t* best,
+                                          const int64_t* offs, int R, int64_t n, int64_t ld_out, int32_t* labels,
+                                          int64_t* info, hipStream_t st);
+
 struct GenerateArgs {
     void* out; int32_t* labels; int64_t row0; int64_t n; int d; int ld;
     int bf16_out; int kind; uint64_t seed; uint32_t stream; int C;
