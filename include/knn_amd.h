@@ -745,8 +745,9 @@ knn_status knn_radius_vote_sweep_device(knn_ctx* ctx, int64_t nq, int64_t n_trai
  * call; [18] is the number of rows sent through the border pass, [19], under profile = 2, the
  * successful hooks of the union-find.  A union-find loop that reaches its iteration cap (3 n + 8
  * steps, a bound no correct run can reach) gives KNN_EHIP, "internal error", never a hang.
- * Not here: sample_weight, HDBSCAN / OPTICS, a host-buffer entry point, a multi-rank driver (lists
- * concatenate by shard: knn_dbscan_lists_device).  The eps sweep is "DBSCAN sweep" below.
+ * Not here: sample_weight, OPTICS, a host-buffer entry point, a multi-rank driver (lists
+ * concatenate by shard: knn_dbscan_lists_device).  The eps sweep is "DBSCAN sweep" below, HDBSCAN's
+ * spanning tree (every eps at once, core rows only) "Spanning tree".
  */
 knn_status knn_dbscan_device(knn_ctx* ctx, const knn_dataset* train, float thr, int32_t min_samples,
                              int32_t* d_labels, int32_t* d_count, int64_t* d_summary, void* hip_stream);
@@ -812,13 +813,99 @@ knn_status knn_dbscan_lists_device(knn_ctx* ctx, int64_t n, const int64_t* d_off
  * knn_last_stats(): [13] and [14] read as after a radius call ([14]: all three passes together);
  * [18] the rows sent through the border pass; [19], under profile = 2, the successful hooks of the
  * link pass and the level chain together.  The union-find's step cap gives KNN_EHIP, never a hang.
- * Not here: sample_weight, a lists-held sweep, a min_samples sweep, HDBSCAN / OPTICS, host-buffer
- * entry points, the MFMA form at widths other than 64 / 128 / 256.
+ * Not here: sample_weight, a lists-held sweep, a min_samples sweep, OPTICS, host-buffer entry points,
+ * the MFMA form at widths other than 64 / 128 / 256.  Every eps without a ladder: "Spanning tree".
  */
 knn_status knn_dbscan_sweep_device(knn_ctx* ctx, const knn_dataset* train, const float* thresholds, int32_t R,
                                    int32_t min_samples, int64_t ld_out, int32_t* d_labels /* [R][ld_out] */,
                                    int32_t* d_count /* optional */, int64_t* d_summary /* [R][4], optional */,
                                    void* hip_stream);
+
+/*
+ * Spanning tree: the minimum spanning tree of the mutual-reachability graph of the train set -- the
+ * part of HDBSCAN that needs a GPU.  It has n - 1 edges and answers every radius at once: cutting it at
+ * thr gives DBSCAN's clusters of core rows (DBSCAN*) at thr, for any number of thresholds, with no
+ * further distance pass; it is also the single-linkage dendrogram the condensed tree is computed from.
+ *   T           the train set of n rows under the context's metric.
+ *   D           the value knn_radius_count_device tests: squared under the Euclidean metric, symmetric
+ *               to the bit.  Everything below is in D's units, like thr in "Radius neighbours".  sqrtf
+ *               is monotone, so the tree is a minimum spanning tree in unsquared units too.
+ *   core        c(i) is the min_samples-th smallest D(i, .) over all of T, the row itself and its copies
+ *               included (sklearn's rule, and DBSCAN's "the row counts itself"): entry min_samples - 1
+ *               of row i's plain top-K list against T, self_base = -1, nothing removed.  So c(i) <= thr
+ *               iff knn_dbscan_device's count[i] >= min_samples at thr.  c(i) = +inf when that entry is
+ *               missing (fewer than min_samples rows qualify under top-k's rule D < FLT_MAX: a row
+ *               with a NaN feature under the Euclidean and Manhattan metrics, whose D is NaN against
+ *               every row, itself included; the Chebyshev maximum skips a NaN difference, "Metrics").
+ *               1 <= min_samples <= 256; min_samples > n is KNN_EINVAL, the outputs untouched.
+ *   edges       a pair a != b is an edge iff D(a, b) < FLT_MAX (top-k's rule: NaN, inf and the sentinel
+ *               never qualify), with weight w = fmaxf(fmaxf(c(a), c(b)), D) in binary32.  w >= +0, so
+ *               its bit pattern orders as an unsigned integer; w may be +inf.
+ *   order       edges are STRICTLY ordered by (w, min(a, b), max(a, b)), and the tree is the unique
+ *               minimum spanning forest under that order (one tree per component of the graph of
+ *               edges).  For a fixed row q, ordering its candidates t by (w, t) is the same order.
+ *   outputs     d_w fp32 [n - 1], d_a / d_b int32 [n - 1] with a < b, ascending by that order; d_core
+ *               fp32 [n], optional; d_summary int64 [4] = {edges E, components n - E, rounds run, rows
+ *               sent through distance passes summed over the rounds}.  Entries past E are left as
+ *               the caller had them.
+ *   determinism the same bits on every run, with any train_splits and with the list shortcut on or
+ *               off: every reduction is an integer minimum, the forest does not depend on the order
+ *               of the unions, the final sort fixes the edge order.  No floating-point atomics.
+ * knn_mst_device: Boruvka rounds.
+ *   1. lists    the vote-less top-K pass of all rows against T (knn_lof_fit_device's, nothing
+ *               removed), K = max(min_samples, 32) capped at n; c(i) and dlast(i), the list's last
+ *               distance.
+ *   2. resolve  per round and row, the smallest key bits(w) << 32 | t over the listed rows t of another
+ *               component.  The row is resolved when its list holds every candidate it has (K == n, or
+ *               a missing entry) or a listed candidate has w < dlast(i) STRICTLY (an unlisted row has
+ *               D >= dlast, and only the strict test excludes a tie the (w, t) order could give to an
+ *               unlisted row of smaller index).  The other rows are compacted into a candidate list.
+ *   3. pass     the candidates against T, k_radius_tile's direct form and segments: per pair
+ *               ok = D < FLT_MAX && comp[t] != comp[q], the lane keeps its minimum key per query, the
+ *               wave's minimum meets the other segments' in a 64-bit integer atomicMin.
+ *   4. pick     the component's smallest edge under (w, lo, hi) by two integer atomicMin steps; one
+ *               union per component root in DBSCAN's lock-free union-find; the call that hooked
+ *               appends the edge (the strict order makes the chosen edges cycle-free, so an edge
+ *               chosen from both sides hooks once); flatten.  One counter read-back, the round's one
+ *               synchronisation.
+ *   5. sort     by (w, a, b) (rocPRIM's radix sort, stable: on (a, b), then on bits(w)).
+ *   Rounds run until the tree is complete or no component has a candidate, at most
+ *   ceil(log2 n) + 1; more, a round that hooks nothing while candidates exist, or the union-find's
+ *   step cap give KNN_EHIP "internal error", never a spin.  The test hook KNN_MST_LISTS=0 (read at
+ *   knn_create) turns the list shortcut off: every row goes through every pass.
+ *   KNN_EINVAL, the outputs untouched, for min_samples outside [1, 256] or above n, n > INT32_MAX, a
+ *   NULL d_summary, and NULL d_w / d_a / d_b when n >= 2.  n == 0 and n == 1 return KNN_OK with zero
+ *   edges.
+ * knn_mst_cut_device: DBSCAN* at R thresholds from a tree the caller holds.
+ *   thresholds  a HOST array thr[0 .. R - 1], 1 <= R <= 32, each in [0, FLT_MAX), non-decreasing: the
+ *               DBSCAN sweep's checks and error codes.
+ *   cut         row i is a core row at r iff c(i) <= thr[r]; the clusters at r are the components of
+ *               the forest's edges with w <= thr[r], numbered 0, 1, ... by ascending smallest row
+ *               ("DBSCAN"'s numbering); every other row is -1.  BORDER ROWS ARE NOT ASSIGNED: this is
+ *               DBSCAN*, HDBSCAN's own definition.  labels[r][i] equals knn_dbscan_sweep_device's
+ *               label where its count[r][i] >= min_samples, and is -1 elsewhere.
+ *   outputs     d_labels int32 [R][ld_out] (ld_out >= n; the columns past n are not touched);
+ *               d_summary int64 [R][3], optional, {clusters, core rows, other rows}.
+ *   The levels are nested: one union-find forest is carried over, level r joins the edges with
+ *   thr[r - 1] < w <= thr[r] in parallel, then the components of the core rows are numbered.  The
+ *   edges need not be sorted.  Every edge index is checked against [0, n) before any table is read
+ *   with it: KNN_EINVAL.  KNN_EINVAL too, before anything is launched, for n > INT32_MAX, n_edges
+ *   outside [0, n - 1], ld_out < n, bad thresholds, and NULL d_core / d_labels (n > 0) or d_w / d_a /
+ *   d_b (n_edges > 0).  n == 0 returns KNN_OK and zero summaries.
+ * Stages under profile = 1: the list pass under its own names ("direct_tile", "gemm_filter", ...),
+ * "mst_lists" (c and dlast), per round "mst_resolve", "mst_pass", "mst_pick", then "mst_sort"; the cut
+ * is "mst_cut".  knn_last_stats()[20] is the rounds run and [21] the rows sent through passes.
+ * Not here: the condensed tree and EOM / leaf extraction (ties among mutual-reachability weights are
+ * the rule -- every edge at a row's core distance -- and sklearn's flat labels then depend on its
+ * Prim order: that needs a tie rule of its own), an MFMA-bracketed form of the pass, skipping rows by
+ * a per-component upper bound, halving the pass by symmetry, a multi-rank driver, a host-buffer entry.
+ */
+knn_status knn_mst_device(knn_ctx* ctx, const knn_dataset* train, int32_t min_samples, float* d_w, int32_t* d_a,
+                          int32_t* d_b, float* d_core /* optional */, int64_t* d_summary /* [4] */, void* hip_stream);
+knn_status knn_mst_cut_device(knn_ctx* ctx, int64_t n, int64_t n_edges, const float* d_w, const int32_t* d_a,
+                              const int32_t* d_b, const float* d_core, const float* thresholds, int32_t R,
+                              int64_t ld_out, int32_t* d_labels /* [R][ld_out] */,
+                              int64_t* d_summary /* [R][3], optional */, void* hip_stream);
 
 /* Per-stage device times (ms) of the last predict call when opts.profile >= 1.
  * names: optional array of n const char* to receive stage names. Returns the
@@ -847,9 +934,10 @@ int32_t knn_stage_times(const knn_ctx* ctx, const char** names, float* ms, int32
  * int8 filter's seed pass lowered to a finite bound (k_seed_thr; counted under profile = 2 only,
  * like [0] and [12]; 0 otherwise), [18] the rows a DBSCAN call sent through its border pass (the
  * non-core rows with a neighbour besides themselves), [19] the successful hooks of its union-find
- * (profile = 2 only; 0 otherwise).
- * Returns the number written (<= 20); a caller that asks for 11, 12, 13, 15, 17 or 18 gets the first
- * 11, 12, 13, 15, 17 or 18 as before. */
+ * (profile = 2 only; 0 otherwise), [20] the rounds a spanning-tree call ran and [21] the rows its rounds
+ * sent through distance passes (knn_mst_device).
+ * Returns the number written (<= 22); a caller that asks for 11, 12, 13, 15, 17, 18 or 20 gets the first
+ * 11, 12, 13, 15, 17, 18 or 20 as before. */
 int32_t knn_last_stats(const knn_ctx* ctx, int64_t* out, int32_t n);
 
 /*

@@ -226,6 +226,24 @@ int* KNN_dbscan(ArffData* train, float radius, int min_samples, long* summary = 
 // border rows, noise rows}.  Runs on the first device.
 int* KNN_dbscan_sweep(ArffData* train, const float* radii, int n_radii, int min_samples,
                       long* summary /* [n_radii][4] */ = nullptr);
+// The mutual-reachability spanning tree (knn_amd.h "Spanning tree"; the tree HDBSCAN is computed from) of
+// the train rows under the run's metric, 1 <= min_samples <= 256.  The last attribute is not read.
+// w / a / b [edges]: the edges ascending by (w, a, b), a < b, w = max(c(a), c(b), D) in the units of the
+// library's reported distance (squared under the Euclidean metric); core [n]: c.  The arrays are
+// malloc'd: KNN_mst_free.  edges == n - 1 when every pair of rows has a finite distance.  Runs on the
+// first device.
+struct KnnMst {
+    long n, edges;
+    float* w; int* a; int* b; float* core;
+    long rounds, pass_rows;  // the Boruvka rounds run, the rows they sent through distance passes
+};
+KnnMst KNN_mst(ArffData* train, int min_samples);
+void KNN_mst_free(KnnMst& tree);
+// DBSCAN* at every one of 1 <= n_radii <= 32 non-decreasing radii from that tree, with no distance pass:
+// returns malloc'd int[n_radii * n] laid out [n_radii][n], row r what KNN_dbscan returns at radii[r] on its
+// core rows and -1 on every other row (border rows are not assigned); caller frees.  summary (optional)
+// receives [n_radii][3] {clusters, core rows, other rows}.
+int* KNN_mst_cut(const KnnMst& tree, const float* radii, int n_radii, long* summary /* [n_radii][3] */ = nullptr);
 // main.cpp:87 -- calloc'd int[C*C], C = dataset->num_classes(), row = true class.
 int* computeConfusionMatrix(int* predictions, ArffData* dataset);
 // main.cpp:102

@@ -158,6 +158,8 @@ def load_library(path=LIB_PATH):
         "knn_dbscan_device": (I32, [P, DS, F, I32, P, P, P, P]),
         "knn_dbscan_lists_device": (I32, [P, I64, P, P, I32, P, P, P, P]),
         "knn_dbscan_sweep_device": (I32, [P, DS, P, I32, I32, I64, P, P, P, P]),
+        "knn_mst_device": (I32, [P, DS, I32, P, P, P, P, P, P]),
+        "knn_mst_cut_device": (I32, [P, I64, I64, P, P, P, P, P, I32, I64, P, P, P]),
         "knn_arff_copy_targets": (I32, [P, P, I32, P]),
         "knn_stage_times": (I32, [P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(F), I32]),
         "knn_last_stats": (I32, [P, ctypes.POINTER(I64), I32]),
@@ -1120,6 +1122,72 @@ class Context:
             _opt_ptr(cnt), summary.data_ptr(), self._stream(stream, train)))
         return labels, (None if cnt is None else cnt[:, :n]), summary
 
+    # the mutual-reachability spanning tree (knn_amd.h "Spanning tree")
+    def mst_device(self, train, min_samples=5, core=False, w=None, a=None, b=None, stream=None, d=None):
+        """The minimum spanning tree of the mutual-reachability graph of the train rows under the
+        context's metric (knn_mst_device): w = max(c(a), c(b), D(a, b)), c the min_samples-th smallest
+        distance of a row (itself included), edges strictly ordered by (w, a, b).  Returns (w float32
+        [E], a int32 [E], b int32 [E] with a < b, ascending by that order; core float32 [n] or None
+        with core=False; summary int64 [4] = edges E, components n - E, rounds, rows sent through
+        distance passes).  E = n - 1 when every pair of rows has a finite distance.  All in the units
+        of the reported distance (squared under the Euclidean metric).  w / a / b may be tensors of at
+        least n - 1 elements to fill: the entries past E are left as they were."""
+        import torch
+        if int(min_samples) != min_samples:
+            raise KnnError(KNN_EINVAL, f"min_samples must be an integer, got {min_samples!r}")
+        self._on_device(train)
+        self._note_train(train)
+        tr = _device_dataset(train, None, d)
+        n, dev = tr.n, train.device
+        m = max(n - 1, 1)
+        w = torch.empty(m, dtype=torch.float32, device=dev) if w is None else _check_tensor(w, "w", torch.float32, m)
+        a = torch.empty(m, dtype=torch.int32, device=dev) if a is None else _check_tensor(a, "a", torch.int32, m)
+        b = torch.empty(m, dtype=torch.int32, device=dev) if b is None else _check_tensor(b, "b", torch.int32, m)
+        c = torch.empty(max(n, 1), dtype=torch.float32, device=dev)[:n] if core else None
+        summary = torch.zeros(4, dtype=torch.int64, device=dev)
+        self._check(self.lib.knn_mst_device(
+            self.h, ctypes.byref(tr), int(min_samples), w.data_ptr(), a.data_ptr(), b.data_ptr(), _opt_ptr(c),
+            summary.data_ptr(), self._stream(stream, train)))
+        E = int(summary[0].item())
+        return w[:E], a[:E], b[:E], c, summary
+
+    def mst_cut_device(self, w, a, b, core, radii=None, thresholds=None, labels=None, stream=None):
+        """DBSCAN* at every one of R <= 32 non-decreasing radii from a tree mst_device returned, with no
+        distance pass (knn_mst_cut_device).  Exactly one of radii= and thresholds= (as the radius
+        sweep).  core is mst_device(..., core=True)'s; it gives n.  Returns (labels int32 [R][n]: a
+        core row's cluster, numbered 0, 1, ... by ascending smallest row, -1 for every other row --
+        border rows are not assigned; summary int64 [R][3] = clusters, core rows, other rows).
+        labels may be an int32 tensor [R][ld] with ld >= n to fill."""
+        import torch
+        thr = self._thresholds(radii, thresholds)
+        R = int(thr.size)
+        self._on_device(core)
+        _check_tensor(core, "core", torch.float32)
+        n, dev, rows = core.numel(), core.device, max(R, 1)
+        E = w.numel()
+        _check_tensor(w, "w", torch.float32)
+        _check_tensor(a, "a", torch.int32, E)
+        _check_tensor(b, "b", torch.int32, E)
+        ld = n
+        if labels is None:
+            labels = torch.empty((rows, max(n, 1)), dtype=torch.int32, device=dev)[:, :n]
+            ld = max(n, 1)
+        else:
+            if labels.dtype != torch.int32 or labels.dim() != 2 or labels.shape[0] < rows or labels.stride(1) != 1:
+                raise KnnError(KNN_EINVAL, "labels must be an int32 tensor [R][ld] with unit column stride")
+            self._on_device(labels)
+            ld = labels.stride(0) if labels.shape[0] > 1 else max(labels.shape[1], 1)
+            if labels.shape[1] < n:
+                ld = labels.shape[1]  # (the library refuses ld_out < n)
+        summary = torch.zeros((rows, 3), dtype=torch.int64, device=dev)
+        # (at least one element: an empty tensor has no address to hand to the library)
+        one = lambda t: t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev)
+        self._check(self.lib.knn_mst_cut_device(
+            self.h, n, E, one(w).data_ptr(), one(a).data_ptr(), one(b).data_ptr(), one(core).data_ptr(),
+            thr.ctypes.data_as(ctypes.c_void_p), R, ld, labels.data_ptr(), summary.data_ptr(),
+            self._stream(stream, core)))
+        return labels, summary
+
     # radius sweep (knn_amd.h "Radius sweep")
     def _thresholds(self, radii, thresholds):
         """The binary32 thresholds of a sweep: exactly one of radii= (each float32(r) * float32(r)
@@ -1363,8 +1431,8 @@ class Context:
         return out
 
     def stats(self):
-        v = (ctypes.c_int64 * 20)()
-        self.lib.knn_last_stats(self.h, v, 20)
+        v = (ctypes.c_int64 * 22)()
+        self.lib.knn_last_stats(self.h, v, 22)
         return {"candidates": v[0], "fallback_queries": v[1], "train_segments": v[2],
                 "filter_operands": FILTER_OPERANDS.get(v[3], v[3]), "rerun_split": bool(v[4]),
                 "fused_norm": bool(v[5]), "h2d_train_bytes": v[6], "h2d_query_bytes": v[7],
@@ -1373,7 +1441,8 @@ class Context:
                 "filter_element": FILTER_ELEMENTS.get(v[11], v[11]) if v[3] in (1, 2, 3) else None,
                 "parked_passes": v[12], "radius_form": RADIUS_FORMS.get(v[13], v[13]),
                 "radius_exact_pairs": v[14], "filter_width": v[15], "filter_chunks": v[16],
-                "seeded_queries": v[17], "dbscan_border_queries": v[18], "dbscan_unions": v[19]}
+                "seeded_queries": v[17], "dbscan_border_queries": v[18], "dbscan_unions": v[19],
+                "mst_rounds": v[20], "mst_pass_rows": v[21]}
 
     def last_seed(self, nq):
         """Test hook (knn_debug_last_seed): the thresholds the int8 filter's seed pass published in the
@@ -1727,6 +1796,40 @@ def dbscan_sizes(labels):
         return torch.bincount(lab[lab >= 0])
     lab = np.asarray(labels).reshape(-1).astype(np.int64)
     return np.bincount(lab[lab >= 0]).astype(np.int64)
+
+
+def mst_linkage(w, a, b, n):
+    """scipy's linkage matrix Z float64 [n - 1][4] of a spanning tree (host arrays or tensors, in
+    mst_device's order): the edges merged in order, heights w, scipy's cluster ids (a leaf is its
+    row, merge j makes cluster n + j) and sizes, the smaller id first.  Defined only for a connected
+    tree: ValueError unless there are n - 1 edges that join all n rows."""
+    host = lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+    w, a, b = host(w).astype(np.float64), host(a).astype(np.int64), host(b).astype(np.int64)
+    n = int(n)
+    if n < 1 or not (w.shape == a.shape == b.shape == (n - 1,)):
+        raise ValueError(f"a connected tree of {n} rows has {n - 1} edges, got {w.shape[0] if w.ndim else w.shape}")
+    parent = np.arange(n, dtype=np.int64)
+    cid = np.arange(n, dtype=np.int64)   # a root's scipy cluster id
+    size = np.ones(n, dtype=np.int64)
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    Z = np.empty((n - 1, 4), dtype=np.float64)
+    for j in range(n - 1):
+        if not (0 <= a[j] < n and 0 <= b[j] < n):
+            raise ValueError(f"edge {j} names a row outside [0, {n})")
+        ra, rb = find(a[j]), find(b[j])
+        if ra == rb:
+            raise ValueError(f"edge {j} closes a cycle: not a tree")
+        Z[j] = (min(cid[ra], cid[rb]), max(cid[ra], cid[rb]), w[j], size[ra] + size[rb])
+        parent[rb] = ra
+        size[ra] += size[rb]
+        cid[ra] = n + j
+    return Z
 
 
 def best_eps(summary):

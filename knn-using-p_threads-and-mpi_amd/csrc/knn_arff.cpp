@@ -1219,6 +1219,122 @@ int* KNN_dbscan_sweep(ArffData* train, const float* radii, int n_radii, int min_
     return labels;
 }
 
+// The mutual-reachability spanning tree of the train rows on the first device (knn_amd.h "Spanning
+// tree"), staged as KNN_dbscan: the cached train upload, knn_mst_device, the edges and core distances back
+KnnMst KNN_mst(ArffData* train, int min_samples) {
+    const KnnFlatView& tr = train->flat();
+    if (min_samples < 1 || min_samples > 256) throwf("KNN_mst: min_samples=%d outside [1, 256]", min_samples);
+    const size_t n = (size_t)tr.n, m = n > 1 ? n - 1 : 1;
+    KnnMst t{};
+    t.n = (long)n;
+    t.w = (float*)std::malloc(sizeof(float) * m);
+    t.a = (int*)std::malloc(sizeof(int) * m);
+    t.b = (int*)std::malloc(sizeof(int) * m);
+    t.core = (float*)std::malloc(sizeof(float) * (n > 0 ? n : 1));
+    std::string why;
+    knn_status s = KNN_OK;
+    try {
+        if (!t.w || !t.a || !t.b || !t.core) throwf("KNN_mst: out of memory");
+        std::vector<knn_ctx*>& cs = contexts();
+        knn_ctx* c = cs[0];
+        std::lock_guard<std::mutex> busy(*devices().busy[0]);
+        const int dev = knn_ctx_device(c);
+        hipStream_t st = (hipStream_t)knn_ctx_stream(c);
+        knn_dataset htr{tr.feat.data(), tr.labels.data(), tr.n, tr.d, tr.ld, KNN_F32}, dtr{};
+        s = knn_set_generation(c, tr.uid);
+        if (s == KNN_OK) s = knn_ctx_train_device(c, &htr, &dtr);
+        DevMem dw(dev, sizeof(float) * m), da(dev, sizeof(int32_t) * m), db(dev, sizeof(int32_t) * m),
+            dcore(dev, sizeof(float) * n), dsum(dev, sizeof(int64_t) * 4);
+        if (s == KNN_OK && (!dw.p || !da.p || !db.p || !dcore.p || !dsum.p)) throwf("KNN_mst: device allocation failed");
+        if (s == KNN_OK)
+            s = knn_mst_device(c, &dtr, min_samples, (float*)dw.p, (int32_t*)da.p, (int32_t*)db.p, (float*)dcore.p,
+                               (int64_t*)dsum.p, st);
+        int64_t sum[4] = {0, 0, 0, 0};
+        if (s == KNN_OK && hipMemcpy(sum, dsum.p, sizeof(sum), hipMemcpyDeviceToHost) != hipSuccess)
+            throwf("KNN_mst: download failed");
+        const size_t E = (size_t)sum[0];
+        if (s == KNN_OK &&
+            ((E > 0 && (hipMemcpy(t.w, dw.p, sizeof(float) * E, hipMemcpyDeviceToHost) != hipSuccess ||
+                        hipMemcpy(t.a, da.p, sizeof(int32_t) * E, hipMemcpyDeviceToHost) != hipSuccess ||
+                        hipMemcpy(t.b, db.p, sizeof(int32_t) * E, hipMemcpyDeviceToHost) != hipSuccess)) ||
+             (n > 0 && hipMemcpy(t.core, dcore.p, sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess)))
+            throwf("KNN_mst: download failed");
+        t.edges = (long)sum[0];
+        t.rounds = (long)sum[2];
+        t.pass_rows = (long)sum[3];
+        if (s != KNN_OK) why = knn_last_error(c);
+    } catch (...) {
+        KNN_mst_free(t);
+        throw;
+    }
+    if (s != KNN_OK) {
+        KNN_mst_free(t);
+        throwf("KNN_mst: %s (status %d)", why.c_str(), (int)s);
+    }
+    return t;
+}
+
+void KNN_mst_free(KnnMst& t) {
+    std::free(t.w);
+    std::free(t.a);
+    std::free(t.b);
+    std::free(t.core);
+    t = KnnMst{};
+}
+
+// DBSCAN* at every one of n_radii radii from a tree KNN_mst returned: the tree goes up, knn_mst_cut_device,
+// the [n_radii][n] labels come back.  No distance is computed.
+int* KNN_mst_cut(const KnnMst& t, const float* radii, int n_radii, long* summary) {
+    if (n_radii < 1 || n_radii > 32 || !radii) throwf("KNN_mst_cut: n_radii=%d outside [1, 32]", n_radii);
+    for (int r = 0; r < n_radii; r++) {
+        if (!(radii[r] >= 0.0f)) throwf("KNN_mst_cut: radius %d = %g must be >= 0", r, (double)radii[r]);
+        if (r && radii[r] < radii[r - 1]) throwf("KNN_mst_cut: radii %d and %d descend", r - 1, r);
+    }
+    if (t.n < 0 || t.edges < 0 || (t.n > 0 && !t.core) || (t.edges > 0 && (!t.w || !t.a || !t.b)))
+        throwf("KNN_mst_cut: not a tree KNN_mst returned");
+    const size_t n = (size_t)t.n, E = (size_t)t.edges, R = (size_t)n_radii;
+    int* labels = (int*)std::malloc(sizeof(int) * (n > 0 ? R * n : 1));
+    if (!labels) throwf("KNN_mst_cut: out of memory");
+    std::vector<int64_t> sum(3 * R, 0);
+    std::string why;
+    knn_status s = KNN_OK;
+    try {
+        std::vector<knn_ctx*>& cs = contexts();
+        knn_ctx* c = cs[0];
+        std::lock_guard<std::mutex> busy(*devices().busy[0]);
+        // the tree's weights are squared under the Euclidean metric (one binary32 product)
+        std::vector<float> thr(radii, radii + R);
+        if (knn_get_metric(c) == KNN_METRIC_SQEUCLIDEAN)
+            for (float& v : thr) v = v * v;
+        const int dev = knn_ctx_device(c);
+        hipStream_t st = (hipStream_t)knn_ctx_stream(c);
+        DevMem dw(dev, sizeof(float) * E), da(dev, sizeof(int32_t) * E), db(dev, sizeof(int32_t) * E),
+            dcore(dev, sizeof(float) * n), dlab(dev, sizeof(int32_t) * R * n), dsum(dev, sizeof(int64_t) * 3 * R);
+        if (!dw.p || !da.p || !db.p || !dcore.p || !dlab.p || !dsum.p) throwf("KNN_mst_cut: device allocation failed");
+        if ((E > 0 && (hipMemcpy(dw.p, t.w, sizeof(float) * E, hipMemcpyHostToDevice) != hipSuccess ||
+                       hipMemcpy(da.p, t.a, sizeof(int32_t) * E, hipMemcpyHostToDevice) != hipSuccess ||
+                       hipMemcpy(db.p, t.b, sizeof(int32_t) * E, hipMemcpyHostToDevice) != hipSuccess)) ||
+            (n > 0 && hipMemcpy(dcore.p, t.core, sizeof(float) * n, hipMemcpyHostToDevice) != hipSuccess))
+            throwf("KNN_mst_cut: upload failed");
+        s = knn_mst_cut_device(c, t.n, t.edges, (const float*)dw.p, (const int32_t*)da.p, (const int32_t*)db.p,
+                               (const float*)dcore.p, thr.data(), n_radii, t.n, (int32_t*)dlab.p, (int64_t*)dsum.p, st);
+        if (s == KNN_OK &&
+            ((n > 0 && hipMemcpy(labels, dlab.p, sizeof(int32_t) * R * n, hipMemcpyDeviceToHost) != hipSuccess) ||
+             hipMemcpy(sum.data(), dsum.p, sizeof(int64_t) * 3 * R, hipMemcpyDeviceToHost) != hipSuccess))
+            throwf("KNN_mst_cut: download failed");
+        if (s != KNN_OK) why = knn_last_error(c);
+    } catch (...) {
+        std::free(labels);
+        throw;
+    }
+    if (s != KNN_OK) {
+        std::free(labels);
+        throwf("KNN_mst_cut: %s (status %d)", why.c_str(), (int)s);
+    }
+    for (size_t i = 0; summary && i < 3 * R; i++) summary[i] = (long)sum[i];
+    return labels;
+}
+
 void* KNN(void* params) {
     arguments* a = static_cast<arguments*>(params);
     predict_range(a->train, a->test, a->k, a->start, a->end, predictions + a->start);

@@ -14,6 +14,9 @@
 //   DBSCAN (knn_dbscan_*): the radius count pass of the train set against itself -> k_dbscan_init ->
 //     the pass in RADIUS_LINK mode (a lock-free union-find) -> k_dbscan_flatten -> k_radius_scan ->
 //     k_dbscan_labels -> k_dbscan_candidates -> the pass in RADIUS_BORDER mode -> k_dbscan_summary
+//   the spanning tree (knn_mst_*): the vote-less top-k pass of ALL rows -> k_mst_core -> per Boruvka
+//     round k_mst_resolve -> k_mst_tile -> k_mst_pick_lo / _hi -> k_mst_hook -> k_mst_flatten and one
+//     counter read-back -> rocPRIM's radix sort -> k_mst_unpack; the cut: k_mst_cut_link / _roots / _labels
 // Train-sharded runs use the same pipeline per shard with the vote
 // replaced by a packed (dist, global idx, label) neighbour list, then k_merge_vote.
 #include <hip/hip_runtime.h>
@@ -151,6 +154,14 @@ struct knn_ctx {
     // the int64 scans of the roots [R][n + 1], the summary words [R][4] + unions, and the counts
     // [R][n] a caller did not ask for
     DBuf dbs_tab, dbs_offs, dbs_info, dbs_count;
+    // the spanning tree (knn_mst_*): the top-K lists of all rows; core | dlast fp32 [2][n]; parent | comp |
+    // cand | comphi int32 [4][n]; rowbest | compbest | the edge keys, 64-bit [3][n]; the edge weights'
+    // bits [n]; the counters; the sort's storage.  The cut: parent | root | isroot int32 [3][n], the
+    // int64 scan of the roots [n + 1], the summary words [3]
+    DBuf mst_idx, mst_dist, mst_f, mst_i, mst_u, mst_w, mst_cnt, mst_sort, mst_cut, mst_offs, mst_info;
+    int mst_lists = 1;       // test hook KNN_MST_LISTS=0: no list shortcut, every row through every pass
+    int mst_list_l = -1;     // test hook KNN_MST_LIST_L=n: the list length beyond min_samples (-1: the library's)
+    int64_t mst_summary[4];  // the fit's summary on its way to the device
     // the pass rd_segcnt's counts came from: a fill whose pass has the same key takes them as they
     // are instead of counting again.  (Rows rewritten in place in between are caught where stale
     // counts would matter: the fill checks every (segment, query) count against its own.)
@@ -193,7 +204,7 @@ struct knn_ctx {
     bool stage_open = false;  // the last stage_begin recorded an event (profile = 3 skips some)
     std::vector<float> stage_ms;
     std::vector<const char*> stage_names;
-    int64_t stats[20] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
+    int64_t stats[22] = {0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // candidates, fallback queries, segments, filter
                                                       // operand type, rerun, fused, train / query H2D
                                                       // bytes, train-side filter operands from the cache,
                                                       // MFMA form, queries per wave, [11] the filter's
@@ -205,7 +216,9 @@ struct knn_ctx {
                                                       // pairs its MFMA form evaluated exactly
                                                       // (profile = 2 only), [18] DBSCAN's border
                                                       // candidates, [19] its successful unions
-                                                      // (profile = 2 only)
+                                                      // (profile = 2 only), [20] the spanning
+                                                      // tree's rounds, [21] the rows its rounds
+                                                      // sent through distance passes
     int64_t rerun_stats[4] = {0, -1, 0, 0};  // segments, operand type, fused, operand width of AUTO's gated split re-run
     int num_cus = 256;
 };
@@ -248,7 +261,7 @@ knn_status fail(knn_ctx* c, knn_status s, const char* fmt, ...) {
 static bool hot_stage(const char* n) {
     static const char* const hot[] = {"gemm_filter", "rescore", "direct_tile", "metric_tile", "exact_scan", "merge_vote",
                                       "exchange", "radius_count", "radius_fill", "radius_sweep", "dbscan_link",
-                                      "dbscan_border", "dbscan_sweep_link", "dbscan_sweep_border"};
+                                      "dbscan_border", "dbscan_sweep_link", "dbscan_sweep_border", "mst_pass"};
     for (const char* h : hot)
         if (!strcmp(n, h)) return true;
     return false;
@@ -1168,6 +1181,8 @@ knn_status knn_create(knn_ctx** out, const knn_opts* opts) {
     //   KNN_FUSED_HEAPS    (set) the LDS-heap shape for 32 < k <= 104 at d = 256
     //   KNN_FUSED_PARK=0|1 the int8 filter's parked passes off (the immediate slow path) / on
     //   KNN_FUSED_SEED=0|1 the int8 filter's seeded thresholds (k_seed_thr) off / on
+    //   KNN_MST_LISTS=0|1  the spanning tree's list shortcut off (every row through every pass) / on
+    //   KNN_MST_LIST_L=n   its lists hold max(min_samples, n) entries (0 .. 256; scripts/time_mst.py's study)
     //   KNN_WS_QUERIES=n   queries per pass of the GEMM path's candidate workspace
     //   KNN_BATCH_ROWS=n   query rows per batch of the host pipeline
     if (const char* e = getenv("KNN_RESCORE_SU")) c->rescore_su = atoi(e);
@@ -1175,6 +1190,8 @@ knn_status knn_create(knn_ctx** out, const knn_opts* opts) {
     c->fforce.heaps = getenv("KNN_FUSED_HEAPS") != nullptr;
     if (const char* e = getenv("KNN_FUSED_PARK")) c->fforce.park = atoi(e) != 0 ? 1 : 0;
     if (const char* e = getenv("KNN_FUSED_SEED")) c->fforce.seed = atoi(e) != 0 ? 1 : 0;
+    if (const char* e = getenv("KNN_MST_LISTS")) c->mst_lists = atoi(e) != 0 ? 1 : 0;
+    if (const char* e = getenv("KNN_MST_LIST_L")) c->mst_list_l = std::min(std::max(atoi(e), 0), 256);
     if (c->device < 0 || c->device >= ndev) { delete c; return KNN_ENODEV; }
     hipDeviceProp_t prop;
     if (hipSetDevice(c->device) != hipSuccess || hipGetDeviceProperties(&prop, c->device) != hipSuccess) {
@@ -1227,7 +1244,8 @@ void knn_destroy(knn_ctx* c) {
                     &c->rm_tnorm, &c->rm_tmax, &c->rm_tsmax, &c->rm_tblk, &c->rm_tctrl, &c->rm_qnorm, &c->rm_qstat,
                     &c->rm_qop, &c->rm_exact, &c->lof_idx, &c->lof_dist, &c->lof_cidx, &c->lof_delta, &c->lof_kd,
                     &c->lof_lrd, &c->lof_qlrd, &c->rd_sweep, &c->db_tab, &c->db_offs, &c->db_info, &c->db_count,
-                    &c->dbs_tab, &c->dbs_offs, &c->dbs_info, &c->dbs_count})
+                    &c->dbs_tab, &c->dbs_offs, &c->dbs_info, &c->dbs_count, &c->mst_idx, &c->mst_dist, &c->mst_f,
+                    &c->mst_i, &c->mst_u, &c->mst_w, &c->mst_cnt, &c->mst_sort, &c->mst_cut, &c->mst_offs, &c->mst_info})
         b->release();
     for (hipEvent_t e : c->events) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; i++) {
@@ -1367,7 +1385,7 @@ knn_dataset offset_rows(const knn_dataset& x, int64_t r0, int64_t n) {
 
 void reset_stats(knn_ctx* c) {
     c->stages.clear();
-    for (int i = 0; i < 20; i++) c->stats[i] = 0;
+    for (int i = 0; i < 22; i++) c->stats[i] = 0;
     c->seed_nq = 0;
     c->stats[3] = -1;
 }
@@ -3137,9 +3155,202 @@ knn_status knn_dbscan_sweep_device(knn_ctx* c, const knn_dataset* tr, const floa
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------------
+// The mutual-reachability spanning tree (knn_amd.h "Spanning tree"): the vote-less top-K pass of ALL
+// rows (LOF's) -> k_mst_core -> Boruvka rounds (k_mst_resolve -> k_mst_tile -> pick / hook / flatten,
+// one counter read-back each) -> the sort; and the cut on a tree the caller holds
+// ---------------------------------------------------------------------------------
+namespace {
+
+// the lists hold max(min_samples, L) entries; L chosen among 0 / 16 / 32 (DESIGN.md "Spanning tree", "Measured")
+constexpr int KNN_MST_LIST_L = 32;
+constexpr int KNN_MST_MAX_MIN_SAMPLES = 256;
+
+// finish_call behind the tree's kernels: the status word's texts are this feature's
+knn_status mst_finish(knn_ctx* c, hipStream_t st, const char* what) {
+    const knn_status s = finish_call(c, st);
+    const int32_t status = c->ctrl_host[0];
+    if (s == KNN_EHIP && (status & KNN_STATUS_UF_LIMIT))
+        return fail(c, s, "%s: internal error: a union-find loop reached its iteration cap", what);
+    if (s == KNN_EINVAL && (status & KNN_STATUS_BAD_INDEX)) return fail(c, s, "%s: an edge index is outside [0, n)", what);
+    return s;
+}
+
+}  // namespace
+
 extern "C" {
 
-knn_status knn_predict(knn_ctx* c, const knn_dataset* tr, const knn_dataset* te, int32_t k, int32_t C,
+knn_status knn_mst_device(knn_ctx* c, const knn_dataset* tr, int32_t min_samples, float* d_w, int32_t* d_a, int32_t* d_b,
+                          float* d_core, int64_t* d_summary, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    reset_stats(c);
+    knn_status s;
+    if (min_samples < 1 || min_samples > KNN_MST_MAX_MIN_SAMPLES)
+        return fail(c, KNN_EINVAL, "mst: min_samples=%d outside [1, %d]", min_samples, KNN_MST_MAX_MIN_SAMPLES);
+    if ((s = radius_check(c, tr, tr, 0.0f, -1, false)) != KNN_OK) return s;
+    const int64_t n = tr->n;
+    if (n > 0 && min_samples > n)
+        return fail(c, KNN_EINVAL, "mst: min_samples=%d exceeds the %lld rows", min_samples, (long long)n);
+    if (!d_summary) return fail(c, KNN_EINVAL, "mst: d_summary is NULL");
+    if (n > 1 && (!d_w || !d_a || !d_b)) return fail(c, KNN_EINVAL, "mst: d_w / d_a / d_b is NULL");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (n == 0) {
+        HIP_OR_FAIL(c, hipMemsetAsync(d_summary, 0, sizeof(int64_t) * 4, st));
+        HIP_OR_FAIL(c, hipStreamSynchronize(st));
+        return KNN_OK;
+    }
+    const int K = (int)std::min<int64_t>(std::max(min_samples, c->mst_list_l >= 0 ? c->mst_list_l : KNN_MST_LIST_L), n);
+    knn_dataset trv = *tr;
+    trv.labels = static_cast<const int32_t*>(tr->feat);  // (for the checks; the zero array replaces it below)
+    QueryOut out{nullptr, nullptr, nullptr, nullptr, K, 0};
+    if ((s = validate_call(c, &trv, &trv, K, 1, out, false, false)) != KNN_OK) return s;
+
+    // every buffer before the first launch: a failed allocation leaves the outputs untouched
+    const size_t N = (size_t)n;
+    HIP_OR_FAIL(c, c->mst_idx.ensure(sizeof(int32_t) * N * K));
+    HIP_OR_FAIL(c, c->mst_dist.ensure(sizeof(float) * N * K));
+    HIP_OR_FAIL(c, c->mst_f.ensure(sizeof(float) * 2 * N));
+    HIP_OR_FAIL(c, c->mst_i.ensure(sizeof(int32_t) * 4 * N));
+    HIP_OR_FAIL(c, c->mst_u.ensure(sizeof(unsigned long long) * 3 * N));
+    HIP_OR_FAIL(c, c->mst_w.ensure(sizeof(uint32_t) * N));
+    HIP_OR_FAIL(c, c->mst_cnt.ensure(sizeof(unsigned long long) * MST_CNT_WORDS));
+    HIP_OR_FAIL(c, c->mst_sort.ensure(knn_mst_sort_bytes(n - 1)));
+    MstTables t{};
+    t.idx = c->mst_idx.as<int32_t>(); t.dist = c->mst_dist.as<float>(); t.K = K;
+    t.core = c->mst_f.as<float>(); t.dlast = t.core + N;
+    t.parent = c->mst_i.as<int32_t>(); t.comp = t.parent + N; t.cand = t.comp + N;
+    t.comphi = reinterpret_cast<uint32_t*>(t.cand + N);
+    t.rowbest = c->mst_u.as<unsigned long long>(); t.compbest = t.rowbest + N; t.ekey = t.compbest + N;
+    t.ew = c->mst_w.as<uint32_t>();
+    t.cnt = c->mst_cnt.as<unsigned long long>();
+    t.status = c->ctrl.as<int32_t>();
+
+    // 1. the lists: LOF's vote-less pass with nothing removed (its own stage names), then c and dlast
+    if ((s = zero_labels(c, n, st, &trv.labels)) != KNN_OK) return s;
+    out.idx = c->mst_idx.as<int32_t>();
+    out.dist = c->mst_dist.as<float>();
+    const int algo = choose_algo(c, n, n, trv.d, K, trv.dtype);
+    const bool gemm = is_gemm(algo);
+    const int64_t pass = gemm ? std::max<int64_t>(1, c->ws_queries) : n;
+    for (int64_t q0 = 0; q0 < n; q0 += pass) {
+        const int64_t m = std::min(pass, n - q0);
+        const knn_dataset tq = offset_rows(trv, q0, m);
+        if ((s = predict_enqueue(c, &trv, &tq, K, 1, offset_out(out, q0), st, algo, nullptr)) == KNN_OK)
+            s = finish_call(c, st);
+        // (a row with fewer than K finite distances: its list ends in missing entries, c may be +inf)
+        if (s == KNN_ERANGE) {
+            c->err.clear();
+            s = KNN_OK;
+        }
+        if (s != KNN_OK) {
+            if (s != KNN_EINVAL) c->tprep.valid = c->tpad.valid = false;  // a HIP failure: the operands may be partial
+            return s;
+        }
+        pass_stats(c, c->ctrl_host, gemm);
+    }
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    stage_begin(c, st, "mst_lists");
+    HIP_OR_FAIL(c, hipMemsetAsync(t.cnt, 0, sizeof(unsigned long long) * MST_CNT_WORDS, st));
+    HIP_OR_FAIL(c, knn_launch_mst_core(t, n, min_samples, d_core, st));
+    stage_end(c, st);
+
+    // 2. the rounds.  The pass has the radius pass's direct form and segments.
+    RadiusTileArgs a = radius_args(c, &trv, &trv, 0.0f, -1, 0, 0);
+    int max_rounds = 1;
+    while (((int64_t)1 << (max_rounds - 1)) < n) max_rounds++;  // ceil(log2 n) + 1
+    int64_t E = 0, rounds = 0, pass_rows = 0;
+    while (E < n - 1) {
+        if (rounds == max_rounds)
+            return fail(c, KNN_EHIP, "mst: internal error: %d rounds did not finish the tree", max_rounds);
+        stage_begin(c, st, "mst_resolve");
+        HIP_OR_FAIL(c, hipMemsetAsync(t.cnt, 0, sizeof(unsigned long long) * MST_CNT_EDGES, st));
+        HIP_OR_FAIL(c, hipMemsetAsync(t.rowbest, 0xff, sizeof(unsigned long long) * 2 * N, st));
+        HIP_OR_FAIL(c, hipMemsetAsync(t.comphi, 0xff, sizeof(uint32_t) * N, st));
+        HIP_OR_FAIL(c, knn_launch_mst_resolve(t, n, c->mst_lists, st));
+        stage_end(c, st);
+        stage_begin(c, st, "mst_pass");
+        HIP_OR_FAIL(c, knn_launch_mst_tile(a, t, c->metric, st));
+        stage_end(c, st);
+        stage_begin(c, st, "mst_pick");
+        HIP_OR_FAIL(c, knn_launch_mst_pick_hook(t, n, st));
+        stage_end(c, st);
+        unsigned long long cnt[MST_CNT_WORDS];
+        HIP_OR_FAIL(c, hipMemcpyAsync(cnt, t.cnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        HIP_OR_FAIL(c, hipStreamSynchronize(st));
+        rounds++;
+        pass_rows += (int64_t)cnt[MST_CNT_NB];
+        if (!cnt[MST_CNT_OFFERS]) break;  // no component has a candidate: the forest is complete
+        if (!cnt[MST_CNT_HOOKS] || (int64_t)cnt[MST_CNT_EDGES] > n - 1)
+            return fail(c, KNN_EHIP, "mst: internal error: a round with candidates hooked nothing");
+        E = (int64_t)cnt[MST_CNT_EDGES];
+    }
+
+    // 3. the order (w, a, b), the summary and the last synchronisation
+    stage_begin(c, st, "mst_sort");
+    HIP_OR_FAIL(c, knn_launch_mst_sort(t, E, c->mst_sort.p, d_w, d_a, d_b, st));
+    c->mst_summary[0] = E; c->mst_summary[1] = n - E; c->mst_summary[2] = rounds; c->mst_summary[3] = pass_rows;
+    HIP_OR_FAIL(c, hipMemcpyAsync(d_summary, c->mst_summary, sizeof(int64_t) * 4, hipMemcpyHostToDevice, st));
+    stage_end(c, st);
+    s = mst_finish(c, st, "mst");
+    c->stats[20] = rounds;
+    c->stats[21] = pass_rows;
+    return s;
+}
+
+knn_status knn_mst_cut_device(knn_ctx* c, int64_t n, int64_t n_edges, const float* d_w, const int32_t* d_a,
+                              const int32_t* d_b, const float* d_core, const float* thresholds, int32_t R, int64_t ld_out,
+                              int32_t* d_labels, int64_t* d_summary, void* hip_stream) {
+    if (!c) return KNN_EINVAL;
+    c->err.clear();
+    c->stages.clear();
+    knn_status s;
+    if ((s = sweep_thresholds_check(c, "mst cut", thresholds, R)) != KNN_OK) return s;
+    if (n < 0 || n > 0x7fffffffLL) return fail(c, KNN_EINVAL, "mst cut: n=%lld outside [0, 2^31-1]", (long long)n);
+    if (n_edges < 0 || n_edges > std::max<int64_t>(n - 1, 0))
+        return fail(c, KNN_EINVAL, "mst cut: n_edges=%lld outside [0, n - 1]", (long long)n_edges);
+    if (ld_out < n) return fail(c, KNN_EINVAL, "mst cut: ld_out=%lld < n=%lld", (long long)ld_out, (long long)n);
+    if (n > 0 && (!d_core || !d_labels)) return fail(c, KNN_EINVAL, "mst cut: d_core / d_labels is NULL");
+    if (n_edges > 0 && (!d_w || !d_a || !d_b)) return fail(c, KNN_EINVAL, "mst cut: d_w / d_a / d_b is NULL");
+    HIP_OR_FAIL(c, hipSetDevice(c->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    if (n == 0) {
+        if (d_summary) HIP_OR_FAIL(c, hipMemsetAsync(d_summary, 0, sizeof(int64_t) * 3 * (size_t)R, st));
+        HIP_OR_FAIL(c, hipStreamSynchronize(st));
+        return KNN_OK;
+    }
+    const size_t N = (size_t)n;
+    HIP_OR_FAIL(c, c->mst_cut.ensure(sizeof(int32_t) * 3 * N));
+    HIP_OR_FAIL(c, c->mst_offs.ensure(sizeof(int64_t) * (N + 1)));
+    HIP_OR_FAIL(c, c->mst_info.ensure(sizeof(unsigned long long) * 3));
+    int32_t *parent = c->mst_cut.as<int32_t>(), *root = parent + N, *isroot = root + N;
+    int64_t* offs = c->mst_offs.as<int64_t>();
+    unsigned long long* info = c->mst_info.as<unsigned long long>();
+    int32_t* status = c->ctrl.as<int32_t>();
+    HIP_OR_FAIL(c, reset_ctrl(c, st));
+    stage_begin(c, st, "mst_cut");
+    HIP_OR_FAIL(c, knn_launch_dbscan_init(parent, n, st));
+    // the levels are nested: one forest, carried over; level r adds the edges with thr[r - 1] < w <= thr[r]
+    for (int r = 0; r < R; r++) {
+        HIP_OR_FAIL(c, hipMemsetAsync(info, 0, sizeof(unsigned long long) * 3, st));
+        HIP_OR_FAIL(c, knn_launch_mst_cut_link(d_w, d_a, d_b, n_edges, n, r ? thresholds[r - 1] : -1.0f, thresholds[r], parent,
+                                               status, st));
+        HIP_OR_FAIL(c, knn_launch_mst_cut_roots(parent, d_core, thresholds[r], n, root, isroot, info, status, st));
+        HIP_OR_FAIL(c, knn_launch_radius_scan(isroot, 1, n, nullptr, offs, st));
+        HIP_OR_FAIL(c, knn_launch_mst_cut_labels(root, offs, n, d_labels + (size_t)r * (size_t)ld_out, info, st));
+        if (d_summary)
+            HIP_OR_FAIL(c, hipMemcpyAsync(d_summary + 3 * (size_t)r, info, sizeof(int64_t) * 3, hipMemcpyDeviceToDevice, st));
+    }
+    stage_end(c, st);
+    return mst_finish(c, st, "mst cut");
+}
+
+}  // extern "C"
+
+extern "C" {
+
+knn_status knn_predict(knn_ctx* c,const knn_dataset* tr, const knn_dataset* te, int32_t k, int32_t C,
                        int64_t q_begin, int64_t q_end, int32_t* out_pred, float* out_dist,
                        int32_t* out_idx) {
     if (!c) return KNN_EINVAL;
@@ -3312,7 +3523,7 @@ int32_t knn_stage_times(const knn_ctx* c, const char** names, float* ms, int32_t
 
 int32_t knn_last_stats(const knn_ctx* c, int64_t* out, int32_t n) {
     if (!c || !out) return 0;
-    int32_t m = std::min(n, 20);
+    int32_t m = std::min(n, 22);
     for (int32_t i = 0; i < m; i++) out[i] = c->stats[i];
     return m;
 }

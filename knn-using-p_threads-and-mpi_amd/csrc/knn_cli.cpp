@@ -4,6 +4,7 @@
 //           [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress]
 //           [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]] [--lof[=KLO] [--lof-threshold=T]]
 //           [--dbscan=R [--min-samples=M]] [--dbscan-radii=R1,R2,... [--min-samples=M]]
+//           [--mst[=M] [--mst-cuts=R1,R2,...]]
 //
 // Same positional arguments as ./main (main.cpp:114-122; k parsed with strtol) plus the
 // optional worker count of ./multi-thread (multi-thread.cpp:135-143), here the number of
@@ -51,6 +52,13 @@
 // with --metric=.  With --dbscan=, with any other mode switch, with more than 32 values, a value that
 // is not a number >= 0, values that descend or an M that is no integer >= 1, it prints a usage error
 // and exits 1.
+// --mst[=M] [--mst-cuts=R1,R2,...]: the mutual-reachability spanning tree (KNN_mst) of the train file's
+// rows, min_samples M (default 5); K and the test path keep their positions and are not read.  One line:
+// the edges, the components and the longest edge as a radius; then, per cut radius, --dbscan='s line for
+// DBSCAN* (KNN_mst_cut: the core rows' clusters from the tree alone, border rows not assigned).
+// Composes with --metric=.  With any other mode switch (--min-samples= included), an M that is no integer
+// in [1, 256], cuts without --mst, more than 32 cuts, a cut that is not a number >= 0 or cuts that
+// descend, it prints a usage error and exits 1.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -80,6 +88,9 @@ static int run(int argc, char* argv[]) {
     const char* min_samples_arg = nullptr;
     const char* dbscan_radii_arg = nullptr;
     bool outlier_given = false;
+    bool mst = false;
+    const char* mst_arg = nullptr;
+    const char* mst_cuts_arg = nullptr;
     for (int i = 0; i < argc; i++) {
         if (!std::strncmp(argv[i], "--outlier=", 10)) outlier_given = true;
         if (!std::strncmp(argv[i], "--weights=", 10)) weights_given = true;
@@ -93,6 +104,9 @@ static int run(int argc, char* argv[]) {
         else if (!std::strncmp(argv[i], "--dbscan=", 9)) dbscan_arg = argv[i] + 9;
         else if (!std::strncmp(argv[i], "--dbscan-radii=", 15)) dbscan_radii_arg = argv[i] + 15;
         else if (!std::strncmp(argv[i], "--min-samples=", 14)) min_samples_arg = argv[i] + 14;
+        else if (!std::strcmp(argv[i], "--mst")) mst = true;
+        else if (!std::strncmp(argv[i], "--mst=", 6)) { mst = true; mst_arg = argv[i] + 6; }
+        else if (!std::strncmp(argv[i], "--mst-cuts=", 11)) mst_cuts_arg = argv[i] + 11;
         else if (!std::strncmp(argv[i], "--radius=", 9)) radius_arg = argv[i] + 9;
         else if (!std::strncmp(argv[i], "--radii=", 8)) radii_arg = argv[i] + 8;
         else if (!std::strncmp(argv[i], "--outlier=", 10)) outlier = (int)std::strtol(argv[i] + 10, NULL, 10);
@@ -113,11 +127,39 @@ static int run(int argc, char* argv[]) {
     }
     argc = n;
     if (argc != 4 && argc != 5) {
-        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress] [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]] [--lof[=KLO] [--lof-threshold=T]] [--dbscan=R [--min-samples=M]] [--dbscan-radii=R1,R2,... [--min-samples=M]]"
+        std::cout << "Usage: ./knn_cli datasets/train.arff datasets/test.arff k [numDevices] [--shard=test|train|auto] [--sweep[=loo]] [--weights=uniform|distance|sqdist] [--metric=euclidean|manhattan|chebyshev] [--regress] [--radius=R [--outlier=L]] [--radii=R1,R2,... [--outlier=L]] [--lof[=KLO] [--lof-threshold=T]] [--dbscan=R [--min-samples=M]] [--dbscan-radii=R1,R2,... [--min-samples=M]] [--mst[=M] [--mst-cuts=R1,R2,...]]"
                   << std::endl;
         std::exit(0);
     }
     int k = (int)std::strtol(argv[3], NULL, 10);
+    int mst_m = 5;
+    std::vector<float> mst_cuts;
+    if (mst || mst_cuts_arg) {
+        bool ok = mst && !sweep && !regress && !radius_arg && !radii_arg && !weights_given && !outlier_given && !lof &&
+                  !lof_thr_arg && !dbscan_arg && !dbscan_radii_arg && !min_samples_arg;
+        if (ok && mst_arg) {
+            char* end = nullptr;
+            const long v = std::strtol(mst_arg, &end, 10);
+            ok = end != mst_arg && *end == '\0' && v >= 1 && v <= 256;
+            mst_m = (int)v;
+        }
+        for (const char* p = mst_cuts_arg; ok && p;) {
+            char* end = nullptr;
+            const float r = std::strtof(p, &end);
+            ok = end != p && (*end == ',' || *end == '\0') && r >= 0.0f && mst_cuts.size() < 32 &&  // (NaN fails >=)
+                 (mst_cuts.empty() || r >= mst_cuts.back());
+            if (ok) mst_cuts.push_back(r);
+            if (!ok || *end == '\0') break;
+            p = end + 1;
+        }
+        if (!ok) {
+            std::cerr << "usage: --mst[=M] needs an integer M in [1, 256], --mst-cuts=R1,R2,... (with --mst) 1 to 32 "
+                         "non-decreasing numbers >= 0, and does not combine with --sweep, --weights=, --regress, --radius=, "
+                         "--radii=, --outlier=, --lof, --dbscan=, --dbscan-radii= or --min-samples="
+                      << std::endl;
+            std::exit(1);
+        }
+    }
     float radius = 0.0f;
     if (radius_arg) {
         char* end = nullptr;
@@ -224,10 +266,40 @@ static int run(int argc, char* argv[]) {
     ArffParser parserTrain(argv[1]);
     ArffParser parserTest(argv[2]);
     ArffData* train = parserTrain.parse();
-    ArffData* test = (loo || lof || dbscan_arg || dbscan_radii_arg) ? train : parserTest.parse();
+    ArffData* test = (loo || lof || dbscan_arg || dbscan_radii_arg || mst) ? train : parserTest.parse();
     knn_amd_init();
 
     struct timespec start, end;
+    if (mst) {
+        KnnMst t = KNN_mst(train, mst_m);
+        // (the weights are squared under the Euclidean metric: the longest edge is reported as a radius)
+        const char* metric = std::getenv("KNN_AMD_METRIC");
+        const bool squared = !metric || !std::strcmp(metric, "euclidean");
+        const float longest = t.edges ? (squared ? std::sqrt(t.w[t.edges - 1]) : t.w[t.edges - 1]) : 0.0f;
+        printf("The mutual-reachability spanning tree (min_samples %d) of %s has %ld edges in %ld components, longest %g\n",
+               mst_m, argv[1], t.edges, t.n - t.edges, (double)longest);
+        const int R = (int)mst_cuts.size();
+        if (R) {
+            const long nt = t.n;
+            std::vector<long> summary((size_t)R * 3, 0);
+            int* labels = KNN_mst_cut(t, mst_cuts.data(), R, summary.data());
+            for (int r = 0; r < R; r++)
+                printf("The radius-%g DBSCAN* (min_samples %d) of %s found %ld clusters: %ld core rows, %ld other rows "
+                       "(border rows are not assigned)\n",
+                       (double)mst_cuts[r], mst_m, argv[1], summary[3 * r], summary[3 * r + 1], summary[3 * r + 2]);
+            if (const char* p = std::getenv("KNN_CLI_PRED_OUT")) {  // test hook: one line of n labels per cut
+                FILE* f = std::fopen(p, "w");
+                for (int r = 0; r < R; r++) {
+                    for (long i = 0; i < nt; i++) std::fprintf(f, i ? " %d" : "%d", labels[(size_t)r * nt + i]);
+                    std::fprintf(f, "\n");
+                }
+                std::fclose(f);
+            }
+            std::free(labels);
+        }
+        KNN_mst_free(t);
+        return 0;
+    }
     if (dbscan_radii_arg) {
         const int R = (int)dbscan_radii.size();
         const long nt = train->num_instances();

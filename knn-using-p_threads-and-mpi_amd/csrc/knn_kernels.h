@@ -476,6 +476,55 @@ hipError_t knn_launch_dbscan_sweep_labels(const int32_t* level, const int32_t* r
                                           const int64_t* offs, int R, int64_t n, int64_t ld_out, int32_t* labels,
                                           int64_t* info, hipStream_t st);
 
+// The mutual-reachability spanning tree (knn_mst.hip; knn_amd.h "Spanning tree"): Boruvka rounds over
+// a self-join (test == train, nq == nt).  A candidate of row q is a row t of another component with
+// D(q, t) < FLT_MAX; its key is bits(w) << 32 | t, w = fmaxf(fmaxf(core[q], core[t]), D), and
+// 0xffff...f means "none".
+//   lists idx / dist [n][K]  the rows' plain top-K lists (the row itself included; idx -1: missing)
+//   core / dlast [n]         c(i); the list's last distance, +inf for a list that holds every
+//                            candidate the row has (K == n, or a missing entry)
+//   parent / comp [n]        the union-find forest and its flattened image, comp[i] = root of i
+//   rowbest [n]              the smallest key of a row: stored by k_mst_resolve, atomicMin by the pass
+//   compbest / comphi [n]    per component root: the smallest (bits(w) << 32 | lo) and, among the rows
+//                            that offer it, the smallest hi
+//   cnt int64 [MST_CNT_WORDS] the counters below, on the device
+// (a round zeroes the first three; the edges add up over the rounds)
+enum { MST_CNT_NB = 0, MST_CNT_OFFERS = 1, MST_CNT_HOOKS = 2, MST_CNT_EDGES = 3, MST_CNT_WORDS = 4 };
+struct MstTables {
+    const int32_t* idx; const float* dist; int K;
+    float* core; float* dlast;
+    int32_t* parent; int32_t* comp;
+    unsigned long long* rowbest; unsigned long long* compbest; uint32_t* comphi;
+    int32_t* cand;
+    unsigned long long* ekey; uint32_t* ew;  // the edges in hook order: a << 32 | b (a < b), bits(w)
+    unsigned long long* cnt;
+    int32_t* status;
+};
+// c(i) = entry min_samples - 1 of row i's list, dlast; parent[i] = comp[i] = i
+hipError_t knn_launch_mst_core(const MstTables& t, int64_t n, int32_t min_samples, float* core_out, hipStream_t st);
+// one round's list walk: rowbest of the resolved rows, the others into cand[0 .. cnt[MST_CNT_NB]);
+// use_lists = 0: every row is a candidate.  Zeroes nothing: the caller resets rowbest / compbest /
+// comphi (all ones) and cnt[NB / OFFERS / HOOKS] first.
+hipError_t knn_launch_mst_resolve(const MstTables& t, int64_t n, int use_lists, hipStream_t st);
+// the pass over the candidates (RadiusTileArgs' geometry fields: train / nt / ld_t / d / elem / seg_len /
+// nseg; test / nq / ld_q are set to the train set's here)
+hipError_t knn_launch_mst_tile(RadiusTileArgs a, const MstTables& t, int metric, hipStream_t st);
+// pick (two steps), hook (a successful union appends its edge), flatten
+hipError_t knn_launch_mst_pick_hook(const MstTables& t, int64_t n, hipStream_t st);
+// the E edges sorted by (w, a, b) into w / a / b; temp: knn_mst_sort_bytes(E) bytes
+size_t knn_mst_sort_bytes(int64_t E);
+hipError_t knn_launch_mst_sort(const MstTables& t, int64_t E, void* temp, float* w, int32_t* a, int32_t* b, hipStream_t st);
+// The cut.  link: the edges with lo < w <= hi (lo < 0: no lower bound) are joined in parent; an index
+// outside [0, n) sets KNN_STATUS_BAD_INDEX and is not followed.  number: root / isroot of the rows with
+// core <= thr (-1 / 0 for the others), and info[1] += those rows (info int64 [3], zeroed by the caller)
+hipError_t knn_launch_mst_cut_link(const float* w, const int32_t* a, const int32_t* b, int64_t E, int64_t n, float lo,
+                                   float hi, int32_t* parent, int32_t* status, hipStream_t st);
+hipError_t knn_launch_mst_cut_roots(int32_t* parent, const float* core, float thr, int64_t n, int32_t* root,
+                                    int32_t* isroot, unsigned long long* info, int32_t* status, hipStream_t st);
+// labels [n] from root and the scan of isroot; info[0] = clusters, info[2] = n - info[1]
+hipError_t knn_launch_mst_cut_labels(const int32_t* root, const int64_t* offsets, int64_t n, int32_t* labels,
+                                     unsigned long long* info, hipStream_t st);
+
 struct GenerateArgs {
     void* out; int32_t* labels; int64_t row0; int64_t n; int d; int ld;
     int bf16_out; int kind; uint64_t seed; uint32_t stream; int C;
