@@ -203,6 +203,16 @@ knn_status knn_predict(knn_ctx* ctx, const knn_dataset* train, const knn_dataset
  * `hip_stream` (a hipStream_t; NULL = the context's own stream, a blocking stream: ordered
  * after work issued earlier on the legacy null stream).  Returns after
  * the stream has drained and the device-side status word was checked.
+ *
+ * The stream contract, of this and of every other entry point that takes a `hip_stream`: every
+ * fill, copy, kernel and mid-call read-back of the call is enqueued on that one stream, so the call
+ * is ordered after whatever the caller enqueued there before it (the work that produces its
+ * inputs need not have finished, or started) and after nothing else; its result does not depend
+ * on any other stream or on what is pending there.  Where a call adds into an output the caller
+ * zeroes (a d_correct, d_outliers or d_summary that says so), that zero fill is the caller's work
+ * and must be enqueued on the same stream, or have finished.  The Python wrappers hold their own
+ * tensor work (zero fills, read-backs, conversions) to this rule: with `stream=` given it runs on
+ * that stream, whatever torch's current stream is.
  */
 knn_status knn_predict_device(knn_ctx* ctx, const knn_dataset* train, const knn_dataset* test,
                               int32_t k, int32_t num_classes, int32_t* d_pred,

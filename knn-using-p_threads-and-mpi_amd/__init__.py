@@ -297,6 +297,20 @@ def _stream_arg(stream, tensor):
     return None if stream is None else ctypes.c_void_p(stream)
 
 
+def _torch_on(stream, tensor):
+    """The context a wrapper does its own torch work under (a zero fill, an .item() read-back, a
+    dtype conversion, a temporary): torch's current stream becomes the call's stream= when one is
+    given, so the result does not depend on what torch's current stream is or on what is pending
+    there.  Without stream= the call runs on torch's current stream already."""
+    import contextlib
+    if stream is None or not getattr(tensor, "is_cuda", False):
+        return contextlib.nullcontext()
+    import torch
+    dev = tensor.device
+    # (handle 0 is the legacy null stream, torch's default stream)
+    return torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev))
+
+
 def _outputs(nq, k, pred=None, dist=None, idx=None):
     """Type/shape checks of device outputs (pred int32 [nq], dist float32 / idx int32 [nq][k])."""
     import torch
@@ -912,21 +926,22 @@ class Context:
         voting = labels is not None
         if (voting or class_counts) and (labels is None or num_classes is None):
             raise KnnError(KNN_EINVAL, "class outputs need labels and num_classes")
-        count = torch.empty(te.n, dtype=torch.int32, device=dev)
-        pred = torch.empty(te.n, dtype=torch.int32, device=dev) if voting else None
-        correct = None
-        if query_labels is not None:
-            if not voting:
-                raise KnnError(KNN_EINVAL, "query_labels need labels and num_classes")
-            _check_tensor(query_labels, "query_labels", torch.int32, te.n)
-            correct = torch.zeros(1, dtype=torch.int64, device=dev)
-        cc = torch.empty((te.n, num_classes), dtype=torch.int32, device=dev) if class_counts else None
-        off = torch.empty(te.n + 1, dtype=torch.int64, device=dev) if offsets else None
-        self._check(self.lib.knn_radius_count_device(
-            self.h, ctypes.byref(tr), ctypes.byref(te), thr, num_classes or 0, _self_base(self_base), outlier_label,
-            _opt_ptr(query_labels), count.data_ptr(), _opt_ptr(cc), _opt_ptr(pred), _opt_ptr(correct), _opt_ptr(off),
-            self._stream(stream, test)))
-        return count, pred, correct, cc, off
+        with _torch_on(stream, test):
+            count = torch.empty(te.n, dtype=torch.int32, device=dev)
+            pred = torch.empty(te.n, dtype=torch.int32, device=dev) if voting else None
+            correct = None
+            if query_labels is not None:
+                if not voting:
+                    raise KnnError(KNN_EINVAL, "query_labels need labels and num_classes")
+                _check_tensor(query_labels, "query_labels", torch.int32, te.n)
+                correct = torch.zeros(1, dtype=torch.int64, device=dev)
+            cc = torch.empty((te.n, num_classes), dtype=torch.int32, device=dev) if class_counts else None
+            off = torch.empty(te.n + 1, dtype=torch.int64, device=dev) if offsets else None
+            self._check(self.lib.knn_radius_count_device(
+                self.h, ctypes.byref(tr), ctypes.byref(te), thr, num_classes or 0, _self_base(self_base), outlier_label,
+                _opt_ptr(query_labels), count.data_ptr(), _opt_ptr(cc), _opt_ptr(pred), _opt_ptr(correct), _opt_ptr(off),
+                self._stream(stream, test)))
+            return count, pred, correct, cc, off
 
     def radius_fill_device(self, train, test, offsets, radius=None, threshold=None, self_base=None,
                            return_distance=True, stream=None, d=None):
@@ -937,14 +952,15 @@ class Context:
         thr = self._threshold(radius, threshold)
         tr, te = self._datasets_arg(train, None, test, d)
         _check_tensor(offsets, "offsets", torch.int64, te.n + 1)
-        total = int(offsets[te.n].item())
-        # (at least one element: an empty tensor has no address to hand to the library)
-        idx = torch.empty(max(total, 1), dtype=torch.int32, device=test.device)
-        dist = torch.empty(max(total, 1), dtype=torch.float32, device=test.device) if return_distance else None
-        self._check(self.lib.knn_radius_fill_device(
-            self.h, ctypes.byref(tr), ctypes.byref(te), thr, _self_base(self_base), offsets.data_ptr(),
-            idx.data_ptr(), _opt_ptr(dist), self._stream(stream, test)))
-        return idx[:total], None if dist is None else dist[:total]
+        with _torch_on(stream, test):
+            total = int(offsets[te.n].item())
+            # (at least one element: an empty tensor has no address to hand to the library)
+            idx = torch.empty(max(total, 1), dtype=torch.int32, device=test.device)
+            dist = torch.empty(max(total, 1), dtype=torch.float32, device=test.device) if return_distance else None
+            self._check(self.lib.knn_radius_fill_device(
+                self.h, ctypes.byref(tr), ctypes.byref(te), thr, _self_base(self_base), offsets.data_ptr(),
+                idx.data_ptr(), _opt_ptr(dist), self._stream(stream, test)))
+            return idx[:total], None if dist is None else dist[:total]
 
     def radius_neighbors_device(self, train, test, radius=None, threshold=None, self_base=None, return_distance=True,
                                 stream=None, d=None):
@@ -971,17 +987,18 @@ class Context:
         if dist is not None:
             _check_tensor(dist, "dist", torch.float32, idx.numel())
         _check_tensor(train_labels, "train_labels", torch.int32)
-        pred = torch.empty(nq, dtype=torch.int32, device=idx.device)
-        scores = self._scores_arg(scores, nq, num_classes, idx.device)
-        correct = None
-        if query_labels is not None:
-            _check_tensor(query_labels, "query_labels", torch.int32, nq)
-            correct = torch.zeros(1, dtype=torch.int64, device=idx.device)
-        self._check(self.lib.knn_radius_vote_device(
-            self.h, nq, train_labels.numel(), offsets.data_ptr(), idx.data_ptr(), _opt_ptr(dist),
-            train_labels.data_ptr(), num_classes, _weight_kind(weights), outlier_label, _opt_ptr(query_labels),
-            pred.data_ptr(), _opt_ptr(correct), _opt_ptr(scores), self._stream(stream, idx)))
-        return pred, correct, scores
+        with _torch_on(stream, idx):
+            pred = torch.empty(nq, dtype=torch.int32, device=idx.device)
+            scores = self._scores_arg(scores, nq, num_classes, idx.device)
+            correct = None
+            if query_labels is not None:
+                _check_tensor(query_labels, "query_labels", torch.int32, nq)
+                correct = torch.zeros(1, dtype=torch.int64, device=idx.device)
+            self._check(self.lib.knn_radius_vote_device(
+                self.h, nq, train_labels.numel(), offsets.data_ptr(), idx.data_ptr(), _opt_ptr(dist),
+                train_labels.data_ptr(), num_classes, _weight_kind(weights), outlier_label, _opt_ptr(query_labels),
+                pred.data_ptr(), _opt_ptr(correct), _opt_ptr(scores), self._stream(stream, idx)))
+            return pred, correct, scores
 
     def radius_regress_vote_device(self, offsets, idx, dist, train_targets, weights="uniform", stream=None):
         """The regression alone on CSR lists the caller holds (knn_radius_regress_device): pred
@@ -1008,18 +1025,19 @@ class Context:
         [1].  "uniform" takes the count pass alone (no lists are built; the scores are the class
         counts as floats); the weighted kinds run count, fill and the vote on the lists."""
         import torch
-        if _weight_kind(weights) == WEIGHTS["uniform"]:
-            count, pred, correct, cc, _ = self.radius_count_device(
-                train, labels, test, radius, threshold, num_classes, query_labels, self_base, outlier_label,
-                class_counts=bool(scores), stream=stream, d=d)
-            sc = cc.to(torch.float32) if cc is not None else None
-        else:
-            count, _, _, _, off = self.radius_count_device(train, None, test, radius, threshold,
-                                                           self_base=self_base, offsets=True, stream=stream, d=d)
-            idx, dist = self.radius_fill_device(train, test, off, radius, threshold, self_base, True, stream, d)
-            pred, correct, sc = self.radius_vote_device(off, idx, dist, labels, num_classes, weights, outlier_label,
-                                                        query_labels, scores, stream)
-        return (pred, sc, count) if query_labels is None else (pred, sc, count, correct)
+        with _torch_on(stream, test):
+            if _weight_kind(weights) == WEIGHTS["uniform"]:
+                count, pred, correct, cc, _ = self.radius_count_device(
+                    train, labels, test, radius, threshold, num_classes, query_labels, self_base, outlier_label,
+                    class_counts=bool(scores), stream=stream, d=d)
+                sc = cc.to(torch.float32) if cc is not None else None
+            else:
+                count, _, _, _, off = self.radius_count_device(train, None, test, radius, threshold,
+                                                               self_base=self_base, offsets=True, stream=stream, d=d)
+                idx, dist = self.radius_fill_device(train, test, off, radius, threshold, self_base, True, stream, d)
+                pred, correct, sc = self.radius_vote_device(off, idx, dist, labels, num_classes, weights, outlier_label,
+                                                            query_labels, scores, stream)
+            return (pred, sc, count) if query_labels is None else (pred, sc, count, correct)
 
     def radius_loo_device(self, train, labels, radius=None, threshold=None, num_classes=None, weights="uniform",
                           outlier_label=-1, scores=True, stream=None, d=None):
@@ -1061,11 +1079,12 @@ class Context:
         self._on_device(train)
         self._note_train(train)
         tr = _device_dataset(train, None, d)
-        labels, count, summary = self._dbscan_out(tr.n, labels, count, train.device)
-        self._check(self.lib.knn_dbscan_device(
-            self.h, ctypes.byref(tr), thr, int(min_samples), labels.data_ptr(), _opt_ptr(count), summary.data_ptr(),
-            self._stream(stream, train)))
-        return labels, count, summary
+        with _torch_on(stream, train):
+            labels, count, summary = self._dbscan_out(tr.n, labels, count, train.device)
+            self._check(self.lib.knn_dbscan_device(
+                self.h, ctypes.byref(tr), thr, int(min_samples), labels.data_ptr(), _opt_ptr(count), summary.data_ptr(),
+                self._stream(stream, train)))
+            return labels, count, summary
 
     def dbscan_lists_device(self, offsets, idx, min_samples=5, labels=None, count=False, stream=None):
         """The same clustering on CSR lists the caller holds (knn_dbscan_lists_device): offsets int64
@@ -1079,13 +1098,14 @@ class Context:
         if int(min_samples) != min_samples:
             raise KnnError(KNN_EINVAL, f"min_samples must be an integer, got {min_samples!r}")
         n = offsets.numel() - 1
-        labels, count, summary = self._dbscan_out(n, labels, count, idx.device)
-        # (at least one element: an empty tensor has no address to hand to the library)
-        ip = idx if idx.numel() else torch.zeros(1, dtype=torch.int32, device=idx.device)
-        self._check(self.lib.knn_dbscan_lists_device(
-            self.h, n, offsets.data_ptr(), ip.data_ptr(), int(min_samples), labels.data_ptr(), _opt_ptr(count),
-            summary.data_ptr(), self._stream(stream, idx)))
-        return labels, count, summary
+        with _torch_on(stream, idx):
+            labels, count, summary = self._dbscan_out(n, labels, count, idx.device)
+            # (at least one element: an empty tensor has no address to hand to the library)
+            ip = idx if idx.numel() else torch.zeros(1, dtype=torch.int32, device=idx.device)
+            self._check(self.lib.knn_dbscan_lists_device(
+                self.h, n, offsets.data_ptr(), ip.data_ptr(), int(min_samples), labels.data_ptr(), _opt_ptr(count),
+                summary.data_ptr(), self._stream(stream, idx)))
+            return labels, count, summary
 
     def dbscan_sweep_device(self, train, radii=None, thresholds=None, min_samples=5, labels=None, count=False,
                             stream=None, d=None):
@@ -1115,12 +1135,13 @@ class Context:
             ld = labels.stride(0) if labels.shape[0] > 1 else max(labels.shape[1], 1)
             if labels.shape[1] < n:
                 ld = labels.shape[1]  # (the library refuses ld_out < n)
-        cnt = torch.empty((rows, max(ld, 1)), dtype=torch.int32, device=dev) if count else None
-        summary = torch.zeros((rows, 4), dtype=torch.int64, device=dev)
-        self._check(self.lib.knn_dbscan_sweep_device(
-            self.h, ctypes.byref(tr), thr.ctypes.data_as(ctypes.c_void_p), R, int(min_samples), ld, labels.data_ptr(),
-            _opt_ptr(cnt), summary.data_ptr(), self._stream(stream, train)))
-        return labels, (None if cnt is None else cnt[:, :n]), summary
+        with _torch_on(stream, train):
+            cnt = torch.empty((rows, max(ld, 1)), dtype=torch.int32, device=dev) if count else None
+            summary = torch.zeros((rows, 4), dtype=torch.int64, device=dev)
+            self._check(self.lib.knn_dbscan_sweep_device(
+                self.h, ctypes.byref(tr), thr.ctypes.data_as(ctypes.c_void_p), R, int(min_samples), ld, labels.data_ptr(),
+                _opt_ptr(cnt), summary.data_ptr(), self._stream(stream, train)))
+            return labels, (None if cnt is None else cnt[:, :n]), summary
 
     # the mutual-reachability spanning tree (knn_amd.h "Spanning tree")
     def mst_device(self, train, min_samples=5, core=False, w=None, a=None, b=None, stream=None, d=None):
@@ -1140,16 +1161,17 @@ class Context:
         tr = _device_dataset(train, None, d)
         n, dev = tr.n, train.device
         m = max(n - 1, 1)
-        w = torch.empty(m, dtype=torch.float32, device=dev) if w is None else _check_tensor(w, "w", torch.float32, m)
-        a = torch.empty(m, dtype=torch.int32, device=dev) if a is None else _check_tensor(a, "a", torch.int32, m)
-        b = torch.empty(m, dtype=torch.int32, device=dev) if b is None else _check_tensor(b, "b", torch.int32, m)
-        c = torch.empty(max(n, 1), dtype=torch.float32, device=dev)[:n] if core else None
-        summary = torch.zeros(4, dtype=torch.int64, device=dev)
-        self._check(self.lib.knn_mst_device(
-            self.h, ctypes.byref(tr), int(min_samples), w.data_ptr(), a.data_ptr(), b.data_ptr(), _opt_ptr(c),
-            summary.data_ptr(), self._stream(stream, train)))
-        E = int(summary[0].item())
-        return w[:E], a[:E], b[:E], c, summary
+        with _torch_on(stream, train):
+            w = torch.empty(m, dtype=torch.float32, device=dev) if w is None else _check_tensor(w, "w", torch.float32, m)
+            a = torch.empty(m, dtype=torch.int32, device=dev) if a is None else _check_tensor(a, "a", torch.int32, m)
+            b = torch.empty(m, dtype=torch.int32, device=dev) if b is None else _check_tensor(b, "b", torch.int32, m)
+            c = torch.empty(max(n, 1), dtype=torch.float32, device=dev)[:n] if core else None
+            summary = torch.zeros(4, dtype=torch.int64, device=dev)
+            self._check(self.lib.knn_mst_device(
+                self.h, ctypes.byref(tr), int(min_samples), w.data_ptr(), a.data_ptr(), b.data_ptr(), _opt_ptr(c),
+                summary.data_ptr(), self._stream(stream, train)))
+            E = int(summary[0].item())
+            return w[:E], a[:E], b[:E], c, summary
 
     def mst_cut_device(self, w, a, b, core, radii=None, thresholds=None, labels=None, stream=None):
         """DBSCAN* at every one of R <= 32 non-decreasing radii from a tree mst_device returned, with no
@@ -1179,14 +1201,15 @@ class Context:
             ld = labels.stride(0) if labels.shape[0] > 1 else max(labels.shape[1], 1)
             if labels.shape[1] < n:
                 ld = labels.shape[1]  # (the library refuses ld_out < n)
-        summary = torch.zeros((rows, 3), dtype=torch.int64, device=dev)
-        # (at least one element: an empty tensor has no address to hand to the library)
-        one = lambda t: t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev)
-        self._check(self.lib.knn_mst_cut_device(
-            self.h, n, E, one(w).data_ptr(), one(a).data_ptr(), one(b).data_ptr(), one(core).data_ptr(),
-            thr.ctypes.data_as(ctypes.c_void_p), R, ld, labels.data_ptr(), summary.data_ptr(),
-            self._stream(stream, core)))
-        return labels, summary
+        with _torch_on(stream, core):
+            summary = torch.zeros((rows, 3), dtype=torch.int64, device=dev)
+            # (at least one element: an empty tensor has no address to hand to the library)
+            one = lambda t: t if t.numel() else torch.zeros(1, dtype=t.dtype, device=dev)
+            self._check(self.lib.knn_mst_cut_device(
+                self.h, n, E, one(w).data_ptr(), one(a).data_ptr(), one(b).data_ptr(), one(core).data_ptr(),
+                thr.ctypes.data_as(ctypes.c_void_p), R, ld, labels.data_ptr(), summary.data_ptr(),
+                self._stream(stream, core)))
+            return labels, summary
 
     # radius sweep (knn_amd.h "Radius sweep")
     def _thresholds(self, radii, thresholds):
@@ -1228,35 +1251,36 @@ class Context:
             _check_tensor(query_labels, "query_labels", torch.int32, nq)
         C = num_classes if voting else 0
         rows = max(R, 1)
-        count = torch.empty((rows, nq), dtype=torch.int32, device=dev)
-        pred = torch.empty((rows, nq), dtype=torch.int32, device=dev) if voting else None
-        correct = torch.zeros(rows, dtype=torch.int64, device=dev) if query_labels is not None else None
-        outliers = torch.zeros(rows, dtype=torch.int64, device=dev)
-        cc = torch.empty((rows, nq, num_classes), dtype=torch.int32, device=dev) if class_counts else None
-        if query_block is None:
-            query_block = int(self.lib.knn_radius_sweep_max_queries(self.h, R, C)) if 1 <= R <= 32 else max(nq, 1)
-        if query_block < 1:
-            raise KnnError(KNN_EINVAL, f"query_block must be >= 1, got {query_block}")
-        st = self._stream(stream, test)
-        thr_p = thr.ctypes.data_as(ctypes.c_void_p)
-        q0 = 0
-        while True:  # (nq = 0: one call, for the library's checks)
-            n = min(query_block, nq - q0)
-            # (an empty tensor has no address)
-            tq = knn_dataset((te.feat or 0) + q0 * te.ld * (2 if te.dtype == KNN_BF16 else 4), None, n, te.d, te.ld,
-                             te.dtype)
-            self._check(self.lib.knn_radius_sweep_count_device(
-                self.h, ctypes.byref(tr), ctypes.byref(tq), thr_p, R, C,
-                -1 if self_base is None else self_base + q0, outlier_label,
-                None if query_labels is None or nq == 0 else query_labels.data_ptr() + 4 * q0, nq,
-                count.data_ptr() + 4 * q0, None if cc is None else cc.data_ptr() + 4 * q0 * num_classes,
-                None if pred is None else pred.data_ptr() + 4 * q0, _opt_ptr(correct) if nq else None,
-                outliers.data_ptr(), st))
-            q0 += n
-            if q0 >= nq:
-                break
-        out = (count, pred, correct, outliers)
-        return out + (cc,) if class_counts else out
+        with _torch_on(stream, test):
+            count = torch.empty((rows, nq), dtype=torch.int32, device=dev)
+            pred = torch.empty((rows, nq), dtype=torch.int32, device=dev) if voting else None
+            correct = torch.zeros(rows, dtype=torch.int64, device=dev) if query_labels is not None else None
+            outliers = torch.zeros(rows, dtype=torch.int64, device=dev)
+            cc = torch.empty((rows, nq, num_classes), dtype=torch.int32, device=dev) if class_counts else None
+            if query_block is None:
+                query_block = int(self.lib.knn_radius_sweep_max_queries(self.h, R, C)) if 1 <= R <= 32 else max(nq, 1)
+            if query_block < 1:
+                raise KnnError(KNN_EINVAL, f"query_block must be >= 1, got {query_block}")
+            st = self._stream(stream, test)
+            thr_p = thr.ctypes.data_as(ctypes.c_void_p)
+            q0 = 0
+            while True:  # (nq = 0: one call, for the library's checks)
+                n = min(query_block, nq - q0)
+                # (an empty tensor has no address)
+                tq = knn_dataset((te.feat or 0) + q0 * te.ld * (2 if te.dtype == KNN_BF16 else 4), None, n, te.d, te.ld,
+                                 te.dtype)
+                self._check(self.lib.knn_radius_sweep_count_device(
+                    self.h, ctypes.byref(tr), ctypes.byref(tq), thr_p, R, C,
+                    -1 if self_base is None else self_base + q0, outlier_label,
+                    None if query_labels is None or nq == 0 else query_labels.data_ptr() + 4 * q0, nq,
+                    count.data_ptr() + 4 * q0, None if cc is None else cc.data_ptr() + 4 * q0 * num_classes,
+                    None if pred is None else pred.data_ptr() + 4 * q0, _opt_ptr(correct) if nq else None,
+                    outliers.data_ptr(), st))
+                q0 += n
+                if q0 >= nq:
+                    break
+            out = (count, pred, correct, outliers)
+            return out + (cc,) if class_counts else out
 
     def radius_sweep_loo_device(self, train, labels, radii=None, thresholds=None, num_classes=None,
                                 outlier_label=-1, class_counts=False, query_block=None, stream=None, d=None):
@@ -1284,18 +1308,19 @@ class Context:
         _check_tensor(dist, "dist", torch.float32, idx.numel())
         _check_tensor(train_labels, "train_labels", torch.int32)
         rows = max(R, 1)
-        pred = torch.empty((rows, nq), dtype=torch.int32, device=idx.device)
-        sc = torch.empty((rows, nq, num_classes), dtype=torch.float32, device=idx.device) if scores else None
-        correct = None
-        if query_labels is not None:
-            _check_tensor(query_labels, "query_labels", torch.int32, nq)
-            correct = torch.zeros(rows, dtype=torch.int64, device=idx.device)
-        self._check(self.lib.knn_radius_vote_sweep_device(
-            self.h, nq, train_labels.numel(), offsets.data_ptr(), idx.data_ptr(), dist.data_ptr(),
-            train_labels.data_ptr(), num_classes, _weight_kind(weights), thr.ctypes.data_as(ctypes.c_void_p), R,
-            outlier_label, _opt_ptr(query_labels), nq, pred.data_ptr(), _opt_ptr(correct), _opt_ptr(sc),
-            self._stream(stream, idx)))
-        return pred, correct, sc
+        with _torch_on(stream, idx):
+            pred = torch.empty((rows, nq), dtype=torch.int32, device=idx.device)
+            sc = torch.empty((rows, nq, num_classes), dtype=torch.float32, device=idx.device) if scores else None
+            correct = None
+            if query_labels is not None:
+                _check_tensor(query_labels, "query_labels", torch.int32, nq)
+                correct = torch.zeros(rows, dtype=torch.int64, device=idx.device)
+            self._check(self.lib.knn_radius_vote_sweep_device(
+                self.h, nq, train_labels.numel(), offsets.data_ptr(), idx.data_ptr(), dist.data_ptr(),
+                train_labels.data_ptr(), num_classes, _weight_kind(weights), thr.ctypes.data_as(ctypes.c_void_p), R,
+                outlier_label, _opt_ptr(query_labels), nq, pred.data_ptr(), _opt_ptr(correct), _opt_ptr(sc),
+                self._stream(stream, idx)))
+            return pred, correct, sc
 
     def radius_sweep_predict_device(self, train, labels, test, radii=None, thresholds=None, num_classes=None,
                                     weights="uniform", outlier_label=-1, query_labels=None, self_base=None,
@@ -1307,28 +1332,29 @@ class Context:
         sweep on them."""
         import torch
         thr = self._thresholds(radii, thresholds)
-        if _weight_kind(weights) == WEIGHTS["uniform"]:
-            out = self.radius_sweep_device(train, labels, test, None, thr, num_classes, query_labels, self_base,
-                                           outlier_label, class_counts=bool(scores), stream=stream, d=d)
-            count, pred, correct = out[0], out[1], out[2]
-            sc = out[4].to(torch.float32) if scores else None
-        else:
-            if not 1 <= thr.size <= 32:
-                raise KnnError(KNN_EINVAL, f"{thr.size} thresholds outside [1, 32]")
-            top = float(thr[-1])
-            off, idx, dist = self.radius_neighbors_device(train, test, threshold=top, self_base=self_base,
-                                                          stream=stream, d=d)
-            pred, correct, sc = self.radius_vote_sweep_device(off, idx, dist, labels, num_classes, None, thr, weights,
-                                                              outlier_label, query_labels, scores, stream)
-            # count[r][q]: the entries of q's list within thr[r]
-            nq = off.numel() - 1
-            seg = torch.repeat_interleave(torch.arange(nq, device=idx.device), (off[1:] - off[:-1]))
-            t = torch.from_numpy(thr).to(idx.device)
-            count = torch.zeros((thr.size, nq), dtype=torch.int32, device=idx.device)
-            if idx.numel():
-                inside = (dist[None, :] <= t[:, None]).to(torch.int32)
-                count.index_add_(1, seg, inside)
-        return (pred, sc, count) if query_labels is None else (pred, sc, count, correct)
+        with _torch_on(stream, test):
+            if _weight_kind(weights) == WEIGHTS["uniform"]:
+                out = self.radius_sweep_device(train, labels, test, None, thr, num_classes, query_labels, self_base,
+                                               outlier_label, class_counts=bool(scores), stream=stream, d=d)
+                count, pred, correct = out[0], out[1], out[2]
+                sc = out[4].to(torch.float32) if scores else None
+            else:
+                if not 1 <= thr.size <= 32:
+                    raise KnnError(KNN_EINVAL, f"{thr.size} thresholds outside [1, 32]")
+                top = float(thr[-1])
+                off, idx, dist = self.radius_neighbors_device(train, test, threshold=top, self_base=self_base,
+                                                              stream=stream, d=d)
+                pred, correct, sc = self.radius_vote_sweep_device(off, idx, dist, labels, num_classes, None, thr, weights,
+                                                                  outlier_label, query_labels, scores, stream)
+                # count[r][q]: the entries of q's list within thr[r]
+                nq = off.numel() - 1
+                seg = torch.repeat_interleave(torch.arange(nq, device=idx.device), (off[1:] - off[:-1]))
+                t = torch.from_numpy(thr).to(idx.device)
+                count = torch.zeros((thr.size, nq), dtype=torch.int32, device=idx.device)
+                if idx.numel():
+                    inside = (dist[None, :] <= t[:, None]).to(torch.int32)
+                    count.index_add_(1, seg, inside)
+            return (pred, sc, count) if query_labels is None else (pred, sc, count, correct)
 
     def radius_regress_device(self, train, targets, test, radius=None, threshold=None, weights="uniform",
                               self_base=None, stream=None, d=None):
@@ -1366,14 +1392,15 @@ class Context:
         import torch
         _check_tensor(pred, "pred", torch.int32)
         _check_tensor(labels, "labels", torch.int32, pred.shape[0])
-        if cm is None:
-            cm = torch.empty((num_classes, num_classes), dtype=torch.int32, device=pred.device)
-        corr = torch.zeros(1, dtype=torch.int64, device=pred.device)
-        self._check(self.lib.knn_confusion_matrix_device(
-            self.h, pred.data_ptr(), labels.data_ptr(), pred.shape[0], num_classes, cm.data_ptr(),
-            corr.data_ptr(), self._stream(stream, pred)))
-        n = pred.shape[0]
-        return cm, float(np.float32(int(corr.item())) / np.float32(n)) if n else float("nan")
+        with _torch_on(stream, pred):
+            if cm is None:
+                cm = torch.empty((num_classes, num_classes), dtype=torch.int32, device=pred.device)
+            corr = torch.zeros(1, dtype=torch.int64, device=pred.device)
+            self._check(self.lib.knn_confusion_matrix_device(
+                self.h, pred.data_ptr(), labels.data_ptr(), pred.shape[0], num_classes, cm.data_ptr(),
+                corr.data_ptr(), self._stream(stream, pred)))
+            n = pred.shape[0]
+            return cm, float(np.float32(int(corr.item())) / np.float32(n)) if n else float("nan")
 
     def mfma_probe_bf16(self, a, b, stream=None):
         """The bf16 filter's MFMA chain on device operands a, b: [32][K] torch.bfloat16
@@ -1381,11 +1408,12 @@ class Context:
         import torch
         if a.shape != b.shape or a.dim() != 2 or a.shape[0] != 32 or a.dtype != torch.bfloat16:
             raise KnnError(KNN_EINVAL, "a, b must be [32][K] bfloat16")
-        a, b = a.contiguous(), b.contiguous()
-        out = torch.empty((32, 32), dtype=torch.float32, device=a.device)
-        self._check(self.lib.knn_mfma_probe_bf16(self.h, a.data_ptr(), b.data_ptr(), a.shape[1], out.data_ptr(),
-                                                 self._stream(stream, a)))
-        return out
+        with _torch_on(stream, a):
+            a, b = a.contiguous(), b.contiguous()
+            out = torch.empty((32, 32), dtype=torch.float32, device=a.device)
+            self._check(self.lib.knn_mfma_probe_bf16(self.h, a.data_ptr(), b.data_ptr(), a.shape[1], out.data_ptr(),
+                                                     self._stream(stream, a)))
+            return out
 
     def mfma_probe_i8(self, a, b, stream=None):
         """The int8 filter's MFMA chain on device operands a, b: [32][K] torch.int8 (K % 32 == 0)
@@ -1393,11 +1421,12 @@ class Context:
         import torch
         if a.shape != b.shape or a.dim() != 2 or a.shape[0] != 32 or a.dtype != torch.int8 or b.dtype != torch.int8:
             raise KnnError(KNN_EINVAL, "a, b must be [32][K] int8")
-        a, b = a.contiguous(), b.contiguous()
-        out = torch.empty((32, 32), dtype=torch.int32, device=a.device)
-        self._check(self.lib.knn_mfma_probe_i8(self.h, a.data_ptr(), b.data_ptr(), a.shape[1], out.data_ptr(),
-                                               self._stream(stream, a)))
-        return out
+        with _torch_on(stream, a):
+            a, b = a.contiguous(), b.contiguous()
+            out = torch.empty((32, 32), dtype=torch.int32, device=a.device)
+            self._check(self.lib.knn_mfma_probe_i8(self.h, a.data_ptr(), b.data_ptr(), a.shape[1], out.data_ptr(),
+                                                   self._stream(stream, a)))
+            return out
 
     def _set_i8_coarsen(self, mul):
         """Test hook: the int8 filter's quantisation step times mul (1 <= mul <= 8) from now on."""
